@@ -24,6 +24,12 @@ ends only after the last gather has completed.
 `python bench.py --gpus N` starts its own N rank processes (children, spawned before anything touches
 the GPU); under torch.distributed.run (WORLD_SIZE already set) it is one of the ranks.
 
+A plain run sets up, warms up, times the K steps and prints the headline.  `--full` adds everything else the
+line can carry: the CPU baseline and the parity classification of its sample, the reference-order / fast /
+branch comparison, the deviation from the reference's own runs, the global-QP, min-time NLP and QSS legs, and
+(N > 1) the bit checksums of the gathered shards.  `--dump-outputs DIR` writes what the last timed step
+returned to its caller as DIR/<group>_<array>.npy (float64; see dump_outputs).
+
 Prints ONE JSON line (rank 0).  See the repo instructions for the field contract.
 """
 import argparse
@@ -573,6 +579,25 @@ def valu_block(prof, kernel_ms):
     return out
 
 
+DUMP_BUDGET_BYTES = 60_000_000   # the arrays of --dump-outputs, under 64 MB with room for the sample indices
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` (name -> array, leading axis = instance) as path/<name>.npy in float64 -- exact for the
+    int32 counters too.  Above DUMP_BUDGET_BYTES in all (only the gathered xy of many ranks gets there), each array keeps
+    the same share of its instances, a fixed seeded sample, whose indices go to path/<name>_index.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k_: np.ascontiguousarray(v_, dtype=np.float64) for k_, v_ in arrays.items()}
+    total = sum(a_.nbytes for a_ in arrays.values())
+    keep = min(1.0, DUMP_BUDGET_BYTES / total)
+    for name, a_ in arrays.items():
+        if keep < 1.0:
+            idx = np.sort(np.random.default_rng(0).choice(a_.shape[0], int(a_.shape[0] * keep), replace=False))
+            np.save(os.path.join(path, f"{name}_index.npy"), idx.astype(np.float64))
+            a_ = a_[idx]
+        np.save(os.path.join(path, f"{name}.npy"), a_)
+
+
 # ------------------------------------------------------------------------------------------------
 def run_rank(args):
     import torch
@@ -737,7 +762,7 @@ def run_rank(args):
         assert np.isfinite(xy).all()
         assert np.array_equal(status, 2 * MAX_ITER * (g["n"] - g["k"]) - ns.reshape(bg, -1).sum(axis=1))
         xy_gpu.append(xy); ns_gpu.append(ns)
-        if gi == 0 and ref_run:
+        if gi == 0 and ref_run and args.full:
             ctrl0 = last["ctrl"].cpu().numpy()
             dev_ref = {bi: float(np.hypot(ctrl0[bi, :, 0] - rc[0], ctrl0[bi, :, 1] - rc[1]).max()) for bi, rc in ref_run.items()}
 
@@ -749,7 +774,7 @@ def run_rank(args):
         return torch.stack([v.sum(), torch.bitwise_xor(v, v >> 29).sum()])
 
     gather_check = None
-    if world > 1:
+    if world > 1 and args.full:
         chk = torch.stack([torch.cat([bit_checksums(g["out"][last_slot]["xy"]),
                                       g["out"][last_slot]["status"].to(torch.int64).sum().reshape(1)]) for g in groups])
         all_chk = [torch.empty_like(chk) for _ in range(world)]
@@ -765,6 +790,18 @@ def run_rank(args):
             gather_check = {"groups": len(groups), "ranks": world, "shards_equal": n_ok, "checksum": "wrapping int64 sums of the bit patterns",
                             "collective": "grouped isend/irecv (dist.gather raised on this backend)" if batch._gather_fallback["p2p"] else "dist.gather",
                             "skipped_qps_per_rank": [[int(all_chk[r][gi, 2]) for gi in range(len(groups))] for r in range(world)]}
+
+    # what the last timed step handed its caller: per group the sampled line (N > 1: gathered from every rank), and this
+    # rank's control points, success counts and skipped-QP counts
+    if args.dump_outputs and rank == 0:
+        arrays = {}
+        for gi, g in enumerate(groups):
+            last = g["out"][last_slot]
+            arrays[f"{g['name']}_xy"] = gathered[last_slot][gi].cpu().numpy() if world > 1 else xy_gpu[gi]
+            arrays[f"{g['name']}_ctrl"] = last["ctrl"].cpu().numpy()
+            arrays[f"{g['name']}_n_success"] = ns_gpu[gi]
+            arrays[f"{g['name']}_status"] = last["status"].cpu().numpy()
+        dump_outputs(args.dump_outputs, arrays)
 
     if rank == 0:
         total_solves = world * B * args.steps
@@ -814,23 +851,23 @@ def run_rank(args):
         }
         if gather_check is not None:
             res["gather_check"] = gather_check
-        if world == 1 and args.workload == "monza" and not args.no_global:
+        if args.full and world == 1 and args.workload == "monza" and not args.no_global:
             try:      # a failing secondary leg is reported in the line, it does not take the headline with it
                 res["global_qp"] = global_qp_leg(groups[0]["trk"], groups[0]["d_widths"], groups[0], args, torch,
                                                  with_cpu=not args.no_cpu_baseline)
             except Exception as e:
                 res["global_qp"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and args.workload == "monza" and not args.no_mintime:
+        if args.full and world == 1 and args.workload == "monza" and not args.no_mintime:
             res["mintime_nlp"] = mintime_leg(args.mintime_batch, with_cpu=not args.no_cpu_baseline)
-        if world == 1 and args.workload == "monza" and not args.no_qss:
+        if args.full and world == 1 and args.workload == "monza" and not args.no_qss:
             res["qss_sim"] = qss_leg(args.qss_batch, with_cpu=not args.no_cpu_baseline)
         pos = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 res["cpu_baseline"], pos = cpu_legs(groups, [g["i_start"] for g in groups], xy_gpu, min(args.cpu_instances, B))
             except Exception as e:
                 res["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and args.workload == "monza" and args.arith in ("fast", "reference") and not args.no_reference_order:
+        if args.full and world == 1 and args.workload == "monza" and args.arith in ("fast", "reference") and not args.no_reference_order:
             try:
                 fast_head = args.arith == "fast"
                 res["reference_order"] = reference_order_leg(groups[0], args, torch, search, kernel_ms if fast_head else None,
@@ -838,7 +875,7 @@ def run_rank(args):
                                                              fast_ns_all=ns_gpu[0] if fast_head else None)
             except Exception as e:
                 res["reference_order"] = {"error": f"{type(e).__name__}: {e}"}
-        if ref_run:
+        if ref_run and args.full:
             per = {d_["instance"]: d_ for d_ in res.get("cpu_baseline", {}).get("gpu_vs_oracle", {}).get("per_instance", [])}
             res["gpu_vs_reference_run"] = {
                 "what": "instances of THIS batch that also exist as a run of the reference's own run_min_curvature_qp loop "
@@ -923,6 +960,11 @@ def main():
     ap.add_argument("--search", choices=["windowed", "culled", "brute"], default="windowed")
     ap.add_argument("--arith", choices=["fast", "reference", "branch"], default="reference",
                     help="arithmetic of the headline's launches (include/rl_mincurv.h: RL_ARITH_*); reference = the library's default")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: CPU baseline, parity sample, reference-order leg, deviation from the reference's own "
+                         "runs, global-QP, min-time NLP and QSS legs, gather checksums (N > 1); the --no-* options below thin it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<group>_<array>.npy (float64)")
     ap.add_argument("--no-reference-order", action="store_true", help="skip the reference-order leg")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-global", action="store_true", help="skip the global-QP leg")
@@ -935,6 +977,8 @@ def main():
                     help="TEST HOOK: all ranks use cuda:0 and the gloo backend (exercises the N>1 code path "
                          "on a single-GPU box; the numbers are meaningless)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         spawn_ranks(args)   # never returns
     run_rank(args)

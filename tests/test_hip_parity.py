@@ -1134,7 +1134,7 @@ def test_bench_two_ranks_on_one_gpu(tmp_path):
     import os
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    tail = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--share-gpu", "--batch", "64"]
+    tail = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--share-gpu", "--batch", "64", "--full"]
     res = _bench([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                   "--master-addr", "127.0.0.1", "--master-port", "29533", os.path.join(root, "bench.py")] + tail, root)
     assert res["n_gpus"] == 2 and res["steps"] == 3 and res["scaling"] == "weak"
@@ -1144,6 +1144,30 @@ def test_bench_two_ranks_on_one_gpu(tmp_path):
     res = _bench([sys.executable, os.path.join(root, "bench.py")] + tail + ["--arith", "fast"], root)
     assert res["n_gpus"] == 2 and res["value"] > 0 and "world size 2" in res["config"]["parallelism"]
     assert res["roofline"]["kernel"] == "k_sweep" and res["summary"]["sweep_fast_ms"] > 0
+
+
+def test_bench_plain_run_dumps_its_outputs(tmp_path):
+    """A plain `bench.py` run times exactly --steps launches and carries the headline only (no secondary leg, no parity
+    sample); --dump-outputs writes what the last timed step returned, and a second run with the same arguments writes the
+    same bits (identical inputs, deterministic kernel)."""
+    import os
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for d in ("a", "b"):
+        res = _bench([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "64",
+                      "--dump-outputs", str(tmp_path / d)], root)
+        assert res["steps"] == 2 and res["ms_per_step"] > 0 and res["value"] > 0 and res["unit"] == "solves/s"
+        assert res["higher_is_better"] is True and res["dtype"] == "f64"
+        for leg in ("cpu_baseline", "reference_order", "global_qp", "mintime_nlp", "qss_sim", "parity", "gpu_vs_reference_run"):
+            assert leg not in res, leg
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["monza_ctrl.npy", "monza_n_success.npy", "monza_status.npy", "monza_xy.npy"], names
+    xy, ns, status = (np.load(tmp_path / "a" / f"monza_{n_}.npy") for n_ in ("xy", "n_success", "status"))
+    assert xy.dtype == np.float64 and xy.shape == (64, 2000, 2) and np.isfinite(xy).all()
+    n_ctrl = np.load(tmp_path / "a" / "monza_ctrl.npy").shape[1]
+    assert np.array_equal(status, 2 * ns.shape[1] * (n_ctrl - 5) - ns.reshape(64, -1).sum(axis=1))
+    for n_ in names:
+        assert np.array_equal(np.load(tmp_path / "a" / n_), np.load(tmp_path / "b" / n_)), n_
 
 
 def test_bench_mixed_workload_two_ranks(tmp_path):
@@ -1166,7 +1190,7 @@ def test_bench_mixed_workload_four_ranks(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     res = _bench([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "3", "--warmup", "1",
-                  "--share-gpu", "--batch", "64", "--workload", "mixed"], root)
+                  "--share-gpu", "--batch", "64", "--workload", "mixed", "--full"], root)
     assert res["n_gpus"] == 4 and res["value"] > 0
     gc = res["gather_check"]
     assert gc == dict(gc, groups=2, ranks=4, shards_equal=8), gc
@@ -1183,7 +1207,7 @@ def test_bench_mixed_workload_full_share_two_ranks(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     res = _bench([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                  "--share-gpu", "--batch", "1024", "--workload", "mixed"], root)
+                  "--share-gpu", "--batch", "1024", "--workload", "mixed", "--full"], root)
     assert res["n_gpus"] == 2 and res["value"] > 0 and "512 Monza + 512 rotated-oval" in res["config"]["workload"]
     gc = res["gather_check"]
     assert gc == dict(gc, groups=2, ranks=2, shards_equal=4), gc

@@ -368,3 +368,28 @@ def test_spawn_ranks_propagates_a_failed_rank():
     assert p.returncode == 7, (p.returncode, p.stdout[-500:], p.stderr[-500:])
     assert took < 200, took              # rank 0 was holding for 600 s: it was terminated, not waited for
     assert p.stdout.strip() == ""        # no line was printed
+
+
+def test_bench_dump_outputs_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float64 files, integers exact; above the size budget every array keeps the same fixed,
+    seeded share of its instances, and the sample's indices are written beside it."""
+    sys.path.insert(0, ROOT)
+    import bench
+    xy = np.random.default_rng(3).standard_normal((40, 10, 2))
+    ns = np.arange(40 * 5 * 2, dtype=np.int32).reshape(40, 5, 2)
+    bench.dump_outputs(str(tmp_path / "all"), {"g_xy": xy, "g_n_success": ns})
+    np.testing.assert_array_equal(np.load(tmp_path / "all" / "g_xy.npy"), xy)
+    back = np.load(tmp_path / "all" / "g_n_success.npy")
+    assert back.dtype == np.float64 and np.array_equal(back, ns)
+    assert not (tmp_path / "all" / "g_xy_index.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", (xy.nbytes + 8 * ns.size) // 4)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"g_xy": xy, "g_n_success": ns})
+    idx = np.load(tmp_path / "a" / "g_xy_index.npy").astype(np.int64)
+    assert len(idx) == 10 and np.all(np.diff(idx) > 0)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "g_xy.npy"), xy[idx])
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "g_n_success.npy"), ns[idx])
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total < xy.nbytes + 8 * ns.size
+    for f in os.listdir(tmp_path / "a"):
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))

@@ -23,6 +23,7 @@
 #include "rl_global_xy.hpp"
 #include "rl_dtrack.hpp"
 #include "rl_mintime.hpp"
+#include "rl_bicycle.hpp"
 
 namespace {
 
@@ -1692,6 +1693,110 @@ int rl_mintime_solve_batch(rl_ctx* ctx, const double* model, int B, int N, const
   const int rc = rl_mintime_solve_batch_dev(ctx, model, B, N, ds.p, dk.p, dl.p, dr.p, bounds_per_instance, margin, track_length,
                                             average_track_width, speed_cap, dX.p, dU.p, dT.p, max_iter, tol, dst.p);
   ctx->mt_poll = false;
+  if (rc) return rc;
+  RL_HIP(hipMemcpyAsync(X, dX.p, dX.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  RL_HIP(hipMemcpyAsync(U, dU.p, dU.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  RL_HIP(hipMemcpyAsync(T, dT.p, dT.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  RL_HIP(hipMemcpyAsync(stats, dst.p, dst.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  RL_HIP(hipStreamSynchronize(ctx->stream));
+  return RL_OK;
+}
+
+
+// ---- the bicycle min-time NLP (rl_bicycle.hpp)
+static int bk_problem(const double* model, int N, rl::BkProblem& P) {
+  for (int i = 0; i < rl::BK_NPARAM; ++i) {
+    if (!std::isfinite(model[i])) return fail(RL_ERR_ARG, "bicycle model: non-finite parameter");
+    P.m[i] = model[i];
+  }
+  if (!(model[RL_BK_L] > 0.0) || !(model[RL_BK_DELTA_MAX] > 0.0) || !(model[RL_BK_V_MAX] > 0.0) ||
+      !(model[RL_BK_A_LON_MAX] > model[RL_BK_A_LON_MIN]) || !(model[RL_BK_DELTA_DOT_MAX] > 0.0) || !(model[RL_BK_ACC_MAX] > 0.0))
+    return fail(RL_ERR_ARG, "bicycle model: L, delta_max, v_max, delta_dot_max, acc_max > 0 and a_lon_max > a_lon_min");
+  P.N = N;
+  return RL_OK;
+}
+
+int rl_bicycle_eval_nodes(rl_ctx* ctx, const double* model, int B, int N, const double* P0, const double* yaw,
+                          const double* X, const double* U, const double* T, double* eq, double* ineq, double* cost) {
+  if (!ctx || !model || !P0 || !yaw || !X || !U || !T || !eq || !ineq || !cost) return fail(RL_ERR_ARG, "null argument");
+  if (B <= 0 || N < 8) return fail(RL_ERR_ARG, "bad sizes (N >= 8 nodes)");
+  rl::BkProblem P{};
+  if (int rc = bk_problem(model, N, P)) return rc;
+  RL_HIP(hipSetDevice(ctx->device));
+  const size_t bn = (size_t)B * N;
+  PoolBuf<double> dP0(ctx), dyaw(ctx), dX(ctx), dU(ctx), dT(ctx), deq(ctx), din(ctx);
+  RL_HIP(dP0.alloc((size_t)2 * N)); RL_HIP(dyaw.alloc(N)); RL_HIP(dX.alloc(bn * 5)); RL_HIP(dU.alloc(bn * 2));
+  RL_HIP(dT.alloc(bn)); RL_HIP(deq.alloc(bn * rl::kBkNe)); RL_HIP(din.alloc(bn * 2));
+  auto up = [&](PoolBuf<double>& d, const double* h) { return hipMemcpyAsync(d.p, h, d.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream); };
+  RL_HIP(up(dP0, P0)); RL_HIP(up(dyaw, yaw)); RL_HIP(up(dX, X)); RL_HIP(up(dU, U)); RL_HIP(up(dT, T));
+  P.P0 = dP0.p; P.yaw = dyaw.p;
+  hipLaunchKernelGGL(rl::k_bk_eval, dim3((N + 63) / 64, B), dim3(64), 0, ctx->stream, P, B, (const double*)dX.p,
+                     (const double*)dU.p, (const double*)dT.p, deq.p, din.p);
+  RL_HIP(hipGetLastError());
+  RL_HIP(hipMemcpyAsync(eq, deq.p, deq.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  RL_HIP(hipMemcpyAsync(ineq, din.p, din.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  RL_HIP(hipStreamSynchronize(ctx->stream));
+  for (int b = 0; b < B; ++b) {   // min_time_cost (:9-10), summed in node order
+    double c = 0.0;
+    for (int j = 0; j < N; ++j) c += T[(size_t)b * N + j];
+    cost[b] = c;
+  }
+  return RL_OK;
+}
+
+int rl_bicycle_solve_batch_dev(rl_ctx* ctx, const double* model, int B, int N, const double* P0, const double* yaw,
+                               const double* dl, const double* dr, int bounds_per_instance, double* X, double* U, double* T,
+                               int max_iter, double tol, double* stats) {
+  if (!ctx || !model || !P0 || !yaw || !dl || !dr || !X || !U || !T || !stats) return fail(RL_ERR_ARG, "null argument");
+  if (B <= 0 || N < 8 || max_iter < 1 || !(tol > 0.0)) return fail(RL_ERR_ARG, "bad sizes (N >= 8 nodes, max_iter >= 1, tol > 0)");
+  rl::BkProblem P{};
+  if (int rc = bk_problem(model, N, P)) return rc;
+  RL_HIP(hipSetDevice(ctx->device));
+  P.per = bounds_per_instance ? 1 : 0;
+  P.P0 = P0; P.yaw = yaw; P.dl = dl; P.dr = dr; P.tol = tol;
+  const size_t bn = (size_t)B * N;
+  const size_t counts[] = {bn * rl::kBkNb, bn * rl::kBkNe, bn * 2, bn * rl::kBkNb, bn * rl::kBkNb, bn * rl::kBkKK,
+                           bn * rl::kBkK, bn * rl::kBkKK, bn * rl::kBkKK, bn * rl::kBkK, bn * 16, bn * 2, bn * rl::kBkNb,
+                           (size_t)B * rl::kBkScal, (size_t)B * rl::kBkFilter * 2};
+  size_t total = 0;
+  for (size_t c : counts) total += Arena::pad(c * sizeof(double));
+  Arena ar(ctx);
+  RL_HIP(ar.reserve(total));
+  rl::BkState st;
+  st.B = B; st.N = N;
+  st.p = ar.take<double>(counts[0]); st.yc = ar.take<double>(counts[1]); st.yd = ar.take<double>(counts[2]);
+  st.zl = ar.take<double>(counts[3]); st.zu = ar.take<double>(counts[4]); st.D = ar.take<double>(counts[5]);
+  st.r = ar.take<double>(counts[6]); st.Dinv = ar.take<double>(counts[7]); st.Tk = ar.take<double>(counts[8]);
+  st.v = ar.take<double>(counts[9]); st.Jd = ar.take<double>(counts[10]); st.dcur = ar.take<double>(counts[11]);
+  st.dp = ar.take<double>(counts[12]); st.scal = ar.take<double>(counts[13]); st.filt = ar.take<double>(counts[14]);
+  const dim3 grid(B), block(rl::kBkThreads);
+  hipLaunchKernelGGL(rl::k_bk_init, grid, block, 0, ctx->stream, P, st, (const double*)X, (const double*)U, (const double*)T);
+  // exactly max_iter iterations are enqueued; an instance that has converged or failed returns from each at once
+  for (int it = 0; it < max_iter; ++it) hipLaunchKernelGGL(rl::k_bk_iter, grid, block, 0, ctx->stream, P, st, 0);
+  hipLaunchKernelGGL(rl::k_bk_iter, grid, block, 0, ctx->stream, P, st, 1);
+  hipLaunchKernelGGL(rl::k_bk_unpack, dim3((N + 63) / 64, B), dim3(64), 0, ctx->stream, P, st, X, U, T, stats);
+  RL_HIP(hipGetLastError());
+  RL_HIP(ar.end());
+  return RL_OK;
+}
+
+int rl_bicycle_solve_batch(rl_ctx* ctx, const double* model, int B, int N, const double* P0, const double* yaw,
+                           const double* dl, const double* dr, int bounds_per_instance, double* X, double* U, double* T,
+                           int max_iter, double tol, double* stats) {
+  if (!ctx || !model || !P0 || !yaw || !dl || !dr || !X || !U || !T || !stats) return fail(RL_ERR_ARG, "null argument");
+  if (B <= 0 || N < 8) return fail(RL_ERR_ARG, "bad sizes (N >= 8 nodes)");
+  const size_t bn = (size_t)B * N, nb_ = bounds_per_instance ? bn : (size_t)N;
+  for (size_t i = 0; i < nb_; ++i)
+    if (!(dr[i] < dl[i])) return fail(RL_ERR_ARG, "bounds: need dr < dl at every node (min_time_optimizer.py:66-68)");
+  RL_HIP(hipSetDevice(ctx->device));
+  PoolBuf<double> dP0(ctx), dyaw(ctx), ddl(ctx), ddr(ctx), dX(ctx), dU(ctx), dT(ctx), dst(ctx);
+  RL_HIP(dP0.alloc((size_t)2 * N)); RL_HIP(dyaw.alloc(N)); RL_HIP(ddl.alloc(nb_)); RL_HIP(ddr.alloc(nb_));
+  RL_HIP(dX.alloc(bn * 5)); RL_HIP(dU.alloc(bn * 2)); RL_HIP(dT.alloc(bn)); RL_HIP(dst.alloc((size_t)B * 12));
+  auto up = [&](PoolBuf<double>& d, const double* h) { return hipMemcpyAsync(d.p, h, d.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream); };
+  RL_HIP(up(dP0, P0)); RL_HIP(up(dyaw, yaw)); RL_HIP(up(ddl, dl)); RL_HIP(up(ddr, dr));
+  RL_HIP(up(dX, X)); RL_HIP(up(dU, U)); RL_HIP(up(dT, T));
+  const int rc = rl_bicycle_solve_batch_dev(ctx, model, B, N, dP0.p, dyaw.p, ddl.p, ddr.p, bounds_per_instance, dX.p, dU.p,
+                                            dT.p, max_iter, tol, dst.p);
   if (rc) return rc;
   RL_HIP(hipMemcpyAsync(X, dX.p, dX.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   RL_HIP(hipMemcpyAsync(U, dU.p, dU.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));

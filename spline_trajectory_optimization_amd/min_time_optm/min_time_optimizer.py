@@ -1,4 +1,5 @@
-"""Host-side mirror of `spline_traj_optm.min_time_optm.min_time_optimizer.set_up_double_track_problem`
+"""Host-side mirror of `spline_traj_optm.min_time_optm.min_time_optimizer`: `set_up_bicycle_problem` (:14-90, over
+`BicycleProblem` and rl_bicycle_solve_batch; see that class) and `set_up_double_track_problem`
 (min_time_optm/min_time_optimizer.py:93-163) and of the solve the reference's CLI performs on it
 (entrypoints/traj_opt_double_track.py:24-86), with the GPU solver behind it.
 
@@ -209,6 +210,94 @@ def set_up_double_track_problem(params):
     X = OptiVariable("X", (prob.N, 6)); U = OptiVariable("U", (prob.N, 4)); T = OptiVariable("T", (prob.N,))
     opti = OptiFacade(prob, X, U, T)
     return (X, U, T), (prob.scale_x, prob.scale_u, prob.scale_t), opti
+
+
+class BicycleProblem:
+    """The NLP of the reference's set_up_bicycle_problem (min_time_optimizer.py:14-90) for the GPU solve
+    (include/rl_mincurv.h: rl_bicycle_solve_batch), in physical units.  `params` is the reference's dictionary
+    (N, traj_d, nu, nx, model, dynamics, x_l, x_u, u_l, u_u, verbose, max_iter, tol) plus the optional
+    `initial_guess`: "reference" (default, :80-83 as written: the affine `set_initial` on x_i puts every node at the
+    global origin with theta = yaw, v = 1, u = 0, T = 1) or "centerline" (on P0, theta = yaw, delta = 0, v = SPEED
+    where filled else 10 m/s, T = segment length / v).  `dynamics` must be the bicycle model; its bound callables
+    are called on the host and must describe what the kernels implement (x, y, theta free; symmetric steering and
+    steering-rate bounds; v in [0, v_max])."""
+
+    def __init__(self, params):
+        from ..models import dynamic_bicycle as dyn
+        self.params = params
+        dynamics = params.get("dynamics", dyn.dynamics)
+        if dynamics is not dyn.dynamics and getattr(dynamics, "__module__", "").split(".")[-1] != "dynamic_bicycle":
+            raise ValueError("set_up_bicycle_problem: params['dynamics'] must be the bicycle model "
+                             "(spline_traj_optm.models.dynamic_bicycle.dynamics); the GPU solver implements no other")
+        model = dict(params["model"])
+        lo_x = np.asarray(params.get("x_l", dyn.x_l)(model), dtype=np.float64).reshape(5)
+        hi_x = np.asarray(params.get("x_u", dyn.x_u)(model), dtype=np.float64).reshape(5)
+        lo_u = np.asarray(params.get("u_l", dyn.u_l)(model), dtype=np.float64).reshape(2)
+        hi_u = np.asarray(params.get("u_u", dyn.u_u)(model), dtype=np.float64).reshape(2)
+        if not (np.all(np.isneginf(lo_x[:3])) and np.all(np.isposinf(hi_x[:3])) and lo_x[3] == -hi_x[3] and lo_x[4] == 0.0
+                and lo_u[1] == -hi_u[1] and np.all(np.isfinite([hi_x[3], hi_x[4], lo_u[0], hi_u[0], hi_u[1]]))):
+            raise ValueError("set_up_bicycle_problem: the bound callables must leave x, y, theta free, bound delta and "
+                             "delta_dot symmetrically and v to [0, v_max] (what rl_bicycle_solve_batch implements)")
+        # the bounds the callables give take the place of the model's own keys
+        self.model = dict(model, delta_max=float(hi_x[3]), v_max=float(hi_x[4]), a_lon_min=float(lo_u[0]),
+                          a_lon_max=float(hi_u[0]), delta_dot_max=float(hi_u[1]))
+        pts = params["traj_d"].points if isinstance(params["traj_d"], Trajectory) else np.asarray(params["traj_d"])
+        self.N = int(params.get("N", len(pts)))
+        assert self.N == len(pts)
+        self.P0 = np.ascontiguousarray(pts[:, Trajectory.X:Trajectory.Y + 1], dtype=np.float64)              # :26
+        self.yaw = np.ascontiguousarray(pts[:, Trajectory.YAW], dtype=np.float64)                             # :28
+        bl = pts[:, Trajectory.LEFT_BOUND_X:Trajectory.LEFT_BOUND_Y + 1]                                      # :29-32
+        br = pts[:, Trajectory.RIGHT_BOUND_X:Trajectory.RIGHT_BOUND_Y + 1]
+        self.left = np.ascontiguousarray(np.linalg.norm(bl - self.P0, axis=1))                               # dl, :66
+        self.right = np.ascontiguousarray(-np.linalg.norm(br - self.P0, axis=1))                             # dr, :67
+        self.scale_x = np.array([[10.0, 10.0, 3.14, 0.1, 80.0]])                                              # :33-35
+        self.scale_u = np.array([[20.0, 1.0]])
+        self.scale_t = 1.0
+        self.x_offset = np.zeros((self.N, 5)); self.x_offset[:, 0:2] = self.P0                                # X_OFFSET, :27
+        mode = params.get("initial_guess", "reference")
+        if mode not in ("reference", "centerline"):
+            raise ValueError(f"initial_guess must be 'reference' or 'centerline', not {mode!r}")
+        self.X0 = np.zeros((self.N, 5)); self.U0 = np.zeros((self.N, 2))
+        self.X0[:, 2] = self.yaw
+        if mode == "reference":                                                                               # :80-83
+            self.X0[:, 4] = 1.0
+            self.T0 = np.ones(self.N)
+        else:
+            v = pts[:, Trajectory.SPEED]
+            v = np.where(np.isfinite(v) & (v > 0.0), v, 10.0)
+            self.X0[:, 0:2] = self.P0
+            self.X0[:, 2] = np.unwrap(self.yaw)
+            self.X0[:, 4] = v
+            self.T0 = np.linalg.norm(np.roll(self.P0, -1, axis=0) - self.P0, axis=1) / v
+
+    def solve(self, max_iter=None, tol=None):
+        """-> (X [N,5], U [N,2], T [N], stats [12]); stats as include/rl_mincurv.h: rl_bicycle_solve_batch."""
+        X, U, T, st = self.solve_batch(self.left[None], self.right[None], max_iter=max_iter, tol=tol)
+        return X[0], U[0], T[0], st[0]
+
+    def solve_batch(self, left, right, X0=None, U0=None, T0=None, max_iter=None, tol=None):
+        """B instances that differ in their boundary distances left (dl > 0) / right (dr < 0) [B,N] (and optionally
+        in their initial guesses).  Default tol 1e-6 (absolute, the solver's own scale)."""
+        left = np.ascontiguousarray(left, dtype=np.float64); right = np.ascontiguousarray(right, dtype=np.float64)
+        B = left.shape[0]
+        rep = lambda a: np.repeat(np.asarray(a)[None], B, axis=0)  # noqa: E731
+        X0 = rep(self.X0) if X0 is None else X0
+        U0 = rep(self.U0) if U0 is None else U0
+        T0 = rep(self.T0) if T0 is None else T0
+        return ops.bicycle_solve_batch(self.model, self.P0, self.yaw, left, right, X0, U0, T0,
+                                       max_iter=int(max_iter or self.params.get("max_iter", 200)),
+                                       tol=float(tol if tol is not None else 1e-6))
+
+
+def set_up_bicycle_problem(params):
+    """-> X, U, T, opti   (min_time_optimizer.py:14-90, return at :90).  X (N x 5), U (N x 2), T (N) are handles in
+    the reference's SCALED variables: X * scale_x + X_OFFSET, U * scale_u and T are physical (scale_x = (10, 10, 3.14,
+    0.1, 80), scale_u = (20, 1), X_OFFSET = (traj_d[:, X:Y+1], 0, 0, 0)).  `opti` is the same facade as
+    set_up_double_track_problem's, over BicycleProblem (`opti.problem`)."""
+    prob = BicycleProblem(params)
+    X = OptiVariable("X", (prob.N, 5)); U = OptiVariable("U", (prob.N, 2)); T = OptiVariable("T", (prob.N,))
+    opti = OptiFacade(prob, X, U, T)
+    return X, U, T, opti
 
 
 def optimise_track(race_track, vehicle, model, average_track_width=7.0, speed_cap=30.0, max_iter=200, tol=1e-6):

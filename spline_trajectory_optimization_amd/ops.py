@@ -377,3 +377,67 @@ def mintime_solve_torch(model, s, kappa, left, right, margin, track_length, X, U
                                              float(track_length), float(average_track_width), float(speed_cap), p(X), p(U),
                                              p(T), int(max_iter), float(tol), p(stats)))
     return stats
+
+
+BK_PARAMS = ("lr", "L", "delta_max", "v_max", "a_lon_max", "a_lon_min", "delta_dot_max", "acc_max")   # rl_bk_param order
+
+
+def _bk_model(model):
+    return as_d([float(model[k]) for k in BK_PARAMS])
+
+
+def bicycle_eval_nodes(model, P0, yaw, X, U, T, device=None):
+    """The bicycle NLP's functions at a physical point (include/rl_mincurv.h: rl_bicycle_eval_nodes).
+    P0 [N,2], yaw [N]; X [B,N,5], U [B,N,2], T [B,N].  Returns (eq [B,N,6], ineq [B,N,2], cost [B])."""
+    ctx = Context.get(device)
+    mv, mp = _bk_model(model)
+    X, Xp = as_d(X); U, Up = as_d(U); T, Tp = as_d(T)
+    B, N = T.shape
+    assert X.shape == (B, N, 5) and U.shape == (B, N, 2)
+    P0, pp = as_d(P0); yaw, yp = as_d(yaw)
+    assert P0.shape == (N, 2) and yaw.shape == (N,)
+    eq = np.empty((B, N, 6)); ineq = np.empty((B, N, 2)); cost = np.empty(B)
+    check(ctx.lib.rl_bicycle_eval_nodes(ctx.h, mp, B, N, pp, yp, Xp, Up, Tp, eq.ctypes.data_as(_dp),
+                                        ineq.ctypes.data_as(_dp), cost.ctypes.data_as(_dp)))
+    return eq, ineq, cost
+
+
+def bicycle_solve_batch(model, P0, yaw, dl, dr, X0, U0, T0, max_iter=200, tol=1e-6, device=None):
+    """The solve of the bicycle min-time NLP for B instances (include/rl_mincurv.h: rl_bicycle_solve_batch; stands in
+    for `opti.solve()` with IPOPT on set_up_bicycle_problem).  dl/dr: [N] shared or [B,N] per instance.
+    X0 [B,N,5], U0 [B,N,2], T0 [B,N]: initial guess (physical).  Returns (X, U, T, stats [B,12])."""
+    ctx = Context.get(device)
+    mv, mp = _bk_model(model)
+    X = np.array(X0, dtype=np.float64, copy=True, order="C"); U = np.array(U0, dtype=np.float64, copy=True, order="C")
+    T = np.array(T0, dtype=np.float64, copy=True, order="C")
+    B, N = T.shape
+    assert X.shape == (B, N, 5) and U.shape == (B, N, 2)
+    P0, pp = as_d(P0); yaw, yp = as_d(yaw); dl, lp = as_d(dl); dr, rp = as_d(dr)
+    per = dl.ndim == 2
+    assert dl.shape == dr.shape == ((B, N) if per else (N,)) and P0.shape == (N, 2) and yaw.shape == (N,)
+    stats = np.zeros((B, 12))
+    check(ctx.lib.rl_bicycle_solve_batch(ctx.h, mp, B, N, pp, yp, lp, rp, int(per), X.ctypes.data_as(_dp),
+                                         U.ctypes.data_as(_dp), T.ctypes.data_as(_dp), int(max_iter), float(tol),
+                                         stats.ctypes.data_as(_dp)))
+    return X, U, T, stats
+
+
+def bicycle_solve_torch(model, P0, yaw, dl, dr, X, U, T, max_iter=200, tol=1e-6):
+    """rl_bicycle_solve_batch_dev on DEVICE tensors (float64, cuda, contiguous): P0 [N,2], yaw [N]; dl, dr [N] or
+    [B,N]; X [B,N,5], U [B,N,2], T [B,N] are updated in place.  Enqueues on torch's current stream, no sync.
+    Returns the stats tensor [B,12]."""
+    import torch
+    dev = X.device
+    for t_ in (P0, yaw, dl, dr, X, U, T):
+        assert t_.is_cuda and t_.dtype == torch.float64 and t_.is_contiguous()
+    B, N = T.shape
+    assert tuple(X.shape) == (B, N, 5) and tuple(U.shape) == (B, N, 2) and tuple(P0.shape) == (N, 2) and yaw.shape[0] == N
+    per = dl.dim() == 2
+    ctx = Context.get(dev.index)
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    mv, mp = _bk_model(model)
+    stats = torch.empty((B, 12), dtype=torch.float64, device=dev)
+    p = lambda t_: ctypes.c_void_p(t_.data_ptr())  # noqa: E731
+    check(ctx.lib.rl_bicycle_solve_batch_dev(ctx.h, mp, B, N, p(P0), p(yaw), p(dl), p(dr), int(per), p(X), p(U), p(T),
+                                             int(max_iter), float(tol), p(stats)))
+    return stats

@@ -146,6 +146,26 @@ int rl_sample_along(rl_ctx* ctx, const double* t, int nt, const double* cx, cons
 int rl_fill_bounds(rl_ctx* ctx, double* points, int N, const double* ringL, int nL,
                    const double* ringR, int nR, double max_dist);
 
+/* ---- Trajectory.fill_region  (models/trajectory.py: fill_region; csrc/rl_region.hpp)
+ * Regions are small HOST arrays: vertices verts[V][2] of all regions one after another, CSR offsets[R+1]
+ * (offsets[0] = 0, region r owns verts[offsets[r] .. offsets[r+1]), V = offsets[R]) and codes[R].  Each polygon's
+ * closing edge is implied.  A point is tagged with the FIRST region, in list order, whose polygon contains it in its
+ * interior: a point on an edge or a vertex is not contained, a zero-area polygon contains nothing, a point with a
+ * non-finite coordinate lies in no region and a region with a non-finite vertex contains nothing.  Self-intersecting
+ * polygons: even-odd rule.  The decision is exact (no dependence on rounding) for coordinates that are 0 or of magnitude in
+ * [2^-480, 2^500].  RL_ERR_ARG for a region with fewer than 3 vertices or offsets that are not as above; R = 0, B = 0 or
+ * N = 0 is a successful no-op.
+ * rl_fill_region: points is the host table [B,N,19]; REGION := code of the containing region, left unchanged where none
+ * contains the point. */
+int rl_fill_region(rl_ctx* ctx, double* points, int B, int N, const double* verts, const int* offsets, int R,
+                   const int* codes);
+/* Same test on DEVICE points: point (b, n) at xy[(b N + n) stride], xy[(b N + n) stride + 1] (stride 19 for a table,
+ * 2 for the sweep's xy output); out is a DEVICE int32 array [B,N] := index of the first containing region or -1
+ * (R = 0: all -1).  Enqueued on the context's stream, no synchronisation; the region arrays are copied before the call
+ * returns. */
+int rl_region_index_dev(rl_ctx* ctx, const double* xy, int B, int N, int stride, const double* verts, const int* offsets,
+                        int R, int* out);
+
 /* ---- track tables: knots + uniform sample grid u_i = i/N (Trajectory.ts, trajectory.py:199-200)
  * cx0/cy0 are the initial control points shared by every instance of a batch. */
 int rl_track_create(rl_ctx* ctx, const double* t, int nt, const double* cx0, const double* cy0,

@@ -54,6 +54,8 @@ _SIGNATURES = {
                                        ctypes.c_double, _dp, ctypes.c_int, _dp]),
     "rl_fill_bounds": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, ctypes.c_int, _dp, ctypes.c_int,
                                       ctypes.c_double]),
+    "rl_fill_region": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _dp, _ip, ctypes.c_int, _ip]),
+    "rl_region_index_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _ip, ctypes.c_int, _vp]),
     "rl_track_create": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _dp, ctypes.c_int, ctypes.c_int,
                                        ctypes.POINTER(_vp)]),
     "rl_track_destroy": (None, [_vp]),

@@ -58,6 +58,30 @@ def load_monza():
             load_track_csv(os.path.join(MONZA_DIR, "MONZA_RIGHT_BOUNDARY_enu.csv")))
 
 
+def monza_sectors(n_sectors=8, refine=4):
+    """Sector polygons of Monza for region tagging (tools/time_region.py, tests/test_region_gpu.py): the left boundary cut
+    into `n_sectors` stretches of equal vertex count, each closed by the reversed stretch of the right boundary between the
+    right-boundary vertices nearest to its two ends.  `refine` > 1 inserts refine - 1 points on every boundary segment
+    first (same polylines, more vertices).  Returns a list of [n, 2] float64 vertex arrays."""
+    _, left, right = load_monza()
+
+    def dense(ring):
+        nxt = np.roll(ring, -1, axis=0)
+        f = np.arange(refine)[None, :, None] / refine
+        return (ring[:, None, :] + f * (nxt - ring)[:, None, :]).reshape(-1, 2)
+
+    left, right = dense(left), dense(right)
+    nL, nR = len(left), len(right)
+    cuts = [i * nL // n_sectors for i in range(n_sectors)] + [nL]
+    near = [int(np.argmin(np.hypot(*(right - left[c % nL]).T))) for c in cuts]
+    out = []
+    for s_ in range(n_sectors):
+        li = np.arange(cuts[s_], cuts[s_ + 1] + 1) % nL
+        rj = (near[s_] + np.arange((near[s_ + 1] - near[s_]) % nR + 1)) % nR
+        out.append(np.vstack([left[li], right[rj[::-1]]]))
+    return out
+
+
 def monza_centerline(s=100.0, k=5):
     """The centre-line spline of tests/test_optimizer.py:16-17 (host FITPACK fit)."""
     centre, _, _ = load_monza()

@@ -24,6 +24,7 @@
 #include "rl_dtrack.hpp"
 #include "rl_mintime.hpp"
 #include "rl_bicycle.hpp"
+#include "rl_region.hpp"
 
 namespace {
 
@@ -1259,6 +1260,88 @@ int rl_mincurv_sweep(rl_ctx* ctx, rl_track* trk, const int* i_start, int max_ite
 int rl_mincurv_sweep_joint(rl_ctx* ctx, rl_track* trk, const int* i_start, int max_iter,
                            double* cx, double* cy, double* points, int* n_success, rl_stats* stats) {
   return sweep_single(ctx, trk, i_start, max_iter, cx, cy, points, n_success, stats, true);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Trajectory.fill_region (csrc/rl_region.hpp)
+static int region_check(const double* verts, const int* offsets, int R) {
+  if (R > 0 && (!offsets || !verts)) return fail(RL_ERR_ARG, "null argument");
+  if (R > 0 && offsets[0] != 0) return fail(RL_ERR_ARG, "region offsets must start at 0");
+  for (int r = 0; r < R; ++r)
+    if (offsets[r + 1] - offsets[r] < 3) return fail(RL_ERR_ARG, "a region needs at least 3 vertices (bad offsets)");
+  return RL_OK;
+}
+
+// The region tables (checked by region_check) get their boxes on the host and are staged through the context's arena
+// with pageable copies (the runtime has read them when the copy call returns), then one launch of k_region_index.
+static int region_launch(rl_ctx* ctx, const double* xy, long long stride, long long n, const double* verts,
+                         const int* offsets, int R, const int* codes, int* out, double* tag, long long tag_stride) {
+  const int V = offsets[R];
+  std::vector<double> box((size_t)4 * R);
+  for (int r = 0; r < R; ++r) {
+    double x0 = verts[2 * offsets[r]], y0 = verts[2 * offsets[r] + 1], x1 = x0, y1 = y0;
+    bool finite = true;
+    for (int v = offsets[r]; v < offsets[r + 1]; ++v) {
+      const double x = verts[2 * v], y = verts[2 * v + 1];
+      finite = finite && std::isfinite(x) && std::isfinite(y);
+      x0 = std::min(x0, x); x1 = std::max(x1, x); y0 = std::min(y0, y); y1 = std::max(y1, y);
+    }
+    if (!finite) { x0 = y0 = 1.0; x1 = y1 = -1.0; }   // an empty box: the region contains nothing
+    box[4 * r] = x0; box[4 * r + 1] = y0; box[4 * r + 2] = x1; box[4 * r + 3] = y1;
+  }
+  Arena ar(ctx);
+  RL_HIP(ar.reserve(Arena::pad(box.size() * 8) + Arena::pad((size_t)V * 16) + Arena::pad((size_t)(R + 1) * 4) +
+                    Arena::pad((size_t)R * 4)));
+  double* dbox = ar.take<double>(box.size()); double* dv = ar.take<double>((size_t)2 * V);
+  int* doff = ar.take<int>(R + 1); int* dcode = ar.take<int>(R);
+  RL_HIP(hipMemcpyAsync(dbox, box.data(), box.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  RL_HIP(hipMemcpyAsync(dv, verts, (size_t)2 * V * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  RL_HIP(hipMemcpyAsync(doff, offsets, (size_t)(R + 1) * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+  if (codes) RL_HIP(hipMemcpyAsync(dcode, codes, (size_t)R * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+  rl::RegionArgs a;
+  a.xy = xy; a.stride = stride; a.n = n;
+  a.verts = reinterpret_cast<const double2*>(dv); a.offsets = doff; a.box = reinterpret_cast<const double4*>(dbox); a.R = R;
+  a.out = out; a.codes = dcode; a.tag = tag; a.tag_stride = tag_stride;
+  hipLaunchKernelGGL(rl::k_region_index, dim3((unsigned)((n + rl::kRegionBlock - 1) / rl::kRegionBlock)),
+                     dim3(rl::kRegionBlock), 0, ctx->stream, a);
+  RL_HIP(hipGetLastError());
+  RL_HIP(ar.end());
+  return RL_OK;
+}
+
+int rl_fill_region(rl_ctx* ctx, double* points, int B, int N, const double* verts, const int* offsets, int R,
+                   const int* codes) {
+  if (!ctx) return fail(RL_ERR_ARG, "null argument");
+  if (B < 0 || N < 0 || R < 0) return fail(RL_ERR_ARG, "bad sizes");
+  if (int rc = region_check(verts, offsets, R)) return rc;
+  if (R == 0 || B == 0 || N == 0) return RL_OK;
+  if (!points || !codes) return fail(RL_ERR_ARG, "null argument");
+  RL_HIP(hipSetDevice(ctx->device));
+  const long long n = (long long)B * N;
+  PoolBuf<double> dpts(ctx);
+  RL_HIP(dpts.alloc((size_t)n * RL_NCOL));
+  RL_HIP(hipMemcpyAsync(dpts.p, points, dpts.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  // REGION is column 8 (models/trajectory.py)
+  if (int rc = region_launch(ctx, dpts.p, RL_NCOL, n, verts, offsets, R, codes, nullptr, dpts.p + 8, RL_NCOL)) return rc;
+  RL_HIP(hipMemcpyAsync(points, dpts.p, dpts.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  RL_HIP(hipStreamSynchronize(ctx->stream));
+  return RL_OK;
+}
+
+int rl_region_index_dev(rl_ctx* ctx, const double* xy, int B, int N, int stride, const double* verts, const int* offsets,
+                        int R, int* out) {
+  if (!ctx) return fail(RL_ERR_ARG, "null argument");
+  if (B < 0 || N < 0 || R < 0 || stride < 2) return fail(RL_ERR_ARG, "bad sizes");
+  if (int rc = region_check(verts, offsets, R)) return rc;
+  if (B == 0 || N == 0) return RL_OK;
+  if (!xy || !out) return fail(RL_ERR_ARG, "null argument");
+  RL_HIP(hipSetDevice(ctx->device));
+  const long long n = (long long)B * N;
+  if (R == 0) {   // no region contains anything
+    RL_HIP(hipMemsetAsync(out, 0xff, (size_t)n * sizeof(int), ctx->stream));
+    return RL_OK;
+  }
+  return region_launch(ctx, xy, stride, n, verts, offsets, R, nullptr, out, nullptr, 0);
 }
 
 int rl_qss_sim_dev(rl_ctx* ctx, double* points, int B, int N, const double* acc_x, const double* acc_c,

@@ -5,8 +5,8 @@ implementation.
 What runs where
   * the spline FIT (scipy FITPACK `splprep`, reference :219-222) and the total length (scipy `quad`,
     :223) are host-side set-up, as in the reference (SURVEY.md 8a row a2);
-  * evaluation, sampling and boundary filling (`eval`, `sample_along`, `fill_bounds`) are HIP kernels
-    behind the C ABI (include/rl_mincurv.h) -- there is no CPU fallback for them.
+  * evaluation, sampling, boundary filling and region tagging (`eval`, `sample_along`, `fill_bounds`, `fill_region`) are
+    HIP kernels behind the C ABI (include/rl_mincurv.h) -- there is no CPU fallback for them.
 """
 import copy
 import pickle
@@ -121,15 +121,13 @@ class Trajectory:
         self.points[nxt, Trajectory.TIME] = seg / (0.5 * (v + v[nxt]))
 
     def fill_region(self, regions: list):
-        """Tag waypoints with the code of the first region polygon containing them (reference
-        :182-194; file tooling, needs shapely)."""
-        from shapely.geometry import Point, Polygon
-        shapes = [(Polygon(np.asarray(r.vertices).tolist()), r.code) for r in regions]
-        for row in self.points:
-            here = Point(row[Trajectory.X], row[Trajectory.Y])
-            code = next((c for poly, c in shapes if poly.contains(here)), None)
-            if code is not None:
-                row[Trajectory.REGION] = code
+        """Tag waypoints with the code of the first region polygon (in list order) that contains them in its interior
+        (reference :182-194, shapely's Polygon.contains) -> HIP kernel k_region_index through rl_fill_region.  Points on
+        an edge or a vertex are not contained; REGION stays as it was where no region contains the point.  ValueError for
+        a region with fewer than 3 vertices."""
+        table = np.ascontiguousarray(self.points, dtype=np.float64)
+        ops.fill_region(table, regions)
+        self.points[:, Trajectory.REGION] = table[:, Trajectory.REGION]
 
     # -- plain CSV of the whole table (reference :202-209); called on the class, like the reference
     def save(f, traj):

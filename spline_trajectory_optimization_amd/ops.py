@@ -46,6 +46,57 @@ def fill_bounds(points, ringL, ringR, max_dist=100.0, device=None):
     return points
 
 
+def region_tables(regions):
+    """Region objects (name, code, vertices [n,2]), or (vertices, code) pairs, in list order -> the C ABI's tables
+    (verts [V,2] float64, offsets [R+1] int32, codes [R] int32).  ValueError for a region with fewer than 3 vertices
+    (shapely cannot build its polygon either)."""
+    verts, offsets, codes = [], [0], []
+    for reg in regions:
+        v, code = (reg.vertices, reg.code) if hasattr(reg, "vertices") else reg
+        v = np.asarray(v, dtype=np.float64)
+        if v.ndim != 2 or v.shape[1] < 2 or v.shape[0] < 3:
+            raise ValueError(f"a region polygon needs at least 3 vertices [n,2], got shape {v.shape}")
+        verts.append(v[:, :2])
+        offsets.append(offsets[-1] + len(v))
+        codes.append(int(code))
+    V = np.ascontiguousarray(np.concatenate(verts) if verts else np.zeros((0, 2)), dtype=np.float64)
+    return V, np.asarray(offsets, dtype=np.int32), np.asarray(codes, dtype=np.int32)
+
+
+def fill_region(points, regions, device=None):
+    """Trajectory.fill_region in place on a C-contiguous host table [N,19] or [B,N,19] (models/trajectory.py: fill_region):
+    REGION := code of the first region whose polygon contains the point in its interior, unchanged where none does."""
+    assert points.dtype == np.float64 and points.flags.c_contiguous and points.shape[-1] == _lib.NCOL
+    B, N = (1, points.shape[0]) if points.ndim == 2 else points.shape[:2]
+    V, off, codes = region_tables(regions)
+    if len(codes) == 0 or B * N == 0:
+        return points
+    ctx = Context.get(device)
+    check(ctx.lib.rl_fill_region(ctx.h, points.ctypes.data_as(_dp), int(B), int(N), V.ctypes.data_as(_dp),
+                                 off.ctypes.data_as(_ip), len(codes), codes.ctypes.data_as(_ip)))
+    return points
+
+
+def region_index_torch(xy, regions, out=None):
+    """Index of the first region containing each point of a DEVICE tensor (float64 cuda, contiguous, [..., C] with C >= 2:
+    x, y in the first two columns -- the sweep's xy [B,N,2] or a table batch [B,N,19]); -1 where no region does.
+    Enqueues on torch's current stream, no sync (rl_region_index_dev).  Returns an int32 cuda tensor of shape xy.shape[:-1]."""
+    import torch
+    assert xy.is_cuda and xy.dtype == torch.float64 and xy.is_contiguous() and xy.dim() >= 1 and xy.shape[-1] >= 2
+    V, off, codes = region_tables(regions)
+    lead = tuple(xy.shape[:-1])
+    n = int(np.prod(lead)) if lead else 1
+    if out is None:
+        out = torch.empty(lead, dtype=torch.int32, device=xy.device)
+    assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() == n
+    ctx = Context.get(xy.device.index)
+    ctx.set_stream(torch.cuda.current_stream(xy.device).cuda_stream)
+    check(ctx.lib.rl_region_index_dev(ctx.h, ctypes.c_void_p(xy.data_ptr()), 1, n, int(xy.shape[-1]),
+                                      V.ctypes.data_as(_dp), off.ctypes.data_as(_ip), len(codes),
+                                      ctypes.c_void_p(out.data_ptr())))
+    return out
+
+
 def mincurv_cost(track, idx, z=None):
     """TrajectoryOptimizer.min_curvature_cost for several control points at once
     (optimization/optimizer.py:24-86).  Returns H [n_idx,2,2], g [n_idx,2], M [n_idx]."""

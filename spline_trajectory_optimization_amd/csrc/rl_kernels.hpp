@@ -1295,7 +1295,8 @@ __global__ __launch_bounds__(BLOCK, (BLOCK >= 512 || (!RINGS_LDS && !SIGMA_LDS &
       // priority) WHILE waves 1..3 form the rows of the same samples (positions, bound points, the four quotients, clamp
       // interval) -- work that used to sit in front of the sums on every wave's path.
       const int M = s1 - s0;
-      const int nchunks = (M + kTermChunk - 1) / kTermChunk;
+      // an empty support (M = 0: sparse samplings) runs one empty chunk: wave 0 still fetches the next step's knot differences
+      const int nchunks = max(1, (M + kTermChunk - 1) / kTermChunk);
       for (int ch = 0; ch < nchunks; ++ch) {
         const int tz = tid + opaque_zero();   // per-lane addresses re-made per step, not carried (and spilled) across the loop
         const int i = s0 + ch * kTermChunk + tz;
@@ -1522,8 +1523,9 @@ __global__ __launch_bounds__(BLOCK, (BLOCK >= 512 || (!RINGS_LDS && !SIGMA_LDS &
           refresh(r0, r1, q0, q1, mode);   // flag_mode: a flagged sample hands the instance to the RAISE instantiation
           RL_STAMP(st_t1); RL_STAMP_ADD(4, st_t1, st_t0);
           // what the refresh wrote to global memory (the bound points) is read next by the rows of the following step, behind the
-          // full barrier that ends its cost pass; until then the other waves read LDS only (control points, hints, c12)
-          if constexpr (RINGS_LDS) __syncthreads(); else lds_barrier();
+          // full barrier that ends its cost pass; until then the other waves read LDS only (control points, hints, c12).  The
+          // branch mode's single-pass phase 1 reads the bound points with no barrier in between: it needs the full one here.
+          if constexpr (RINGS_LDS || (LITE && RL_LITE_COST)) __syncthreads(); else lds_barrier();
           RL_STAMP(st_t0); RL_STAMP_ADD(5, st_t0, st_t1);
         } else {
         enum { A_NONE, A_REFRESH, A_FULL, A_UNDO };

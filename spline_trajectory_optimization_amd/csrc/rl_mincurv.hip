@@ -1,4 +1,4 @@
-// rl_mincurv.hip -- C ABI (include/rl_mincurv.h) over the HIP kernels in rl_kernels.hpp.
+// rl_mincurv.hip -- C ABI (include/rl_mincurv.h) over the HIP kernels in rl_kernels.hpp, rl_sweep.hpp and the headers below.
 // Built for gfx950 only:  hipcc -O3 -std=c++17 --offload-arch=gfx950 -shared -fPIC
 //
 // There is deliberately no CPU path in this library: every entry point launches HIP kernels and
@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "rl_kernels.hpp"
+#include "rl_sweep.hpp"
 #include "rl_qss_df.hpp"
 #include "rl_global.hpp"
 #include "rl_global2.hpp"
@@ -289,16 +290,16 @@ int check_spline(const double* t, int nt, const double* cx, const double* cy, in
 }
 
 struct SweepPlan {
-  bool rings_in_lds;
-  bool sigma_in_lds;
+  rl::Residency residency;
   size_t lds_bytes;
   size_t gscratch_doubles;  // per instance
   int block;
 };
 
 SweepPlan plan_sweep(const rl_ctx* ctx, int n, int N, int nL, int nR, int B, bool joint = false, bool strict = false) {
+  using rl::Residency;
   SweepPlan p;
-  p.block = 256;
+  p.block = rl::kSweepThreads;
   // Residency of the per-instance state (ring vertices 16 B x (nL + nR), crossings 8 B x 2N):
   //   all in LDS      : lowest latency per step, but ~120 KB at N = 2000 -> one workgroup per CU;
   //   all in global   : ~31 KB of LDS -> four workgroups per CU (VGPR-limited), state served by L1/L2;
@@ -312,79 +313,72 @@ SweepPlan plan_sweep(const rl_ctx* ctx, int n, int N, int nL, int nR, int B, boo
   if (force && (force[0] == '0' || force[0] == '1')) want = force[0] == '1' ? 0 : 1;
   if (const char* r = getenv("RL_FORCE_RESIDENCY")) if (r[0] >= '0' && r[0] <= '2') want = r[0] - '0';
   if (strict && want == 2) want = 0;   // the reference-order mode exists all-LDS and all-global
-  rl::SweepLds in = rl::sweep_lds_layout(n, N, nL, nR, true, true, joint, strict);
+  rl::SweepLds in = rl::sweep_lds_layout(n, N, nL, nR, Residency::Lds, joint, strict);
   if (want == 1 && in.total * sizeof(double) > (size_t)ctx->max_lds) want = 0;
   if (want == 2) {
-    rl::SweepLds mid = rl::sweep_lds_layout(n, N, nL, nR, false, true, joint);
+    rl::SweepLds mid = rl::sweep_lds_layout(n, N, nL, nR, Residency::CrossingsLds, joint);
     if (mid.total * sizeof(double) > (size_t)ctx->max_lds) want = 0;
   }
-  p.rings_in_lds = want == 1;
-  p.sigma_in_lds = want != 0;
-  rl::SweepLds L = rl::sweep_lds_layout(n, N, nL, nR, p.rings_in_lds, p.sigma_in_lds, joint, strict);
+  p.residency = want == 1 ? Residency::Lds : want == 2 ? Residency::CrossingsLds : Residency::Global;
+  rl::SweepLds L = rl::sweep_lds_layout(n, N, nL, nR, p.residency, joint, strict);
   p.lds_bytes = L.total * sizeof(double);
   // crossings (fast mode: one double per sample and side) or bound points (reference-order mode: two)
-  p.gscratch_doubles = (p.sigma_in_lds ? 0 : (size_t)2 * ((N + 1) & ~1) * (strict ? 2 : 1)) +
-                       (p.rings_in_lds ? 0 : (size_t)2 * (nL + rl::kRingPad) + (size_t)2 * (nR + rl::kRingPad));
+  p.gscratch_doubles = (p.residency != Residency::Global ? 0 : (size_t)2 * ((N + 1) & ~1) * (strict ? 2 : 1)) +
+                       (p.residency == Residency::Lds ? 0 : (size_t)2 * (nL + rl::kRingPad) + (size_t)2 * (nR + rl::kRingPad));
   return p;
 }
 
-template <int K, int BLOCK, bool RL, bool JOINT = false, bool DUMP = false, bool SL = RL, bool STRICT = false, bool RAISE = false,
-          bool LITE = false>
+template <class Cfg>
 int launch_sweep_t(const rl_ctx* ctx, const rl::SweepArgs& a, size_t lds) {
-  auto kern = rl::k_sweep<K, BLOCK, RL, JOINT, DUMP, SL, STRICT, RAISE, LITE>;
+  auto kern = rl::k_sweep<Cfg>;
   RL_HIP(grant_dyn_lds(const_cast<rl_ctx*>(ctx), reinterpret_cast<const void*>(kern), lds));
-  hipLaunchKernelGGL(kern, dim3(a.B), dim3(BLOCK), lds, ctx->stream, a);
+  hipLaunchKernelGGL(kern, dim3(a.B), dim3(rl::kSweepThreads), lds, ctx->stream, a);
   RL_HIP(hipGetLastError());
   return RL_OK;
 }
 
+// One instantiation in the residency the plan chose (all-LDS or all-global; the third residency has a line of its own below).
+constexpr bool kRecordSteps = true;   // the DUMP instantiation
+template <int K, rl::Driver DRIVER, rl::Arith ARITH, bool DUMP = false>
+int launch_sweep_in(const rl_ctx* ctx, const SweepPlan& p, const rl::SweepArgs& a) {
+  return p.residency == rl::Residency::Lds
+             ? launch_sweep_t<rl::SweepConfig<K, rl::Residency::Lds, DRIVER, ARITH, DUMP>>(ctx, a, p.lds_bytes)
+             : launch_sweep_t<rl::SweepConfig<K, rl::Residency::Global, DRIVER, ARITH, DUMP>>(ctx, a, p.lds_bytes);
+}
+
 int launch_sweep(const rl_ctx* ctx, int k, const SweepPlan& p, const rl::SweepArgs& a, bool joint = false, bool strict = false,
                  bool lite = false) {
+  using rl::Arith; using rl::Driver; using rl::Residency;
   if (strict) {   // RL_ARITH_REFERENCE / _BRANCH: degree-5 splines (the reference's wrap is written for k = 5, optimizer.py:281-285)
 #ifdef RL_STAMPS
-    if (k == 5 && !joint && !lite && !p.rings_in_lds)   // diagnostic build: the plain reference-order kernel with its phase stamps in a.dbg
-      return launch_sweep_t<5, 256, false, false, false, false, true>(ctx, a, p.lds_bytes);
+    if (k == 5 && !joint && !lite && p.residency == Residency::Global)   // diagnostic build: the plain reference-order kernel with its phase stamps in a.dbg
+      return launch_sweep_t<rl::SweepConfig<5, Residency::Global, Driver::Sweep, Arith::Reference>>(ctx, a, p.lds_bytes);
 #endif
     if (k != 5 || a.dbg || (joint && lite)) return fail(RL_ERR_UNSUPPORTED, "reference-order / branch arithmetic: degree-5 splines, no step dump; the sliding-window driver in the reference-order arithmetic only");
     if (joint)    // run_joint_min_curvature_qp in the reference-order arithmetic
-      return p.rings_in_lds ? launch_sweep_t<5, 256, true, true, false, true, true>(ctx, a, p.lds_bytes)
-                            : launch_sweep_t<5, 256, false, true, false, false, true>(ctx, a, p.lds_bytes);
+      return launch_sweep_in<5, Driver::Window, Arith::Reference>(ctx, p, a);
     if (lite)     // RL_ARITH_BRANCH
-      return p.rings_in_lds ? launch_sweep_t<5, 256, true, false, false, true, true, false, true>(ctx, a, p.lds_bytes)
-                            : launch_sweep_t<5, 256, false, false, false, false, true, false, true>(ctx, a, p.lds_bytes);
+      return launch_sweep_in<5, Driver::Sweep, Arith::Branch>(ctx, p, a);
     // the plain kernel flags the instances that need numpy's error state modelled (a sample of exactly zero curvature while
-    // numpy is in raise mode); the RAISE instantiation behind it redoes those and returns at once on all others
-    if (int rc = p.rings_in_lds ? launch_sweep_t<5, 256, true, false, false, true, true>(ctx, a, p.lds_bytes)
-                                : launch_sweep_t<5, 256, false, false, false, false, true>(ctx, a, p.lds_bytes)) return rc;
-    return p.rings_in_lds ? launch_sweep_t<5, 256, true, false, false, true, true, true>(ctx, a, p.lds_bytes)
-                          : launch_sweep_t<5, 256, false, false, false, false, true, true>(ctx, a, p.lds_bytes);
+    // numpy is in raise mode); the ReferenceRaise instantiation behind it redoes those and returns at once on all others
+    if (int rc = launch_sweep_in<5, Driver::Sweep, Arith::Reference>(ctx, p, a)) return rc;
+    return launch_sweep_in<5, Driver::Sweep, Arith::ReferenceRaise>(ctx, p, a);
   }
   if (joint) {
     if (k != 5) return fail(RL_ERR_UNSUPPORTED, "the sliding-window variant is built for degree 5 (span 5)");
-    return p.rings_in_lds ? launch_sweep_t<5, 256, true, true>(ctx, a, p.lds_bytes)
-                          : launch_sweep_t<5, 256, false, true>(ctx, a, p.lds_bytes);
+    return launch_sweep_in<5, Driver::Window, Arith::Fast>(ctx, p, a);
   }
-#ifdef RL_ABLATION
-  if (k == 5 && !joint && !p.rings_in_lds && !a.dbg && getenv("RL_SWEEP_BLOCK") && atoi(getenv("RL_SWEEP_BLOCK")) == 512)
-    return p.sigma_in_lds ? launch_sweep_t<5, 512, false, false, false, true>(ctx, a, p.lds_bytes)
-                          : launch_sweep_t<5, 512, false>(ctx, a, p.lds_bytes);
-#endif
-  if (k == 5 && !joint && !p.rings_in_lds && p.sigma_in_lds)
-    return launch_sweep_t<5, 256, false, false, false, true>(ctx, a, p.lds_bytes);
+  if (k == 5 && p.residency == Residency::CrossingsLds)
+    return launch_sweep_t<rl::SweepConfig<5, Residency::CrossingsLds>>(ctx, a, p.lds_bytes);
 #ifdef RL_STAMPS
-  if (k == 5 && !p.rings_in_lds && !p.sigma_in_lds) return launch_sweep_t<5, 256, false>(ctx, a, p.lds_bytes);  // stamps go to a.dbg
+  if (k == 5 && p.residency == Residency::Global) return launch_sweep_t<rl::SweepConfig<5, Residency::Global>>(ctx, a, p.lds_bytes);  // stamps go to a.dbg
 #endif
   if (k == 5) {
     if (a.dbg)  // recording instantiation (test aid): same source, one extra store block per step
-      return p.rings_in_lds ? launch_sweep_t<5, 256, true, false, true>(ctx, a, p.lds_bytes)
-                            : launch_sweep_t<5, 256, false, false, true>(ctx, a, p.lds_bytes);
-    return p.rings_in_lds ? launch_sweep_t<5, 256, true>(ctx, a, p.lds_bytes)
-                          : launch_sweep_t<5, 256, false>(ctx, a, p.lds_bytes);
+      return launch_sweep_in<5, Driver::Sweep, Arith::Fast, kRecordSteps>(ctx, p, a);
+    return launch_sweep_in<5, Driver::Sweep, Arith::Fast>(ctx, p, a);
   }
-  if (k == 3) {
-    return p.rings_in_lds ? launch_sweep_t<3, 256, true>(ctx, a, p.lds_bytes)
-                          : launch_sweep_t<3, 256, false>(ctx, a, p.lds_bytes);
-  }
+  if (k == 3) return launch_sweep_in<3, Driver::Sweep, Arith::Fast>(ctx, p, a);
   return fail(RL_ERR_UNSUPPORTED, "spline degree must be 3 or 5");
 }
 
@@ -879,9 +873,9 @@ static int solve_batch_common(rl_ctx* ctx, const rl_track* trk, int form, const 
   RL_HIP(hipSetDevice(ctx->device));
   SweepPlan p = plan_sweep(ctx, n, N, a.nL, a.nR, B, joint, strict);
   if (p.lds_bytes > (size_t)ctx->max_lds) return fail(RL_ERR_UNSUPPORTED, "problem does not fit LDS");
-  if (p.sigma_in_lds && !p.rings_in_lds && (joint || k != 5 || a.dbg)) {   // the mixed residency exists for the k = 5 sweep only
-    p.sigma_in_lds = false;
-    p.lds_bytes = rl::sweep_lds_layout(n, N, a.nL, a.nR, false, false, joint).total * sizeof(double);
+  if (p.residency == rl::Residency::CrossingsLds && (joint || k != 5 || a.dbg)) {   // the mixed residency exists for the k = 5 sweep only
+    p.residency = rl::Residency::Global;
+    p.lds_bytes = rl::sweep_lds_layout(n, N, a.nL, a.nR, rl::Residency::Global, joint).total * sizeof(double);
     p.gscratch_doubles += (size_t)2 * ((N + 1) & ~1);
   }
   if (p.gscratch_doubles) {
@@ -904,7 +898,7 @@ static int solve_batch_common(rl_ctx* ctx, const rl_track* trk, int form, const 
   if (stats) {
     stats->lds_bytes = (int)p.lds_bytes;
     stats->block_threads = p.block;
-    stats->rings_in_lds = p.rings_in_lds ? 1 : (p.sigma_in_lds ? 2 : 0);
+    stats->rings_in_lds = p.residency == rl::Residency::Lds ? 1 : (p.residency == rl::Residency::CrossingsLds ? 2 : 0);
     stats->reserved[0] = arith;
   }
   if (plan_out) *plan_out = p;

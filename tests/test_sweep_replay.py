@@ -28,7 +28,7 @@ from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
 
-HEAD = 16  # rl_kernels.hpp: kSweepDumpHead
+HEAD = 16  # rl_sweep.hpp: kSweepDumpHead
 
 
 def _record(rl, trk, widths, i_start, n_inst):

@@ -29,13 +29,13 @@ for line in open(os.path.join(src, "stats.log")):
 
 
 def match(name, pattern):
-    """pattern = "substring" or "substring|end of the template argument list": k_sweep's instantiations differ in their
-    last two template arguments (STRICT: the reference-order arithmetic; RAISE: its numpy-error-state variant, which
-    returns at once for instances that do not need it)."""
+    """pattern = "substring" or "substring|second substring": k_sweep's instantiations are told apart by the arithmetic in
+    their configuration, rl::SweepConfig<K, Residency, Driver, Arith, DUMP> (a demangler prints an enumerator as a cast
+    of its value: `(rl::Arith)1`)."""
     sub, _, last = pattern.partition("|")
     if sub not in name:
         return False
-    return not last or name.split(">(")[0].rstrip().endswith(last)
+    return not last or last in name
 
 
 def durations(fname, pattern):
@@ -76,9 +76,11 @@ def per_kernel(pattern):
 
 
 kernels = {}
-# k_sweep<K, BLOCK, RINGS_LDS, JOINT, DUMP, SIGMA_LDS, STRICT, RAISE, LITE>: told apart by the last three arguments
-for name, pat in (("k_sweep", "k_sweep<|false, false, false"), ("k_sweep_reference_order", "k_sweep<|true, false, false"),
-                  ("k_sweep_reference_order_raise", "k_sweep<|true, true, false"), ("k_sweep_branch", "k_sweep<|true, false, true"),
+# the explicit values of enum class Arith in csrc/rl_sweep.hpp
+ARITH = {"Fast": 0, "Reference": 1, "ReferenceRaise": 2, "Branch": 3}
+sweep = lambda arith: f"k_sweep<|(rl::Arith){ARITH[arith]}"
+for name, pat in (("k_sweep", sweep("Fast")), ("k_sweep_reference_order", sweep("Reference")),
+                  ("k_sweep_reference_order_raise", sweep("ReferenceRaise")), ("k_sweep_branch", sweep("Branch")),
                   ("k_global_qp", "k_global_qp"), ("k_global_xy", "k_global_xy<")):
     k = per_kernel(pat)
     if k:

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """One launch configuration of the sweep kernel on the benchmarked batch (Monza, N = 2000, 1024 instances, max_iter = 5):
-kernel time and a digest of the results, for A/B runs of diagnostic builds (RL_LIB_PATH, RL_SWEEP_BLOCK, RL_FORCE_RESIDENCY).
+kernel time and a digest of the results, for A/B runs of diagnostic builds (RL_LIB_PATH, RL_FORCE_RESIDENCY).
 python tools/sweep_variant.py [out.npy]"""
 import hashlib, os, sys
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo")); sys.path.insert(0, os.path.join(os.environ.get("GRAFT_REPO_ROOT", "/root/repo"), "tests"))
@@ -20,5 +20,5 @@ ms = []
 for rep in range(4):
     ctrl, xy, ns, status, st = ops.solve_batch_host(trk, _lib.BOUNDS_WIDTHS, W, i_start)
     ms.append(st.kernel_ms)
-print({v: os.environ.get(v) for v in ("RL_LIB_PATH", "RL_SWEEP_BLOCK", "RL_FORCE_RESIDENCY")}, "kernel ms", [round(m, 3) for m in ms],
+print({v: os.environ.get(v) for v in ("RL_LIB_PATH", "RL_FORCE_RESIDENCY")}, "kernel ms", [round(m, 3) for m in ms],
       "block", st.block_threads, "lds", st.lds_bytes, "digest", hashlib.sha1(ctrl.tobytes()).hexdigest()[:12])

@@ -123,6 +123,8 @@ int rl_ctx_set_numpy_raise(rl_ctx* ctx, int on);
  *   "qss_df_waves"    1 | 2 | 4 waves per instance of the dataflow kernel (default 4)
  *   "qss_df_bail_at"  g > 0: the dataflow kernel hands every instance back to the list-order kernel at iteration g (the path
  *                     taken when its tables overflow); 0 = never
+ *   "tables_search"   RL_SEARCH_BRUTE | _CULLED | _WINDOWED (default): ring search of rl_tables_batch_*
+ *   "tables_rings"    0 = rl_tables_batch_* keeps an instance's ring vertices in LDS where they fit (default), 1 = in the arena
  * Defaults come from RL_QSS_DF / RL_QSS_V1 / RL_QSS_DF_WAVES / RL_QSS_DF_BAIL_AT, read ONCE in rl_ctx_create. */
 int rl_ctx_set_option(rl_ctx* ctx, const char* name, int value);
 /* test aid: out[n,5] = yaw, cos / sin(yaw + pi/2), cos / sin(yaw - pi/2) of the tangents (dx, dy), as the
@@ -409,6 +411,37 @@ int rl_qss_sim(rl_ctx* ctx, double* points, int B, int N, const double* acc_x, c
 int rl_qss_sim_dev(rl_ctx* ctx, double* points, int B, int N, const double* acc_x, const double* acc_c,
                    int acc_m, const double* dcc_x, const double* dcc_c, int dcc_m, const double* params,
                    int* iters);
+
+/* ---- tables of a solved batch (csrc/rl_tables.hpp).  For every instance b: the table BSplineTrajectory.sample_along(ts = i/N)
+ * builds from the spline (trk's knots, ctrl[b]) (models/trajectory.py:268-291), then Trajectory.fill_bounds against that
+ * instance's rings (models/trajectory.py:83-141, max_dist 100: race_track.py:104) -- one launch for the batch.
+ *   ctrl        [B,n,2]  (out_ctrl of any batched solve, or any control points on trk's knots)
+ *   bounds_form / bounds  exactly as rl_mincurv_solve_batch_dev defines an instance's rings: RL_BOUNDS_SHARED_RINGS (trk's
+ *               rings, bounds NULL), RL_BOUNDS_WIDTHS [B,N,2] (vertex i = p0_i +- w n0_i from trk's INITIAL control points, in the
+ *               arithmetic the sweep of this context builds them with), RL_BOUNDS_POINTS [B,N,4]
+ *   length      BSplineTrajectory._length for DIST_TO_SF_FWD (the length of the spline as constructed, as
+ *               rl_track_set_length documents); <= 0: both DIST columns stay 0
+ *   bank        NULL or [N] / [B,N] values copied into BANK (config 4); bank_per_instance != 0: [B,N]
+ *   points      [B,N,19] out: X, Y, YAW, CURVATURE (turn radius), DIST_TO_SF_BWD / _FWD (running sum in index order), the four
+ *               bound columns, BANK, IDX = i, ITERATION_FLAG = -1, every other column 0
+ * The arithmetic is that of rl_sample_along and rl_fill_bounds (a legal rounding of the reference's, not its bits).
+ * RL_ERR_ARG for nulls, B <= 0, WIDTHS / POINTS without `bounds`, SHARED_RINGS without rings.
+ * *_dev: device pointers, enqueued on the context's stream, no synchronisation; rings that do not fit LDS live in the context's
+ * grow-only arena (a repeated call of the same shape allocates nothing).  *_host: host pointers, synchronises.
+ * Test hooks (rl_ctx_set_option, bit-identical results): "tables_search" RL_SEARCH_* (default windowed), "tables_rings"
+ * 0 = ring vertices in LDS where they fit (default), 1 = always in the arena. */
+int rl_tables_batch_dev(rl_ctx* ctx, const rl_track* trk, const double* ctrl, int B, int bounds_form, const double* bounds,
+                        double length, const double* bank, int bank_per_instance, double* points);
+int rl_tables_batch_host(rl_ctx* ctx, const rl_track* trk, const double* ctrl, int B, int bounds_form, const double* bounds,
+                         double length, const double* bank, int bank_per_instance, double* points);
+
+/* Per-instance summary of simulated tables points [B,N,19]: out [B,8] = lap time (sum of TIME, added in index order), the
+ * reference's total_time (TIME[0], simulator.py:378), its average_speed (DIST_TO_SF_FWD[0] / TIME[0], :379-380), max / min
+ * SPEED, max LAT_ACC, max / min LON_ACC (:381-385).  A NaN in a column gives NaN (numpy's max / min).  iters (may be NULL):
+ * an instance with iters[b] < 0 (rl_qss_sim's "the reference would have raised") gets NaN in all eight.
+ * *_dev: device pointers, context's stream, no synchronisation, no scratch.  *_host: host pointers, synchronises. */
+int rl_table_summary_dev(rl_ctx* ctx, const double* points, int B, int N, const int* iters, double* out);
+int rl_table_summary_host(rl_ctx* ctx, const double* points, int B, int N, const int* iters, double* out);
 
 #ifdef __cplusplus
 }

@@ -101,6 +101,12 @@ _SIGNATURES = {
                                                       _vp, _vp, _vp, _vp, ctypes.POINTER(Stats)]),
     "rl_mincurv_global_xy_batch_host": (ctypes.c_int, [_vp, _vp, _dp, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                                        ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.POINTER(Stats)]),
+    "rl_tables_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_double, _vp,
+                                           ctypes.c_int, _vp]),
+    "rl_tables_batch_host": (ctypes.c_int, [_vp, _vp, _dp, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_double, _dp,
+                                            ctypes.c_int, _dp]),
+    "rl_table_summary_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp]),
+    "rl_table_summary_host": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _ip, _dp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -193,7 +199,8 @@ class Context:
         return old
 
     def set_option(self, name, value):
-        """Test hooks (include/rl_mincurv.h: rl_ctx_set_option): "qss_kernel", "qss_df_waves", "qss_df_bail_at"."""
+        """Test hooks (include/rl_mincurv.h: rl_ctx_set_option): "qss_kernel", "qss_df_waves", "qss_df_bail_at",
+        "tables_search", "tables_rings"."""
         check(self.lib.rl_ctx_set_option(self.h, name.encode(), int(value)))
 
     def set_numpy_raise(self, on):

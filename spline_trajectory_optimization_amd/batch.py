@@ -117,6 +117,51 @@ def make_track(spline: BSplineTrajectory, N: int, device=None):
     return _lib.Track(_lib.Context.get(device), t, cx, cy, k, N)
 
 
+# ---------------------------------------------------------------- solved batch -> tables -> lap times
+def vehicle_tables(vehicle):
+    """(acc_x, acc_c, dcc_x, dcc_c, params) of a Vehicle as rl_qss_sim takes them; a 5-tuple is passed through."""
+    if isinstance(vehicle, (tuple, list)):
+        if len(vehicle) != 5:
+            raise ValueError("vehicle: a Vehicle or the 5-tuple (acc_x, acc_c, dcc_x, dcc_c, params)")
+        return tuple(vehicle)
+    p = vehicle.param
+    acc, dcc = vehicle.acc_intp, vehicle.dcc_intp   # scipy CubicSpline (vehicle.py:21-24)
+    params = np.array([p.max_lon_acc_mpss, p.max_lon_dcc_mpss, p.max_left_acc_mpss, p.max_right_acc_mpss, p.max_speed_mps,
+                       p.max_jerk], dtype=np.float64)
+    return (np.ascontiguousarray(acc.x), np.ascontiguousarray(acc.c), np.ascontiguousarray(dcc.x),
+            np.ascontiguousarray(dcc.c), params)
+
+
+def lap_times_torch(track, ctrl, bounds_form, bounds, length, vehicle, bank=None):
+    """Which of these B solved lines is the fastest lap, and what is its table: tables of the batch (ops.tables_torch) ->
+    QSS simulation in place (ops.qss_sim_torch) -> per-instance summary (ops.table_summary_torch), all enqueued on torch's
+    current stream with no host round trip.  ctrl [B,n,2] (e.g. solve_batch_torch(...)["ctrl"]), bounds / bank as for
+    ops.tables_torch, vehicle = a Vehicle or vehicle_tables(...).  Returns dict(points [B,N,19], iters [B] int32,
+    summary [B,8] in the order of ops.SUMMARY_COLUMNS) of cuda tensors."""
+    veh = vehicle_tables(vehicle)
+    points = ops.tables_torch(track, ctrl, bounds_form, bounds, length, bank=bank)
+    iters = ops.qss_sim_torch(points, *veh)
+    summary = ops.table_summary_torch(points, iters)
+    return {"points": points, "iters": iters, "summary": summary}
+
+
+def lap_times_host(track, ctrl, bounds_form, bounds, length, vehicle, bank=None):
+    """lap_times_torch for numpy input (float64, C-contiguous): copies in, runs the same chain on the track's device, copies
+    out.  Returns dict(points, iters, summary) of numpy arrays."""
+    import torch
+    veh = vehicle_tables(vehicle)
+    B, bshape, kshape, _ = ops._tables_shapes(track, ctrl, bounds_form, bounds, bank)
+    ops._check_np(ctrl, "ctrl", (B, track.n, 2))
+    if bshape:
+        ops._check_np(bounds, "bounds", bshape)
+    if kshape:
+        ops._check_np(bank, "bank", kshape)
+    dev = torch.device("cuda", track.ctx.device)
+    up = lambda a: None if a is None else torch.from_numpy(a).to(dev)  # noqa: E731
+    out = lap_times_torch(track, up(ctrl), bounds_form, up(bounds), length, veh, bank=up(bank))
+    return {k_: v.cpu().numpy() for k_, v in out.items()}
+
+
 # ---------------------------------------------------------------- min-time NLP plumbing (config 5)
 def min_time_initial_guess(points):
     """The initial guess the reference hands to its min-time NLP when no previous solution is given

@@ -26,6 +26,7 @@
 #include "rl_mintime.hpp"
 #include "rl_bicycle.hpp"
 #include "rl_region.hpp"
+#include "rl_tables.hpp"
 
 namespace {
 
@@ -84,6 +85,8 @@ struct rl_ctx {
   // once in rl_ctx_create): which kernel (-1 = by the rounds the batch takes, 0 = list order, 1 = dataflow), waves per instance of
   // the dataflow kernel, the iteration at which it hands every instance back (0 = never)
   int qss_kernel = -1, qss_df_waves = 4, qss_df_bail_at = 0;
+  // test hooks of rl_tables_batch_*: ring search (RL_SEARCH_*), 1 = ring vertices in the arena even where they fit LDS
+  int tables_search = RL_SEARCH_WINDOWED, tables_rings_global = 0;
   // largest dynamic-LDS size already granted per kernel (hipFuncSetAttribute is issued only when a call needs more)
   // Device scratch owned by the context (grow-only): the *_dev entry points of the QSS simulator and the
   // min-time solve carve their work arrays out of it, so that steady-state calls allocate nothing.
@@ -508,6 +511,8 @@ int rl_ctx_set_option(rl_ctx* ctx, const char* name, int value) {
   if (k == "qss_kernel") { if (value < -1 || value > 1) return fail(RL_ERR_ARG, "qss_kernel: -1 (auto), 0 (list order), 1 (dataflow)"); ctx->qss_kernel = value; }
   else if (k == "qss_df_waves") { if (value != 1 && value != 2 && value != 4) return fail(RL_ERR_ARG, "qss_df_waves: 1, 2 or 4"); ctx->qss_df_waves = value; }
   else if (k == "qss_df_bail_at") { if (value < 0) return fail(RL_ERR_ARG, "qss_df_bail_at >= 0"); ctx->qss_df_bail_at = value; }
+  else if (k == "tables_search") { if (value < RL_SEARCH_BRUTE || value > RL_SEARCH_WINDOWED) return fail(RL_ERR_ARG, "tables_search: RL_SEARCH_BRUTE, _CULLED or _WINDOWED"); ctx->tables_search = value; }
+  else if (k == "tables_rings") { if (value != 0 && value != 1) return fail(RL_ERR_ARG, "tables_rings: 0 (LDS where they fit) or 1 (arena)"); ctx->tables_rings_global = value; }
   else return fail(RL_ERR_ARG, "unknown option '" + k + "'");
   return RL_OK;
 }
@@ -1459,6 +1464,124 @@ int rl_qss_sim(rl_ctx* ctx, double* points, int B, int N, const double* acc_x, c
   if (int rc = rl_qss_sim_dev(ctx, dpts.p, B, N, acc_x, acc_c, acc_m, dcc_x, dcc_c, dcc_m, params, dit.p)) return rc;
   RL_HIP(hipMemcpyAsync(points, dpts.p, dpts.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   RL_HIP(hipMemcpyAsync(iters, dit.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  RL_HIP(hipStreamSynchronize(ctx->stream));
+  return RL_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// tables of a solved batch and their summary (csrc/rl_tables.hpp)
+extern "C++" {
+template <int K>
+static int launch_tables(rl_ctx* ctx, const rl::TablesArgs& a, bool rings_lds, size_t lds) {
+  const void* fn = rings_lds ? reinterpret_cast<const void*>(rl::k_tables<K, true>) : reinterpret_cast<const void*>(rl::k_tables<K, false>);
+  RL_HIP(grant_dyn_lds(ctx, fn, lds));
+  if (rings_lds) hipLaunchKernelGGL((rl::k_tables<K, true>), dim3(a.B), dim3(rl::kTablesThreads), lds, ctx->stream, a);
+  else hipLaunchKernelGGL((rl::k_tables<K, false>), dim3(a.B), dim3(rl::kTablesThreads), lds, ctx->stream, a);
+  RL_HIP(hipGetLastError());
+  return RL_OK;
+}
+}  // extern "C++"
+
+int rl_tables_batch_dev(rl_ctx* ctx, const rl_track* trk, const double* ctrl, int B, int bounds_form, const double* bounds,
+                        double length, const double* bank, int bank_per_instance, double* points) {
+  if (!ctx || !trk || !ctrl || !points) return fail(RL_ERR_ARG, "null argument");
+  if (B <= 0) return fail(RL_ERR_ARG, "B <= 0");
+  if (!degree_supported(trk->k)) return fail(RL_ERR_UNSUPPORTED, "spline degree must be 3 or 5");
+  const int n = trk->n, N = trk->N, k = trk->k;
+  rl::TablesArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.ctrl = ctrl; a.B = B; a.form = bounds_form; a.in = bounds;
+  if (bounds_form == RL_BOUNDS_SHARED_RINGS) {
+    if (trk->nL == 0) return fail(RL_ERR_ARG, "rl_track_set_rings was not called");
+    a.ringL = reinterpret_cast<const double2*>(trk->ringL.p);
+    a.ringR = reinterpret_cast<const double2*>(trk->ringR.p);
+    a.nL = trk->nL; a.nR = trk->nR;
+  } else if (bounds_form == RL_BOUNDS_WIDTHS || bounds_form == RL_BOUNDS_POINTS) {
+    if (!bounds) return fail(RL_ERR_ARG, "bounds input is null");
+    a.nL = N; a.nR = N;
+  } else {
+    return fail(RL_ERR_ARG, "bad bounds_form");
+  }
+  RL_HIP(hipSetDevice(ctx->device));
+  // width-form rings in the arithmetic the sweep of this context builds them with: the reference-order tables where that
+  // arithmetic exists (degree 5) and was not switched off, the fast tables elsewhere
+  if (bounds_form == RL_BOUNDS_WIDTHS && k == 5 && ctx->arith != RL_ARITH_FAST) {
+    if (int rc = ensure_strict_tables(ctx, trk)) return rc;
+    a.strict_rings = 1;
+  }
+  a.tr = trk->dev();
+  a.search = ctx->tables_search;
+  a.max_dist = 100.0;   // race_track.py:104
+  a.length = length;
+  a.bank = bank; a.bank_per_instance = bank_per_instance;
+  a.points = points;
+  bool rings_lds = !ctx->tables_rings_global;
+  size_t lds = rl::tables_lds_layout(trk->nt, n, N, a.nL, a.nR, true).total * sizeof(double);
+  if (lds > (size_t)ctx->max_lds) rings_lds = false;
+  if (!rings_lds) lds = rl::tables_lds_layout(trk->nt, n, N, a.nL, a.nR, false).total * sizeof(double);
+  if (lds > (size_t)ctx->max_lds) return fail(RL_ERR_UNSUPPORTED, "tables: the instance does not fit LDS");
+  Arena ar(ctx);
+  if (!rings_lds) {
+    a.gscratch_stride = rl::tables_ring_scratch_doubles(a.nL, a.nR);
+    RL_HIP(ar.reserve(Arena::pad(a.gscratch_stride * (size_t)B * sizeof(double))));
+    a.gscratch = ar.take<double>(a.gscratch_stride * (size_t)B);
+  }
+  if (int rc = (k == 3 ? launch_tables<3>(ctx, a, rings_lds, lds) : launch_tables<5>(ctx, a, rings_lds, lds))) return rc;
+  if (!rings_lds) RL_HIP(ar.end());
+  return RL_OK;
+}
+
+int rl_tables_batch_host(rl_ctx* ctx, const rl_track* trk, const double* ctrl, int B, int bounds_form, const double* bounds,
+                         double length, const double* bank, int bank_per_instance, double* points) {
+  if (!ctx || !trk || !ctrl || !points) return fail(RL_ERR_ARG, "null argument");
+  if (B <= 0) return fail(RL_ERR_ARG, "B <= 0");
+  const int cols = bounds_form == RL_BOUNDS_WIDTHS ? 2 : (bounds_form == RL_BOUNDS_POINTS ? 4 : 0);
+  if (cols && !bounds) return fail(RL_ERR_ARG, "bounds input is null");
+  RL_HIP(hipSetDevice(ctx->device));
+  const int n = trk->n, N = trk->N;
+  PoolBuf<double> dctrl(ctx), din(ctx), dbank(ctx), dpts(ctx);
+  RL_HIP(dctrl.alloc((size_t)B * n * 2)); RL_HIP(dpts.alloc((size_t)B * N * RL_NCOL));
+  RL_HIP(hipMemcpyAsync(dctrl.p, ctrl, dctrl.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  if (cols) {
+    RL_HIP(din.alloc((size_t)B * N * cols));
+    RL_HIP(hipMemcpyAsync(din.p, bounds, din.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (bank) {
+    RL_HIP(dbank.alloc((size_t)(bank_per_instance ? B : 1) * N));
+    RL_HIP(hipMemcpyAsync(dbank.p, bank, dbank.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (int rc = rl_tables_batch_dev(ctx, trk, dctrl.p, B, bounds_form, din.p, length, dbank.p, bank_per_instance, dpts.p)) return rc;
+  RL_HIP(hipMemcpyAsync(points, dpts.p, dpts.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  RL_HIP(hipStreamSynchronize(ctx->stream));
+  return RL_OK;
+}
+
+int rl_table_summary_dev(rl_ctx* ctx, const double* points, int B, int N, const int* iters, double* out) {
+  if (!ctx || !points || !out) return fail(RL_ERR_ARG, "null argument");
+  if (B <= 0 || N <= 0) return fail(RL_ERR_ARG, "bad sizes");
+  const size_t lds = (size_t)N * sizeof(double);
+  if (lds > (size_t)ctx->max_lds) return fail(RL_ERR_UNSUPPORTED, "table summary: trajectory too long for the LDS-resident TIME column");
+  RL_HIP(hipSetDevice(ctx->device));
+  RL_HIP(grant_dyn_lds(ctx, reinterpret_cast<const void*>(rl::k_table_summary), lds));
+  hipLaunchKernelGGL(rl::k_table_summary, dim3(B), dim3(rl::kWave), lds, ctx->stream, points, N, iters, out);
+  RL_HIP(hipGetLastError());
+  return RL_OK;
+}
+
+int rl_table_summary_host(rl_ctx* ctx, const double* points, int B, int N, const int* iters, double* out) {
+  if (!ctx || !points || !out) return fail(RL_ERR_ARG, "null argument");
+  if (B <= 0 || N <= 0) return fail(RL_ERR_ARG, "bad sizes");
+  RL_HIP(hipSetDevice(ctx->device));
+  PoolBuf<double> dpts(ctx), dout(ctx);
+  PoolBuf<int> dit(ctx);
+  RL_HIP(dpts.alloc((size_t)B * N * RL_NCOL)); RL_HIP(dout.alloc((size_t)B * 8));
+  RL_HIP(hipMemcpyAsync(dpts.p, points, dpts.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  if (iters) {
+    RL_HIP(dit.alloc(B));
+    RL_HIP(hipMemcpyAsync(dit.p, iters, (size_t)B * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (int rc = rl_table_summary_dev(ctx, dpts.p, B, N, dit.p, dout.p)) return rc;
+  RL_HIP(hipMemcpyAsync(out, dout.p, dout.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   RL_HIP(hipStreamSynchronize(ctx->stream));
   return RL_OK;
 }

@@ -330,6 +330,133 @@ def qss_sim(points, acc_x, acc_c, dcc_x, dcc_c, params, device=None):
     return (pts[0] if single else pts), it
 
 
+SUMMARY_COLUMNS = ("lap_time", "total_time", "average_speed", "max_speed", "min_speed", "max_lat_acc", "max_lon_acc",
+                   "max_lon_dcc")   # rl_table_summary_*: out[B,8]
+_BOUNDS_COLS = {_lib.BOUNDS_SHARED_RINGS: 0, _lib.BOUNDS_WIDTHS: 2, _lib.BOUNDS_POINTS: 4}
+
+
+def _check_np(a, name, shape, dtype=np.float64):
+    """A caller's numpy array as the C ABI takes it: ValueError before any device call otherwise."""
+    if not isinstance(a, np.ndarray) or a.dtype != dtype:
+        raise ValueError(f"{name}: expected a numpy {np.dtype(dtype).name} array, got {getattr(a, 'dtype', type(a))}")
+    if tuple(a.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(a.shape)}")
+    if not a.flags.c_contiguous:
+        raise ValueError(f"{name}: must be C-contiguous")
+    return a
+
+
+def _check_torch(a, name, shape, dtype=None):
+    import torch
+    dtype = dtype or torch.float64
+    if not isinstance(a, torch.Tensor) or not a.is_cuda or a.dtype != dtype:
+        raise ValueError(f"{name}: expected a cuda tensor of {dtype}")
+    if tuple(a.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(a.shape)}")
+    if not a.is_contiguous():
+        raise ValueError(f"{name}: must be contiguous")
+    return a
+
+
+def _tables_shapes(track, ctrl, bounds_form, bounds, bank):
+    """(B, bounds shape | None, bank shape | None, bank_per_instance) of a tables call; ValueError for a bad form / rank."""
+    if bounds_form not in _BOUNDS_COLS:
+        raise ValueError(f"bounds_form: one of BOUNDS_SHARED_RINGS / _WIDTHS / _POINTS, got {bounds_form!r}")
+    if getattr(ctrl, "ndim", None) != 3:
+        raise ValueError(f"ctrl: expected [B,{track.n},2]")
+    B = int(ctrl.shape[0])
+    if B <= 0:
+        raise ValueError("ctrl: empty batch")
+    cols = _BOUNDS_COLS[bounds_form]
+    if (bounds is None) != (cols == 0):
+        raise ValueError("bounds: None for BOUNDS_SHARED_RINGS, [B,N,2] widths / [B,N,4] points otherwise")
+    per = bank is not None and getattr(bank, "ndim", 1) == 2
+    return B, ((B, track.N, cols) if cols else None), (None if bank is None else ((B, track.N) if per else (track.N,))), per
+
+
+def tables_host(track, ctrl, bounds_form, bounds, length, bank=None):
+    """Tables of a solved batch (rl_tables_batch_host): per instance BSplineTrajectory.sample_along(ts = i/N) of the spline
+    (track's knots, ctrl[b]) + Trajectory.fill_bounds against the instance's rings (models/trajectory.py:268-291, 83-141).
+    ctrl [B,n,2]; bounds None / widths [B,N,2] / points [B,N,4] as for solve_batch_host; bank None, [N] or [B,N].
+    numpy float64, C-contiguous.  Returns points [B,N,19]."""
+    B, bshape, kshape, per = _tables_shapes(track, ctrl, bounds_form, bounds, bank)
+    _check_np(ctrl, "ctrl", (B, track.n, 2))
+    if bshape:
+        _check_np(bounds, "bounds", bshape)
+    if kshape:
+        _check_np(bank, "bank", kshape)
+    ctx = track.ctx
+    pts = np.empty((B, track.N, _lib.NCOL))
+    check(ctx.lib.rl_tables_batch_host(ctx.h, track.h, ctrl.ctypes.data_as(_dp), B, int(bounds_form),
+                                       bounds.ctypes.data_as(_dp) if bshape else None, float(length),
+                                       bank.ctypes.data_as(_dp) if kshape else None, int(per), pts.ctypes.data_as(_dp)))
+    return pts
+
+
+def tables_torch(track, ctrl, bounds_form, bounds, length, bank=None, out=None):
+    """tables_host on DEVICE tensors (float64 cuda, contiguous): enqueues on torch's current stream, no sync
+    (rl_tables_batch_dev).  Returns the cuda tensor points [B,N,19] (`out` if given)."""
+    import torch
+    B, bshape, kshape, per = _tables_shapes(track, ctrl, bounds_form, bounds, bank)
+    _check_torch(ctrl, "ctrl", (B, track.n, 2))
+    if bshape:
+        _check_torch(bounds, "bounds", bshape)
+    if kshape:
+        _check_torch(bank, "bank", kshape)
+    dev = ctrl.device
+    if out is None:
+        out = torch.empty((B, track.N, _lib.NCOL), dtype=torch.float64, device=dev)
+    _check_torch(out, "out", (B, track.N, _lib.NCOL))
+    ctx = track.ctx
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    p = lambda t_: ctypes.c_void_p(t_.data_ptr())  # noqa: E731
+    check(ctx.lib.rl_tables_batch_dev(ctx.h, track.h, p(ctrl), B, int(bounds_form), p(bounds) if bshape else None,
+                                      float(length), p(bank) if kshape else None, int(per), p(out)))
+    return out
+
+
+def table_summary(points, iters=None, device=None):
+    """Per-instance summary of simulated tables [B,N,19] (numpy): [B,8] in the order of SUMMARY_COLUMNS -- lap time (TIME
+    added up in index order) and the scalars of the reference's SimulationResult (simulator.py:375-386).  iters [B] int32
+    (optional): instances with iters < 0 are NaN throughout."""
+    if getattr(points, "ndim", None) != 3:
+        raise ValueError("points: expected [B,N,19]")
+    B, N = int(points.shape[0]), int(points.shape[1])
+    _check_np(points, "points", (B, N, _lib.NCOL))
+    if B <= 0 or N <= 0:
+        raise ValueError("points: empty")
+    if iters is not None:
+        _check_np(iters, "iters", (B,), np.int32)
+    ctx = Context.get(device)
+    out = np.empty((B, 8))
+    check(ctx.lib.rl_table_summary_host(ctx.h, points.ctypes.data_as(_dp), B, N,
+                                        iters.ctypes.data_as(_ip) if iters is not None else None, out.ctypes.data_as(_dp)))
+    return out
+
+
+def table_summary_torch(points, iters=None, out=None):
+    """table_summary on DEVICE tensors: points float64 cuda [B,N,19], iters int32 cuda [B] or None; torch's current stream,
+    no sync (rl_table_summary_dev).  Returns the cuda tensor [B,8]."""
+    import torch
+    if getattr(points, "ndim", None) != 3:
+        raise ValueError("points: expected [B,N,19]")
+    B, N = int(points.shape[0]), int(points.shape[1])
+    _check_torch(points, "points", (B, N, _lib.NCOL))
+    if B <= 0 or N <= 0:
+        raise ValueError("points: empty")
+    if iters is not None:
+        _check_torch(iters, "iters", (B,), torch.int32)
+    if out is None:
+        out = torch.empty((B, 8), dtype=torch.float64, device=points.device)
+    _check_torch(out, "out", (B, 8))
+    ctx = Context.get(points.device.index)
+    ctx.set_stream(torch.cuda.current_stream(points.device).cuda_stream)
+    check(ctx.lib.rl_table_summary_dev(ctx.h, ctypes.c_void_p(points.data_ptr()), B, N,
+                                       ctypes.c_void_p(iters.data_ptr()) if iters is not None else None,
+                                       ctypes.c_void_p(out.data_ptr())))
+    return out
+
+
 DT_PARAMS = ["kd_f", "kb_f", "mass", "Jzz", "lf", "lr", "twf", "twr", "delta_max", "fr", "hcog", "kroll_f",
              "cl_f", "cl_r", "rho", "A", "cd", "mu", "Bf", "Cf", "Br", "Cr", "Pmax", "Fd_max", "Fb_max",
              "Td", "Tb", "Tdelta"]  # include/rl_mincurv.h: rl_dt_param

@@ -1,0 +1,335 @@
+"""A solver-agnostic first-order optimality certificate (numpy + scipy only; nothing from csrc, no CPU twin).
+
+A point w of   min f(w)  s.t.  c(w) = 0,  d(w) <= 0   is a KKT point iff the cost gradient lies in the cone of the
+constraint gradients:  gf + Jc' y + Jd' z = 0  with  z >= 0  and  z_i d_i = 0  row by row.  `certify` looks for the best
+such multipliers with ONE bounded linear least-squares problem over (y free, z >= 0) on the stacked residual
+
+    [ gf + Jc' y + Jd' z ]      stationarity, in the unknowns' own scaling
+    [ diag(-d) z          ]      complementarity, row by row
+
+EVERY inequality row takes part: there is no active-set threshold (a free parameter that could hide a failure).  An
+inactive row (d_i < 0) pays |d_i| z_i for a multiplier, so it gets none; a tight row gets one for free.
+
+The rest of the module states the three optimiser families' problems for the certificate from evaluators that the
+reference pins and that no solver wrote:
+  * the global min-curvature QPs: P, q, A handed in (tests/test_global_qp.py: NumpyGlobal, test_global_qp_xy.py:
+    NumpyGlobalXY), rows lo <= A a <= hi;
+  * the bicycle min-time NLP on the host mirrors models/dynamic_bicycle.py + utils/integrator.py + utils/utils.py
+    (fixture G13, 1e-12);
+  * the double-track min-time NLP on oracle/dt_checker.py (fixture G8, 1e-13).
+NLP Jacobians are 4th-order central differences of those evaluators (Richardson on steps h and 2h; the difference to the
+same formula on the tighter steps h / 2 and h is their own, printed, error).  A function of pair j depends on nodes j and j+1 only, so one
+unknown is moved at every node of one colour at a time (2 colours, 3 on an odd ring): the whole block-bidiagonal Jacobian
+costs colours x 6 x n_var evaluations, all stacked into one call of the evaluator."""
+from dataclasses import dataclass
+
+import numpy as np
+import scipy.sparse as sp
+from scipy.optimize import lsq_linear
+
+
+@dataclass
+class Certificate:
+    stat: float            # |gf + Jc' y + Jd' z|_inf
+    compl: float           # |d z|_inf
+    viol: float            # max(|c|_inf, max(d, 0))
+    y: np.ndarray
+    z: np.ndarray
+    s_d: float             # IPOPT's dual scaling max(100, mean(|y|, |z|)) / 100
+    s_c: float             # IPOPT's complementarity scaling max(100, mean |z|) / 100
+    r_stat: np.ndarray     # the stationarity block itself (the largest entry names the unknown)
+    r_compl: np.ndarray
+
+
+def bounded_lsq_sparse(M, b, nfree, max_iter=200):
+    """min |M x - b|_2 with x[nfree:] >= 0 for a sparse M of full column rank: block principal pivoting (Kim & Park 2011)
+    on the passive set, every pass one sparse LU of the augmented system [[I, M_F], [M_F', 0]] of the least-squares problem
+    on the passive columns F.  scipy.optimize.lsq_linear needs 50 s on the 128-node ring (measured, BVLS and TRF / LSMR
+    alike), this 0.1 s; tests/test_optimality_cpu.py holds the two against each other where both run."""
+    from scipy.sparse.linalg import splu
+    M = sp.csc_matrix(M)
+    m, n = M.shape
+    bound = np.arange(n) >= nfree
+    passive = np.ones(n, dtype=bool)
+    x = np.zeros(n)
+    backup, best = 3, n + 1
+    for _ in range(max_iter):
+        F = np.where(passive)[0]
+        MF = M[:, F]
+        K = sp.bmat([[sp.identity(m), MF], [MF.T, None]], format="csc")
+        lu = splu(K)
+        rhs = np.r_[b, np.zeros(len(F))]
+        sol = lu.solve(rhs)
+        sol += lu.solve(rhs - K @ sol)                                # one step of iterative refinement
+        r, xF = sol[:m], sol[m:]                                      # r = b - M_F x_F
+        x = np.zeros(n); x[F] = xF
+        grad = -(M.T @ r)                                             # of 1/2 |M x - b|^2
+        xs, gs = np.abs(xF).max() if len(F) else 1.0, np.abs(M.T @ b).max()
+        bad_x = passive & bound & (x < -1e-13 * xs)
+        bad_g = ~passive & (grad < -1e-11 * gs)
+        nbad = int(bad_x.sum() + bad_g.sum())
+        if nbad == 0:
+            break
+        if nbad < best:
+            best, backup = nbad, 3
+        elif backup > 0:
+            backup -= 1
+        else:                                                         # the backup rule: move one index only
+            last = np.where(bad_x | bad_g)[0].max()
+            bad_x, bad_g = bad_x & (np.arange(n) == last), bad_g & (np.arange(n) == last)
+        passive = (passive & ~bad_x) | bad_g
+    return x
+
+
+def certify(gf, Jc, c, Jd, d, w_stat=1.0, w_compl=1.0, scipy_bvls=False):
+    """gf [n]; Jc [me,n], c [me]; Jd [mi,n], d [mi] (rows d(w) <= 0; two-sided bounds as two rows, infinite ones dropped).
+    Dense or scipy.sparse Jacobians.  ANY z >= 0 gives true figures for its own multipliers: the least-squares solve only
+    looks for the best ones, so a solve that stops short can reject a good point but cannot accept a bad one.  The solver
+    is bounded_lsq_sparse above; scipy_bvls=True hands the same problem to scipy.optimize.lsq_linear (dense BVLS) instead.
+    w_stat, w_compl: weights of the two blocks in the least-squares problem, for callers whose bounds on the two differ by
+    orders of magnitude (each block is then measured in units of its own bound); the figures returned are unweighted."""
+    gf = np.asarray(gf, dtype=np.float64)
+    n = len(gf)
+    c = np.asarray(c, dtype=np.float64).reshape(-1); d = np.asarray(d, dtype=np.float64).reshape(-1)
+    me, mi = len(c), len(d)
+    Jc = sp.csr_matrix(Jc) if me else sp.csr_matrix((0, n))
+    Jd = sp.csr_matrix(Jd) if mi else sp.csr_matrix((0, n))
+    assert Jc.shape == (me, n) and Jd.shape == (mi, n)
+    M = sp.bmat([[w_stat * Jc.T, w_stat * Jd.T], [sp.csr_matrix((mi, me)), sp.diags(-d * w_compl)]], format="csc")
+    rhs = np.r_[-gf * w_stat, np.zeros(mi)]
+    # unit columns (a positive scaling of each multiplier: the bounds and the minimiser are unchanged, the solve is quicker)
+    cn = np.sqrt(np.asarray(M.multiply(M).sum(axis=0)).ravel())
+    cn[cn == 0.0] = 1.0
+    Ms = (M @ sp.diags(1.0 / cn)).tocsc()
+    if scipy_bvls:
+        lb = np.r_[np.full(me, -np.inf), np.zeros(mi)]
+        res = lsq_linear(Ms.toarray(), rhs, bounds=(lb, np.inf), method="bvls", tol=1e-14, max_iter=10 * (me + mi))
+        xs = res.x
+    else:
+        xs = bounded_lsq_sparse(Ms, rhs, me)
+    x = xs / cn
+    y, z = x[:me], np.maximum(x[me:], 0.0)
+    r_stat = gf + Jc.T @ y + Jd.T @ z
+    r_compl = -d * z
+    mult = np.r_[np.abs(y), np.abs(z)]
+    return Certificate(stat=float(np.abs(r_stat).max()), compl=float(np.abs(r_compl).max()) if mi else 0.0,
+                       viol=float(max(np.abs(c).max() if me else 0.0, max(d.max(), 0.0) if mi else 0.0)), y=y, z=z,
+                       s_d=max(100.0, mult.mean() if len(mult) else 0.0) / 100.0,
+                       s_c=max(100.0, np.abs(z).mean() if mi else 0.0) / 100.0, r_stat=r_stat, r_compl=r_compl)
+
+
+# ---------------------------------------------------------------------------------------------------------- the QPs
+QP_STAT_REL, QP_COMPL_REL, QP_VIOL = 1e-6, 1e-8, 1e-9
+
+
+def qp_rows(P, q, A, lo, hi, a):
+    """min 1/2 a'Pa + q'a, lo <= A a <= hi  ->  the certificate's inputs at a."""
+    a = np.asarray(a, dtype=np.float64).reshape(-1)
+    Aa = A @ a
+    return dict(gf=P @ a + q, Jc=np.zeros((0, len(a))), c=np.zeros(0), Jd=np.vstack([A, -A]), d=np.r_[Aa - hi, lo - Aa])
+
+
+def certify_qp(P, q, A, lo, hi, a):
+    """-> certificate, (stat bound, compl bound, viol bound).  The bounds are the project's own rules: stationarity
+    1e-6 |q|_inf (tests/test_global_qp.py: test_twin_solves_the_qp_kkt), complementarity 1e-8 max(1, |z|_inf) (the kernels
+    leave at a mean complementarity below 1e-10), 1e-9 m.  The two blocks enter the least-squares problem in units of
+    these bounds (with |z|_inf taken as 1, which it is not known before)."""
+    qinf = float(np.abs(q).max())
+    cert = certify(**qp_rows(P, q, A, lo, hi, a), w_stat=1.0 / (QP_STAT_REL * qinf), w_compl=1.0 / QP_COMPL_REL)
+    return cert, (QP_STAT_REL * qinf, QP_COMPL_REL * max(1.0, float(cert.z.max())), QP_VIOL)
+
+
+# --------------------------------------------------------------------------------------------------------- the NLPs
+def node_colours(N):
+    """Colour classes of the ring of N nodes in which no two neighbours share a colour."""
+    col = np.arange(N) % 2
+    if N % 2:
+        col[N - 1] = 2
+    return [np.where(col == k)[0] for k in range(col.max() + 1)]
+
+
+class PairNLP:
+    """An NLP on a ring of N nodes with nv scaled unknowns each, whose rows come in pairs (node j, node j+1).
+    Subclasses give rows(W) for a stack W [M,N,nv] -> (c [M,N,me], d [M,N,mi]) and cost_gradient(w) [N,nv]."""
+    nv = 0
+    h = 1e-4
+
+    def rows(self, W):
+        raise NotImplementedError
+
+    def cost_gradient(self, w):
+        raise NotImplementedError
+
+    def jacobian_blocks(self, w, h=None):
+        """Jo, Jn [N, me+mi, nv]: derivatives of pair j's rows by the unknowns of node j and of node j+1; Eo, En: their own
+        error, entry by entry (the difference to the same formula on the tighter steps h / 2 and h)."""
+        h = self.h if h is None else h
+        N, nv = w.shape
+        cols = node_colours(N)
+        W = np.repeat(w[None], len(cols) * nv * 6, axis=0).reshape(len(cols), nv, 6, N, nv)
+        steps = np.array([h, -h, 2 * h, -2 * h, h / 2, -h / 2])
+        for ci, nodes in enumerate(cols):
+            for k in range(nv):
+                W[ci, k, :, nodes, k] += steps[None, :]
+        c, d = self.rows(W.reshape(-1, N, nv))
+        f = np.concatenate([c, d], axis=2).reshape(len(cols), nv, 6, N, -1)
+        d1 = (f[:, :, 0] - f[:, :, 1]) / (2 * h)
+        d2 = (f[:, :, 2] - f[:, :, 3]) / (4 * h)
+        dh = (f[:, :, 4] - f[:, :, 5]) / h
+        fd = (4.0 * d1 - d2) / 3.0                                   # [colour, k, N, rows]
+        fine = (4.0 * dh - d1) / 3.0                                 # the same formula on the tighter steps h / 2 and h
+        m = f.shape[-1]
+        err = np.abs(fd - fine)
+        Jo = np.zeros((N, m, nv)); Jn = np.zeros((N, m, nv)); Eo = np.zeros((N, m, nv)); En = np.zeros((N, m, nv))
+        for ci, nodes in enumerate(cols):
+            prev = (nodes - 1) % N
+            for src, own, nxt in ((fd, Jo, Jn), (err, Eo, En)):
+                own[nodes] = np.transpose(src[ci][:, nodes], (1, 2, 0))
+                nxt[prev] = np.transpose(src[ci][:, prev], (1, 2, 0))
+        return Jo, Jn, Eo, En
+
+    @staticmethod
+    def assemble(Jo, Jn):
+        """Blocks [N, r, nv] (own / next node) -> sparse [N r, N nv]."""
+        N, r, nv = Jo.shape
+        ri = np.broadcast_to(np.arange(N)[:, None, None] * r + np.arange(r)[None, :, None], (N, r, nv)).ravel()
+        co = np.broadcast_to(np.arange(N)[:, None, None] * nv + np.arange(nv)[None, None, :], (N, r, nv)).ravel()
+        cn = np.broadcast_to(((np.arange(N) + 1) % N)[:, None, None] * nv + np.arange(nv)[None, None, :], (N, r, nv)).ravel()
+        return (sp.coo_matrix((Jo.ravel(), (ri, co)), shape=(N * r, N * nv)) +
+                sp.coo_matrix((Jn.ravel(), (ri, cn)), shape=(N * r, N * nv))).tocsr()
+
+    def certificate_inputs(self, w, h=None):
+        """gf, Jc, c, Jd, d at w [N,nv] (rows with an infinite bound never enter: rows() leaves them out), and the
+        Jacobians' own error (Ec, Ed), entry by entry."""
+        c, d = self.rows(w[None])
+        me = c.shape[2]
+        Jo, Jn, Eo, En = self.jacobian_blocks(w, h)
+        return dict(gf=self.cost_gradient(w).ravel(), Jc=self.assemble(Jo[:, :me], Jn[:, :me]), c=c[0].ravel(),
+                    Jd=self.assemble(Jo[:, me:], Jn[:, me:]), d=d[0].ravel()), \
+            (self.assemble(Eo[:, :me], En[:, :me]), self.assemble(Eo[:, me:], En[:, me:]))
+
+
+class BicycleNLP(PairNLP):
+    """set_up_bicycle_problem (min_time_optm/min_time_optimizer.py:14-90) on the host mirrors.  Unknowns per node, scaled
+    like the reference: w = (X[5], U[2], T), x = X * SX + (P0, 0, 0, 0), u = U * SU.  Rows per pair: RK4 defect (5) and
+    longitudinal Frenet offset (1) = 0; lateral offset between dr and dl, traction circle, the model's finite state / control
+    bounds in the scaled unknowns, T >= 0."""
+    nv = 8
+    SX = np.array([10.0, 10.0, 3.14, 0.1, 80.0])
+    SU = np.array([20.0, 1.0])
+
+    def __init__(self, model, P0, yaw, dl, dr):
+        from spline_trajectory_optimization_amd.models import dynamic_bicycle as dyn
+        self.model, self.P0, self.yaw, self.dl, self.dr = model, np.asarray(P0), np.asarray(yaw), np.asarray(dl), np.asarray(dr)
+        self.N = len(self.yaw)
+        s = np.r_[self.SX, self.SU]
+        self.lo = np.r_[dyn.x_l(model)[0], dyn.u_l(model)[0]] / s
+        self.hi = np.r_[dyn.x_u(model)[0], dyn.u_u(model)[0]] / s
+
+    def to_w(self, X, U, T):
+        w = np.zeros((self.N, 8))
+        w[:, 0:2] = (X[:, 0:2] - self.P0) / self.SX[0:2]
+        w[:, 2:5] = X[:, 2:5] / self.SX[2:5]
+        w[:, 5:7] = U / self.SU; w[:, 7] = T
+        return w
+
+    def rows(self, W):
+        from spline_trajectory_optimization_amd.models import dynamic_bicycle as dyn
+        from spline_trajectory_optimization_amd.utils import integrator, utils
+        M, N, _ = W.shape
+        X = W[:, :, 0:5] * self.SX
+        X[:, :, 0:2] += self.P0[None]
+        U = W[:, :, 5:7] * self.SU
+        T = W[:, :, 7]
+        Xn = np.roll(X, -1, axis=1)
+        c = np.empty((M, N, 6))
+        c[:, :, :5] = integrator.rk4(self.model, dyn.dynamics, X.reshape(-1, 5), Xn.reshape(-1, 5), U.reshape(-1, 2),
+                                     T.reshape(-1)).reshape(M, N, 5)
+        rel = (X[:, :, :2] - self.P0[None]).reshape(-1, 2)
+        pf = utils.global_to_frenet(rel.T, np.zeros((2, 1)), np.tile(self.yaw, M))
+        c[:, :, 5] = pf[0].reshape(M, N)
+        lat = pf[1].reshape(M, N)
+        xf, uf = X.reshape(-1, 5).T, U.reshape(-1, 2).T
+        acc = (dyn.lat_acc(self.model, xf, uf) ** 2 + dyn.lon_acc(self.model, xf, uf) ** 2).reshape(M, N)
+        d = [lat - self.dl[None], self.dr[None] - lat, acc - self.model["acc_max"] ** 2]
+        for k in range(7):
+            if np.isfinite(self.hi[k]):
+                d.append(W[:, :, k] - self.hi[k])
+            if np.isfinite(self.lo[k]):
+                d.append(self.lo[k] - W[:, :, k])
+        d.append(-T)
+        return c, np.stack(d, axis=2)
+
+    def cost_gradient(self, w):
+        g = np.zeros_like(w)
+        g[:, 7] = 1.0
+        return g
+
+
+class DoubleTrackNLP(PairNLP):
+    """The double-track min-time NLP (min_time_optimizer.py:93-163) on oracle/dt_checker.py.  Unknowns per node, scaled like
+    the reference (:109-113): (n, xi, omega, beta, v) / scale_x[1:], (F, delta, gamma) / scale_u[0, 2, 3], t; the abscissa is
+    pinned to the node (:130) and u[1] enters the cost alone, which holds it at 0.  Rows: the checker's 7 equalities and 14
+    inequalities, each in the reference's own scaling (as tests/test_mintime.py scales them), and t >= 0."""
+    nv = 9
+    XCOL, UCOL = [1, 2, 3, 4, 5], [0, 2, 3]
+
+    def __init__(self, model, s, kappa, left, right, track_length, average_track_width, speed_cap):
+        self.m = dict(model)
+        m = self.m
+        self.s, self.kappa, self.left, self.right = (np.asarray(a, dtype=np.float64) for a in (s, kappa, left, right))
+        self.L, self.N = float(track_length), len(self.s)
+        self.margin = m["vehicle_width"] / 2.0 + m["safety_margin"]
+        self.scale_x = np.array([1.0, average_track_width, 1.0, 1.0, 0.5, speed_cap])
+        self.scale_u = np.array([m["Fd_max"], abs(m["Fb_max"]), m["delta_max"], m["mass"] * 50.0])
+        sx, su = self.scale_x, self.scale_u
+        self.sw = np.r_[sx[self.XCOL], su[self.UCOL], 1.0]
+        self.es = np.r_[sx, su[3]]
+        self.gs = np.array([1, 1, 1, 1, m["Pmax"], sx[5], su[0], su[0], su[2], su[2], su[0], su[2], sx[1], sx[1]])
+
+    def to_w(self, X, U, T):
+        w = np.zeros((self.N, 9))
+        w[:, :5] = X[:, self.XCOL]; w[:, 5:8] = U[:, self.UCOL]; w[:, 8] = T
+        return w / self.sw
+
+    def unpack(self, W):
+        ph = W * self.sw
+        X = np.zeros(W.shape[:-1] + (6,)); U = np.zeros(W.shape[:-1] + (4,))
+        X[..., 0] = self.s
+        X[..., self.XCOL] = ph[..., :5]
+        U[..., self.UCOL] = ph[..., 5:8]
+        return X, U, ph[..., 8]
+
+    def rows(self, W):
+        from oracle import dt_checker as dc
+        X, U, T = self.unpack(W)
+        eq, g, _ = dc.eval_nodes(self.m, self.s, self.kappa, self.left, self.right, self.margin, self.L, X, U, T)
+        return eq[:, :, :7] / self.es, np.concatenate([g / self.gs, -T[:, :, None]], axis=2)
+
+    def cost(self, w):
+        from oracle import dt_checker as dc
+        X, U, T = self.unpack(w[None])
+        return float(dc.eval_nodes(self.m, self.s, self.kappa, self.left, self.right, self.margin, self.L, X, U, T)[2][0])
+
+    def cost_gradient(self, w):
+        """Of sum T + 1e-4 sum |u|^2 + 1e-1 sum |u_next - u|^2 in the scaled controls (:119-123): the cost is quadratic, so
+        tests hold this against a central difference of the checker's cost along a random direction, which is exact."""
+        us = w[:, 5:8]
+        g = np.zeros_like(w)
+        g[:, 8] = 1.0
+        g[:, 5:8] = 2e-4 * us + 2e-1 * (2 * us - np.roll(us, -1, axis=0) - np.roll(us, 1, axis=0))
+        return g
+
+
+def fd_error_in_stationarity(err, cert):
+    """What the Jacobians' own error can put into one stationarity row: max over the unknowns of |Ec|' |y| + |Ed|' |z|
+    (the finite-difference error times the multipliers, entry by entry rather than norm by norm)."""
+    Ec, Ed = err
+    return float((Ec.T @ np.abs(cert.y) + Ed.T @ np.abs(cert.z)).max())
+
+
+def worst_block(nlp, cert):
+    """(node, unknown, value) of the largest stationarity entry."""
+    r = cert.r_stat.reshape(nlp.N, nlp.nv)
+    j, k = np.unravel_index(np.abs(r).argmax(), r.shape)
+    return int(j), int(k), float(r[j, k])

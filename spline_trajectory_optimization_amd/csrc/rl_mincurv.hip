@@ -3,18 +3,14 @@
 //
 // There is deliberately no CPU path in this library: every entry point launches HIP kernels and
 // fails with RL_ERR_HIP when no device is usable.
-#include "../../include/rl_mincurv.h"
-
-#include <hip/hip_runtime.h>
+#include "rl_host.hpp"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
-#include <string>
-#include <vector>
+#include <type_traits>
 
 #include "rl_kernels.hpp"
 #include "rl_sweep.hpp"
@@ -29,210 +25,9 @@
 #include "rl_tables.hpp"
 
 namespace {
-
-thread_local std::string g_err;
 double* g_dbg_buf = nullptr;   // rl_debug_dump_enable: step / window dump of the sweep kernels (tests)
 size_t g_dbg_len = 0;
 int g_dbg_instances = 0;
-
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-
-#define RL_HIP(expr)                                                                      \
-  do {                                                                                    \
-    hipError_t _e = (expr);                                                               \
-    if (_e != hipSuccess) {                                                               \
-      return fail(RL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));         \
-    }                                                                                     \
-  } while (0)
-
-template <typename T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  hipError_t alloc(size_t count) {
-    release();
-    n = count;
-    if (count == 0) return hipSuccess;
-    return hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T));
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-  ~DevBuf() { release(); }
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-};
-
-}  // namespace
-
-struct rl_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  int max_lds = 65536;
-  int num_cu = 0;
-  bool force_global_v1 = false;  // test hook: RL_GLOBAL_V1=1 keeps the generic kernel
-  int arith = RL_ARITH_REFERENCE;   // rl_ctx_set_arith: arithmetic of the sweep; the reference-order arithmetic since round 6
-  bool arith_explicit = false;      // set by rl_ctx_set_arith / RL_ARITH: an explicit choice fails where it does not exist, the default follows
-  int np_raise_at_start = 0;     // rl_ctx_set_numpy_raise: the reference-order sweep starts with np.seterr(all='raise') in effect
-  // test hooks of the QSS simulator (rl_ctx_set_option; defaults from RL_QSS_DF / RL_QSS_V1 / RL_QSS_DF_WAVES / RL_QSS_DF_BAIL_AT, read
-  // once in rl_ctx_create): which kernel (-1 = by the rounds the batch takes, 0 = list order, 1 = dataflow), waves per instance of
-  // the dataflow kernel, the iteration at which it hands every instance back (0 = never)
-  int qss_kernel = -1, qss_df_waves = 4, qss_df_bail_at = 0;
-  // test hooks of rl_tables_batch_*: ring search (RL_SEARCH_*), 1 = ring vertices in the arena even where they fit LDS
-  int tables_search = RL_SEARCH_WINDOWED, tables_rings_global = 0;
-  // largest dynamic-LDS size already granted per kernel (hipFuncSetAttribute is issued only when a call needs more)
-  // Device scratch owned by the context (grow-only): the *_dev entry points of the QSS simulator and the
-  // min-time solve carve their work arrays out of it, so that steady-state calls allocate nothing.
-  void* arena = nullptr;
-  size_t arena_cap = 0;
-  // The arena is handed out from offset 0 by every *_dev call, so two calls may only overlap in time if they are
-  // ordered on the device: each call records `arena_ev` behind its last use, and a call made after
-  // rl_ctx_set_stream switched to another stream first makes that stream wait for the event (Arena::begin).
-  hipEvent_t arena_ev = nullptr;
-  hipStream_t arena_stream = nullptr;
-  bool arena_busy = false;       // arena_ev has been recorded at least once
-  // second in-order queue of the min-time solve (half batches side by side), forked from / joined into `stream`
-  static constexpr int kMaxGroups = 8;
-  hipStream_t aux_stream[kMaxGroups - 1] = {};
-  hipEvent_t ev_fork = nullptr, ev_join[kMaxGroups - 1] = {};
-  bool mt_poll = false;          // set by the HOST entry point of the min-time solve around its call of the _dev one: poll for early exit
-  // the poll never drains the queues: the status words of a chunk of 8 iterations are copied by a side stream into pinned
-  // memory while the next chunk is already enqueued, and looked at one chunk later
-  hipStream_t poll_stream = nullptr;
-  hipEvent_t ev_chunk[kMaxGroups] = {}, ev_poll[2] = {nullptr, nullptr};
-  double* poll_host = nullptr;   // pinned, 2 x poll_cap doubles
-  size_t poll_cap = 0;
-  bool mt_hes_sweep = false;     // RL_MT_HES_SWEEP=1: the Hessian by k_mt_derivs<2> instead of the chain-rule kernels
-  bool mt_kkt4 = true;           // RL_MT_KKT4=0: the elimination with two fronts per instance (k_mt_kkt) instead of four (k_mt_kkt4, N >= 64)
-  bool mt_unfused = false;       // RL_MT_UNFUSED=1: Jacobian / Hessian / block assembly by the four separate kernels instead of k_mt_node
-  int mt_groups = 3;             // RL_MT_GROUPS=1..8 (round 3, 1024 instances: 1 / 2 / 3 / 4 / 8 streams 1.23 / 1.29 / 1.21 / 1.19 / 1.19 s)
-  // Device staging blocks of the HOST-pointer entry points (PoolBuf): handed out best-fit, returned at the end of
-  // the call, freed with the context -- a second call of the same shape allocates nothing.
-  struct PoolBlock { void* p; size_t cap; bool used; };
-  std::vector<PoolBlock> pool;
-};
-
-namespace {
-// hipFuncAttributeMaxDynamicSharedMemorySize is a property of the FUNCTION on a device, shared by every context of the
-// process: one process-wide table per (device, kernel) that only ever raises the value, instead of one call per launch
-// (a per-context cache would go stale as soon as a second context asked for less).
-hipError_t grant_dyn_lds(rl_ctx* ctx, const void* fn, size_t bytes) {
-  static std::mutex mu;
-  static std::vector<std::pair<std::pair<int, const void*>, size_t>> granted;
-  std::lock_guard<std::mutex> lock(mu);
-  const std::pair<int, const void*> key(ctx->device, fn);
-  for (auto& e : granted)
-    if (e.first == key) {
-      if (e.second >= bytes) return hipSuccess;
-      const hipError_t r = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-      if (r == hipSuccess) e.second = bytes;
-      return r;
-    }
-  const hipError_t r = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (r == hipSuccess) granted.emplace_back(key, bytes);
-  return r;
-}
-// per-call device staging of the host-pointer entry points, from the context's pool (every such entry point ends
-// with a stream synchronisation, so a block is idle when it is returned)
-template <typename T>
-struct PoolBuf {
-  rl_ctx* ctx;
-  T* p = nullptr;
-  size_t n = 0;
-  int slot = -1;
-  explicit PoolBuf(rl_ctx* c) : ctx(c) {}
-  hipError_t alloc(size_t count) {
-    release();
-    n = count;
-    if (count == 0) return hipSuccess;
-    const size_t bytes = (count * sizeof(T) + 255) & ~(size_t)255;
-    int best = -1;
-    for (int i = 0; i < (int)ctx->pool.size(); ++i)
-      if (!ctx->pool[i].used && ctx->pool[i].cap >= bytes && ctx->pool[i].cap <= 4 * bytes + 4096 &&   // never park a small request on a huge block
-          (best < 0 || ctx->pool[i].cap < ctx->pool[best].cap)) best = i;
-    if (best < 0) {
-      if (ctx->pool.size() >= 96) {   // shapes keep changing: drop what is idle before growing further
-        for (auto& blk : ctx->pool)
-          if (!blk.used && blk.p) { (void)hipFree(blk.p); blk.p = nullptr; blk.cap = 0; }
-      }
-      void* q = nullptr;
-      hipError_t e = hipMalloc(&q, bytes);
-      if (e != hipSuccess) {          // out of memory: give back what is idle, then try once more
-        (void)hipGetLastError();
-        for (auto& blk : ctx->pool)
-          if (!blk.used && blk.p) { (void)hipFree(blk.p); blk.p = nullptr; blk.cap = 0; }
-        e = hipMalloc(&q, bytes);
-      }
-      if (e != hipSuccess) return e;
-      for (int i = 0; i < (int)ctx->pool.size() && best < 0; ++i)
-        if (!ctx->pool[i].p) { ctx->pool[i] = {q, bytes, false}; best = i; }
-      if (best < 0) { ctx->pool.push_back({q, bytes, false}); best = (int)ctx->pool.size() - 1; }
-    }
-    ctx->pool[best].used = true;
-    slot = best;
-    p = static_cast<T*>(ctx->pool[best].p);
-    return hipSuccess;
-  }
-  void release() {
-    if (slot >= 0) ctx->pool[slot].used = false;
-    slot = -1; p = nullptr; n = 0;
-  }
-  // Success paths end with a stream synchronisation, so the block is idle here.  An early error return does not: wait for
-  // whatever was already enqueued (copies into / out of this block) before the block can be handed to the next call.
-  ~PoolBuf() {
-    if (slot >= 0 && hipStreamQuery(ctx->stream) == hipErrorNotReady) (void)hipStreamSynchronize(ctx->stream);
-    release();
-  }
-  PoolBuf(const PoolBuf&) = delete;
-  PoolBuf& operator=(const PoolBuf&) = delete;
-};
-
-// sequential carve-out of the context's scratch arena; reserve() first with the total
-struct Arena {
-  rl_ctx* ctx; size_t off = 0;
-  explicit Arena(rl_ctx* c) : ctx(c) {}
-  static size_t pad(size_t b) { return (b + 255) & ~(size_t)255; }
-  // order this call behind the previous user of the arena if that one ran on another stream
-  hipError_t begin() {
-    if (!ctx->arena_ev) {
-      const hipError_t e = hipEventCreateWithFlags(&ctx->arena_ev, hipEventDisableTiming);
-      if (e != hipSuccess) return e;
-    }
-    if (ctx->arena_busy && ctx->arena_stream != ctx->stream) return hipStreamWaitEvent(ctx->stream, ctx->arena_ev, 0);
-    return hipSuccess;
-  }
-  // record "the arena is free again once everything enqueued so far on the context's stream has run"
-  hipError_t end() {
-    const hipError_t e = hipEventRecord(ctx->arena_ev, ctx->stream);
-    if (e == hipSuccess) { ctx->arena_busy = true; ctx->arena_stream = ctx->stream; }
-    return e;
-  }
-  hipError_t reserve(size_t bytes) {
-    hipError_t e = begin();
-    if (e != hipSuccess) return e;
-    if (bytes <= ctx->arena_cap) return hipSuccess;
-    if (ctx->arena_busy) { e = hipEventSynchronize(ctx->arena_ev); if (e != hipSuccess) return e; }   // the last user, whatever its stream
-    e = hipStreamSynchronize(ctx->stream);                     // nothing in flight may still use the old block
-    if (e != hipSuccess) return e;
-    if (ctx->arena) (void)hipFree(ctx->arena);
-    ctx->arena = nullptr; ctx->arena_cap = 0;
-    e = hipMalloc(&ctx->arena, bytes);
-    if (e == hipSuccess) ctx->arena_cap = bytes;
-    return e;
-  }
-  template <typename T> T* take(size_t count) {
-    T* p = reinterpret_cast<T*>(static_cast<char*>(ctx->arena) + off);
-    off += pad(count * sizeof(T));
-    return p;
-  }
-};
 }  // namespace
 
 struct rl_track {
@@ -277,12 +72,26 @@ namespace {
 
 bool degree_supported(int k) { return k == 3 || k == 5; }
 
-// dispatch a callable templated on the spline degree
-template <typename F3, typename F5>
-int by_degree(int k, F3&& f3, F5&& f5) {
-  if (k == 3) return f3();
-  if (k == 5) return f5();
+// dispatch on the spline degree: f(std::integral_constant<int, K>) for K = 3 or 5 (a generic lambda; RL_DEGREE names its K)
+template <typename F>
+int by_degree(int k, F&& f) {
+  if (k == 3) return f(std::integral_constant<int, 3>{});
+  if (k == 5) return f(std::integral_constant<int, 5>{});
   return fail(RL_ERR_UNSUPPORTED, "spline degree must be 3 or 5");
+}
+#define RL_DEGREE(kc) (std::decay_t<decltype(kc)>::value)
+
+// Samples [s0, s1) under control points j .. j + span - 1, with the reference's own mask (u >= t[j]) & (u < t[j+span+k]),
+// u_i = i * (1/N).  The two loops ARE the mask: the indices are part of the bit-exact contract.
+struct SupportRange { int s0, s1; };
+SupportRange support_range(const std::vector<double>& t_host, int k, int N, int j, int span = 1) {
+  const double step = 1.0 / (double)N;
+  const double ts = t_host[j], te = t_host[j + span + k];
+  int a = 0;
+  while (a < N && !((double)a * step >= ts)) ++a;
+  int b = a;
+  while (b < N && (double)b * step < te) ++b;
+  return {a, b};
 }
 
 int check_spline(const double* t, int nt, const double* cx, const double* cy, int k) {
@@ -331,31 +140,25 @@ SweepPlan plan_sweep(const rl_ctx* ctx, int n, int N, int nL, int nR, int B, boo
   return p;
 }
 
-template <class Cfg>
-int launch_sweep_t(const rl_ctx* ctx, const rl::SweepArgs& a, size_t lds) {
-  auto kern = rl::k_sweep<Cfg>;
-  RL_HIP(grant_dyn_lds(const_cast<rl_ctx*>(ctx), reinterpret_cast<const void*>(kern), lds));
-  hipLaunchKernelGGL(kern, dim3(a.B), dim3(rl::kSweepThreads), lds, ctx->stream, a);
-  RL_HIP(hipGetLastError());
-  return RL_OK;
-}
-
 // One instantiation in the residency the plan chose (all-LDS or all-global; the third residency has a line of its own below).
 constexpr bool kRecordSteps = true;   // the DUMP instantiation
 template <int K, rl::Driver DRIVER, rl::Arith ARITH, bool DUMP = false>
 int launch_sweep_in(const rl_ctx* ctx, const SweepPlan& p, const rl::SweepArgs& a) {
-  return p.residency == rl::Residency::Lds
-             ? launch_sweep_t<rl::SweepConfig<K, rl::Residency::Lds, DRIVER, ARITH, DUMP>>(ctx, a, p.lds_bytes)
-             : launch_sweep_t<rl::SweepConfig<K, rl::Residency::Global, DRIVER, ARITH, DUMP>>(ctx, a, p.lds_bytes);
+  using rl::Residency; using rl::SweepConfig;
+  const dim3 grid(a.B), block(rl::kSweepThreads);
+  return p.residency == Residency::Lds
+             ? launch(ctx, rl::k_sweep<SweepConfig<K, Residency::Lds, DRIVER, ARITH, DUMP>>, grid, block, p.lds_bytes, a)
+             : launch(ctx, rl::k_sweep<SweepConfig<K, Residency::Global, DRIVER, ARITH, DUMP>>, grid, block, p.lds_bytes, a);
 }
 
 int launch_sweep(const rl_ctx* ctx, int k, const SweepPlan& p, const rl::SweepArgs& a, bool joint = false, bool strict = false,
                  bool lite = false) {
-  using rl::Arith; using rl::Driver; using rl::Residency;
+  using rl::Arith; using rl::Driver; using rl::Residency; using rl::SweepConfig;
+  const dim3 grid(a.B), block(rl::kSweepThreads);
   if (strict) {   // RL_ARITH_REFERENCE / _BRANCH: degree-5 splines (the reference's wrap is written for k = 5, optimizer.py:281-285)
 #ifdef RL_STAMPS
     if (k == 5 && !joint && !lite && p.residency == Residency::Global)   // diagnostic build: the plain reference-order kernel with its phase stamps in a.dbg
-      return launch_sweep_t<rl::SweepConfig<5, Residency::Global, Driver::Sweep, Arith::Reference>>(ctx, a, p.lds_bytes);
+      return launch(ctx, rl::k_sweep<SweepConfig<5, Residency::Global, Driver::Sweep, Arith::Reference>>, grid, block, p.lds_bytes, a);
 #endif
     if (k != 5 || a.dbg || (joint && lite)) return fail(RL_ERR_UNSUPPORTED, "reference-order / branch arithmetic: degree-5 splines, no step dump; the sliding-window driver in the reference-order arithmetic only");
     if (joint)    // run_joint_min_curvature_qp in the reference-order arithmetic
@@ -372,9 +175,9 @@ int launch_sweep(const rl_ctx* ctx, int k, const SweepPlan& p, const rl::SweepAr
     return launch_sweep_in<5, Driver::Window, Arith::Fast>(ctx, p, a);
   }
   if (k == 5 && p.residency == Residency::CrossingsLds)
-    return launch_sweep_t<rl::SweepConfig<5, Residency::CrossingsLds>>(ctx, a, p.lds_bytes);
+    return launch(ctx, rl::k_sweep<SweepConfig<5, Residency::CrossingsLds>>, grid, block, p.lds_bytes, a);
 #ifdef RL_STAMPS
-  if (k == 5 && p.residency == Residency::Global) return launch_sweep_t<rl::SweepConfig<5, Residency::Global>>(ctx, a, p.lds_bytes);  // stamps go to a.dbg
+  if (k == 5 && p.residency == Residency::Global) return launch(ctx, rl::k_sweep<SweepConfig<5, Residency::Global>>, grid, block, p.lds_bytes, a);  // stamps go to a.dbg
 #endif
   if (k == 5) {
     if (a.dbg)  // recording instantiation (test aid): same source, one extra store block per step
@@ -392,16 +195,50 @@ int ensure_strict_tables(const rl_ctx* ctx, const rl_track* trk) {
   if (k != 5) return fail(RL_ERR_UNSUPPORTED, "reference-order arithmetic: degree-5 splines");
   if (!trk->Ds.p) RL_HIP(trk->Ds.alloc((size_t)rl::StrictRows<5>::total * N));
   if (!trk->base_s.p) RL_HIP(trk->base_s.alloc((size_t)6 * N));
-  const dim3 grid((N + 127) / 128), block(128);
-  hipLaunchKernelGGL(rl::k_build_tables_strict<5>, grid, block, 0, ctx->stream, trk->t.p, trk->nt, trk->c0.p, N,
-                     trk->Ds.p, trk->base_s.p);
-  RL_HIP(hipGetLastError());
+  if (int rc = launch(ctx, rl::k_build_tables_strict<5>, dim3((N + 127) / 128), dim3(128), 0, trk->t.p, trk->nt, trk->c0.p, N,
+                      trk->Ds.p, trk->base_s.p))
+    return rc;
   // like the other table builders: complete (and known to have succeeded) before the tables count as valid -- a later call
   // may arrive on another stream (rl_ctx_set_stream), with no event ordering it behind this launch
   RL_HIP(hipStreamSynchronize(ctx->stream));
   trk->strict_valid = true;
   return RL_OK;
 }
+
+// the track's de Boor tables from its knots and control points (rl_kernels.hpp: k_build_tables), complete on return
+int build_tables(const rl_ctx* ctx, const rl_track* trk) {
+  const int N = trk->N;
+  if (int rc = by_degree(trk->k, [&](auto kc) {
+        return launch(ctx, rl::k_build_tables<RL_DEGREE(kc)>, dim3((N + 127) / 128), dim3(128), 0, trk->t.p, trk->nt, trk->c0.p, N,
+                      trk->ell.p, trk->D.p, trk->base.p);
+      }))
+    return rc;
+  RL_HIP(hipStreamSynchronize(ctx->stream));
+  return RL_OK;
+}
+
+// The rings an instance is bounded by: the track's shared pair, or N vertices per side that the kernel builds from the
+// per-instance input (`in`: widths or bound points).
+struct Bounds {
+  const double2 *ringL = nullptr, *ringR = nullptr;
+  int nL = 0, nR = 0;
+};
+int resolve_bounds(const rl_track* trk, int form, const double* in, Bounds& b) {
+  if (form == RL_BOUNDS_SHARED_RINGS) {
+    if (trk->nL == 0) return fail(RL_ERR_ARG, "rl_track_set_rings was not called");
+    b.ringL = reinterpret_cast<const double2*>(trk->ringL.p);
+    b.ringR = reinterpret_cast<const double2*>(trk->ringR.p);
+    b.nL = trk->nL; b.nR = trk->nR;
+  } else if (form == RL_BOUNDS_WIDTHS || form == RL_BOUNDS_POINTS) {
+    if (!in) return fail(RL_ERR_ARG, "bounds input is null");
+    b.nL = trk->N; b.nR = trk->N;
+  } else {
+    return fail(RL_ERR_ARG, "bad bounds_form");
+  }
+  return RL_OK;
+}
+// doubles per sample of the per-instance bounds input (0: the track's shared rings, or no such form)
+int bounds_cols(int form) { return form == RL_BOUNDS_WIDTHS ? 2 : (form == RL_BOUNDS_POINTS ? 4 : 0); }
 
 }  // namespace
 
@@ -525,16 +362,12 @@ int rl_ctx_set_numpy_raise(rl_ctx* ctx, int on) {
 
 int rl_debug_cr_heading(rl_ctx* ctx, const double* dx, const double* dy, int n, double* out) {
   if (!ctx || !dx || !dy || !out || n <= 0) return fail(RL_ERR_ARG, "bad argument");
-  RL_HIP(hipSetDevice(ctx->device));
-  PoolBuf<double> ddx(ctx), ddy(ctx), dout(ctx);
-  RL_HIP(ddx.alloc(n)); RL_HIP(ddy.alloc(n)); RL_HIP(dout.alloc((size_t)5 * n));
-  RL_HIP(hipMemcpyAsync(ddx.p, dx, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  RL_HIP(hipMemcpyAsync(ddy.p, dy, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(rl::k_debug_cr_heading, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ddx.p, ddy.p, n, dout.p);
-  RL_HIP(hipGetLastError());
-  RL_HIP(hipMemcpyAsync(out, dout.p, (size_t)5 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipStreamSynchronize(ctx->stream));
-  return RL_OK;
+  Staging sg(ctx);
+  const double* ddx = sg.in(dx, n);
+  const double* ddy = sg.in(dy, n);
+  double* dout = sg.out(out, (size_t)5 * n);
+  sg.run([&] { return launch(ctx, rl::k_debug_cr_heading, dim3((n + 255) / 256), dim3(256), 0, ddx, ddy, n, dout); });
+  return sg.finish();
 }
 
 int rl_ctx_synchronize(rl_ctx* ctx) {
@@ -549,25 +382,16 @@ int rl_spline_eval(rl_ctx* ctx, const double* t, int nt, const double* cx, const
   if (!ctx || !u || !out) return fail(RL_ERR_ARG, "null argument");
   if (int rc = check_spline(t, nt, cx, cy, k)) return rc;
   if (N <= 0 || der_max < 0 || der_max > 2) return fail(RL_ERR_ARG, "bad N / der_max");
-  RL_HIP(hipSetDevice(ctx->device));
   const int n = nt - k - 1;
-  PoolBuf<double> dt(ctx), dcx(ctx), dcy(ctx), du(ctx), dout(ctx);
-  RL_HIP(dt.alloc(nt)); RL_HIP(dcx.alloc(n)); RL_HIP(dcy.alloc(n)); RL_HIP(du.alloc(N));
-  RL_HIP(dout.alloc((size_t)2 * (der_max + 1) * N));
-  RL_HIP(hipMemcpyAsync(dt.p, t, nt * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  RL_HIP(hipMemcpyAsync(dcx.p, cx, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  RL_HIP(hipMemcpyAsync(dcy.p, cy, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  RL_HIP(hipMemcpyAsync(du.p, u, (size_t)N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  const dim3 grid((N + 255) / 256), block(256);
-  int rc = by_degree(
-      k,
-      [&] { hipLaunchKernelGGL(rl::k_spline_eval<3>, grid, block, 0, ctx->stream, dt.p, nt, dcx.p, dcy.p, du.p, N, der_max, dout.p); return RL_OK; },
-      [&] { hipLaunchKernelGGL(rl::k_spline_eval<5>, grid, block, 0, ctx->stream, dt.p, nt, dcx.p, dcy.p, du.p, N, der_max, dout.p); return RL_OK; });
-  if (rc) return rc;
-  RL_HIP(hipGetLastError());
-  RL_HIP(hipMemcpyAsync(out, dout.p, dout.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipStreamSynchronize(ctx->stream));
-  return RL_OK;
+  Staging sg(ctx);
+  const double *dt = sg.in(t, nt), *dcx = sg.in(cx, n), *dcy = sg.in(cy, n), *du = sg.in(u, N);
+  double* dout = sg.out(out, (size_t)2 * (der_max + 1) * N);
+  sg.run([&] {
+    return by_degree(k, [&](auto kc) {
+      return launch(ctx, rl::k_spline_eval<RL_DEGREE(kc)>, dim3((N + 255) / 256), dim3(256), 0, dt, nt, dcx, dcy, du, N, der_max, dout);
+    });
+  });
+  return sg.finish();
 }
 
 int rl_sample_along(rl_ctx* ctx, const double* t, int nt, const double* cx, const double* cy, int k,
@@ -575,46 +399,33 @@ int rl_sample_along(rl_ctx* ctx, const double* t, int nt, const double* cx, cons
   if (!ctx || !u || !points) return fail(RL_ERR_ARG, "null argument");
   if (int rc = check_spline(t, nt, cx, cy, k)) return rc;
   if (N <= 0) return fail(RL_ERR_ARG, "bad N");
-  RL_HIP(hipSetDevice(ctx->device));
   const int n = nt - k - 1;
-  PoolBuf<double> dt(ctx), dcx(ctx), dcy(ctx), du(ctx), dpts(ctx), dseg(ctx);
-  RL_HIP(dt.alloc(nt)); RL_HIP(dcx.alloc(n)); RL_HIP(dcy.alloc(n)); RL_HIP(du.alloc(N));
-  RL_HIP(dpts.alloc((size_t)N * RL_NCOL)); RL_HIP(dseg.alloc(N));
-  RL_HIP(hipMemcpyAsync(dt.p, t, nt * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  RL_HIP(hipMemcpyAsync(dcx.p, cx, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  RL_HIP(hipMemcpyAsync(dcy.p, cy, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  RL_HIP(hipMemcpyAsync(du.p, u, (size_t)N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  const dim3 grid((N + 127) / 128), block(128);
-  int rc = by_degree(
-      k,
-      [&] { hipLaunchKernelGGL(rl::k_sample_geometry<3>, grid, block, 0, ctx->stream, dt.p, nt, dcx.p, dcy.p, du.p, N, dpts.p, dseg.p); return RL_OK; },
-      [&] { hipLaunchKernelGGL(rl::k_sample_geometry<5>, grid, block, 0, ctx->stream, dt.p, nt, dcx.p, dcy.p, du.p, N, dpts.p, dseg.p); return RL_OK; });
-  if (rc) return rc;
-  RL_HIP(hipGetLastError());
-  hipLaunchKernelGGL(rl::k_sample_cumsum, dim3(1), dim3(64), 0, ctx->stream, dseg.p, N, length, dpts.p);
-  RL_HIP(hipGetLastError());
-  RL_HIP(hipMemcpyAsync(points, dpts.p, dpts.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipStreamSynchronize(ctx->stream));
-  return RL_OK;
+  Staging sg(ctx);
+  const double *dt = sg.in(t, nt), *dcx = sg.in(cx, n), *dcy = sg.in(cy, n), *du = sg.in(u, N);
+  double* dpts = sg.out(points, (size_t)N * RL_NCOL);
+  double* dseg = sg.scratch<double>(N);
+  sg.run([&] {
+    if (int rc = by_degree(k, [&](auto kc) {
+          return launch(ctx, rl::k_sample_geometry<RL_DEGREE(kc)>, dim3((N + 127) / 128), dim3(128), 0, dt, nt, dcx, dcy, du, N, dpts, dseg);
+        }))
+      return rc;
+    return launch(ctx, rl::k_sample_cumsum, dim3(1), dim3(64), 0, dseg, N, length, dpts);
+  });
+  return sg.finish();
 }
 
 int rl_fill_bounds(rl_ctx* ctx, double* points, int N, const double* ringL, int nL,
                    const double* ringR, int nR, double max_dist) {
   if (!ctx || !points || !ringL || !ringR) return fail(RL_ERR_ARG, "null argument");
   if (N <= 0 || nL < 2 || nR < 2) return fail(RL_ERR_ARG, "bad sizes");
-  RL_HIP(hipSetDevice(ctx->device));
-  PoolBuf<double> dpts(ctx), dL(ctx), dR(ctx);
-  RL_HIP(dpts.alloc((size_t)N * RL_NCOL)); RL_HIP(dL.alloc((size_t)2 * nL)); RL_HIP(dR.alloc((size_t)2 * nR));
-  RL_HIP(hipMemcpyAsync(dpts.p, points, dpts.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  RL_HIP(hipMemcpyAsync(dL.p, ringL, dL.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  RL_HIP(hipMemcpyAsync(dR.p, ringR, dR.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(rl::k_fill_bounds, dim3((2 * N + 63) / 64), dim3(64), 0, ctx->stream, dpts.p, N,
-                     reinterpret_cast<const double2*>(dL.p), nL,
-                     reinterpret_cast<const double2*>(dR.p), nR, max_dist);
-  RL_HIP(hipGetLastError());
-  RL_HIP(hipMemcpyAsync(points, dpts.p, dpts.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipStreamSynchronize(ctx->stream));
-  return RL_OK;
+  Staging sg(ctx);
+  double* dpts = sg.inout(points, (size_t)N * RL_NCOL);
+  const double *dL = sg.in(ringL, (size_t)2 * nL), *dR = sg.in(ringR, (size_t)2 * nR);
+  sg.run([&] {
+    return launch(ctx, rl::k_fill_bounds, dim3((2 * N + 63) / 64), dim3(64), 0, dpts, N, reinterpret_cast<const double2*>(dL), nL,
+                  reinterpret_cast<const double2*>(dR), nR, max_dist);
+  });
+  return sg.finish();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -630,17 +441,11 @@ int rl_track_create(rl_ctx* ctx, const double* t, int nt, const double* cx0, con
   trk->ctx = ctx;
   trk->k = k; trk->n = n; trk->nt = nt; trk->N = N;
   trk->t_host.assign(t, t + nt);
-  // support ranges with the reference's own mask: (u >= t[j]) & (u < t[j+k+1]), u_i = i * (1/N)
   std::vector<int> sup(2 * (size_t)n);
-  const double step = 1.0 / (double)N;
   for (int j = 0; j < n; ++j) {
-    const double ts = t[j], te = t[j + k + 1];
-    int a = 0;
-    while (a < N && !((double)a * step >= ts)) ++a;
-    int b = a;
-    while (b < N && (double)b * step < te) ++b;
-    sup[2 * j] = a;
-    sup[2 * j + 1] = b;
+    const SupportRange r = support_range(trk->t_host, k, N, j);
+    sup[2 * j] = r.s0;
+    sup[2 * j + 1] = r.s1;
   }
   hipError_t e = hipSuccess;
   auto ok = [&](hipError_t r) { if (e == hipSuccess) e = r; };
@@ -650,18 +455,11 @@ int rl_track_create(rl_ctx* ctx, const double* t, int nt, const double* cx0, con
   if (e == hipSuccess) ok(hipMemcpyAsync(trk->c0.p, cx0, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   if (e == hipSuccess) ok(hipMemcpyAsync(trk->c0.p + n, cy0, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   if (e == hipSuccess) ok(hipMemcpyAsync(trk->sup.p, sup.data(), sup.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-  if (e == hipSuccess) {
-    const dim3 grid((N + 127) / 128), block(128);
-    if (k == 3)
-      hipLaunchKernelGGL(rl::k_build_tables<3>, grid, block, 0, ctx->stream, trk->t.p, nt, trk->c0.p, N, trk->ell.p, trk->D.p, trk->base.p);
-    else
-      hipLaunchKernelGGL(rl::k_build_tables<5>, grid, block, 0, ctx->stream, trk->t.p, nt, trk->c0.p, N, trk->ell.p, trk->D.p, trk->base.p);
-    ok(hipGetLastError());
-    ok(hipStreamSynchronize(ctx->stream));
-  }
-  if (e != hipSuccess) {
+  const int rc = e == hipSuccess ? build_tables(ctx, trk)   // its synchronisation also covers `sup`, a host vector
+                                 : fail(RL_ERR_HIP, std::string("rl_track_create: ") + hipGetErrorString(e));
+  if (rc) {
     delete trk;
-    return fail(RL_ERR_HIP, std::string("rl_track_create: ") + hipGetErrorString(e));
+    return rc;
   }
   *out = trk;
   return RL_OK;
@@ -696,16 +494,10 @@ int rl_track_set_control_points(rl_track* trk, const double* cx0, const double* 
   if (!trk || !cx0 || !cy0) return fail(RL_ERR_ARG, "null argument");
   rl_ctx* ctx = trk->ctx;
   RL_HIP(hipSetDevice(ctx->device));
-  const int n = trk->n, N = trk->N;
+  const int n = trk->n;
   RL_HIP(hipMemcpyAsync(trk->c0.p, cx0, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   RL_HIP(hipMemcpyAsync(trk->c0.p + n, cy0, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  const dim3 grid((N + 127) / 128), block(128);
-  if (trk->k == 3)
-    hipLaunchKernelGGL(rl::k_build_tables<3>, grid, block, 0, ctx->stream, trk->t.p, trk->nt, trk->c0.p, N, trk->ell.p, trk->D.p, trk->base.p);
-  else
-    hipLaunchKernelGGL(rl::k_build_tables<5>, grid, block, 0, ctx->stream, trk->t.p, trk->nt, trk->c0.p, N, trk->ell.p, trk->D.p, trk->base.p);
-  RL_HIP(hipGetLastError());
-  RL_HIP(hipStreamSynchronize(ctx->stream));
+  if (int rc = build_tables(ctx, trk)) return rc;
   trk->gq_valid = false;
   trk->gxy_valid = false;
   trk->strict_valid = false;
@@ -719,70 +511,45 @@ int rl_mincurv_cost(rl_ctx* ctx, const rl_track* trk, const int* idx, int n_idx,
   if (n_idx <= 0) return fail(RL_ERR_ARG, "n_idx <= 0");
   for (int q = 0; q < n_idx; ++q)
     if (idx[q] < 0 || idx[q] >= trk->n) return fail(RL_ERR_ARG, "control point index out of range");
-  RL_HIP(hipSetDevice(ctx->device));
-  PoolBuf<int> didx(ctx), dM(ctx);
-  PoolBuf<double> dz(ctx), dH(ctx), dg(ctx);
-  RL_HIP(didx.alloc(n_idx)); RL_HIP(dM.alloc(n_idx));
-  RL_HIP(dH.alloc((size_t)4 * n_idx)); RL_HIP(dg.alloc((size_t)2 * n_idx));
-  RL_HIP(hipMemcpyAsync(didx.p, idx, n_idx * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-  if (z) {
-    RL_HIP(dz.alloc((size_t)2 * n_idx));
-    RL_HIP(hipMemcpyAsync(dz.p, z, (size_t)2 * n_idx * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  }
-  if (ctx->arith == RL_ARITH_REFERENCE && trk->k == 5) if (int rc = ensure_strict_tables(ctx, trk)) return rc;
-  const rl::TrackDev td = trk->dev();
-  const double* cx = trk->c0.p;
-  const double* cy = trk->c0.p + trk->n;
-  if (ctx->arith == RL_ARITH_REFERENCE && trk->k == 5)     // the oracle's bits (orc_min_curvature_cost)
-    hipLaunchKernelGGL(rl::k_cost_strict<5>, dim3(n_idx), dim3(256), 0, ctx->stream, td, cx, cy, didx.p, dz.p, dH.p, dg.p, dM.p);
-  else if (trk->k == 3)
-    hipLaunchKernelGGL(rl::k_cost<3>, dim3(n_idx), dim3(256), 0, ctx->stream, td, cx, cy, didx.p, dz.p, dH.p, dg.p, dM.p);
-  else
-    hipLaunchKernelGGL(rl::k_cost<5>, dim3(n_idx), dim3(256), 0, ctx->stream, td, cx, cy, didx.p, dz.p, dH.p, dg.p, dM.p);
-  RL_HIP(hipGetLastError());
-  RL_HIP(hipMemcpyAsync(H, dH.p, dH.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipMemcpyAsync(g, dg.p, dg.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (M) RL_HIP(hipMemcpyAsync(M, dM.p, n_idx * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipStreamSynchronize(ctx->stream));
-  return RL_OK;
+  const bool strict = ctx->arith == RL_ARITH_REFERENCE && trk->k == 5;   // the oracle's bits (orc_min_curvature_cost)
+  Staging sg(ctx);
+  const int* didx = sg.in(idx, n_idx);
+  const double* dz = sg.in(z, (size_t)2 * n_idx);
+  double *dH = sg.out(H, (size_t)4 * n_idx), *dg = sg.out(g, (size_t)2 * n_idx);
+  int* dM = sg.out_optional(M, n_idx);
+  sg.run([&] {
+    if (strict) if (int rc = ensure_strict_tables(ctx, trk)) return rc;
+    const rl::TrackDev td = trk->dev();
+    const double *cx = trk->c0.p, *cy = trk->c0.p + trk->n;
+    const dim3 grid(n_idx), block(256);
+    if (strict) return launch(ctx, rl::k_cost_strict<5>, grid, block, 0, td, cx, cy, didx, dz, dH, dg, dM);
+    return by_degree(trk->k, [&](auto kc) { return launch(ctx, rl::k_cost<RL_DEGREE(kc)>, grid, block, 0, td, cx, cy, didx, dz, dH, dg, dM); });
+  });
+  return sg.finish();
 }
 
 int rl_track_constraint(rl_ctx* ctx, const rl_track* trk, const double* points, int idx,
                         double* b, double* lba, double* uba, int* M) {
   if (!ctx || !trk || !points || !b || !lba || !uba || !M) return fail(RL_ERR_ARG, "null argument");
   if (idx < 0 || idx >= trk->n) return fail(RL_ERR_ARG, "control point index out of range");
-  RL_HIP(hipSetDevice(ctx->device));
   const int N = trk->N, k = trk->k;
-  // support size on the host (same mask as rl_track_create)
-  const double step = 1.0 / (double)N;
-  const double ts = trk->t_host[idx], te = trk->t_host[idx + k + 1];
-  int s0 = 0;
-  while (s0 < N && !((double)s0 * step >= ts)) ++s0;
-  int s1 = s0;
-  while (s1 < N && (double)s1 * step < te) ++s1;
-  const int m = s1 - s0;
+  const SupportRange sup = support_range(trk->t_host, k, N, idx);
+  const int m = sup.s1 - sup.s0;
   *M = m;
   if (m == 0) return RL_OK;
-  PoolBuf<double> dpts(ctx), db(ctx), dl(ctx), du(ctx);
-  RL_HIP(dpts.alloc((size_t)N * RL_NCOL)); RL_HIP(db.alloc(m)); RL_HIP(dl.alloc((size_t)2 * m)); RL_HIP(du.alloc((size_t)2 * m));
-  RL_HIP(hipMemcpyAsync(dpts.p, points, dpts.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  if (ctx->arith == RL_ARITH_REFERENCE && k == 5) if (int rc = ensure_strict_tables(ctx, trk)) return rc;
-  const rl::TrackDev td = trk->dev();
-  const double* cx = trk->c0.p;
-  const double* cy = trk->c0.p + trk->n;
-  const dim3 grid((m + 255) / 256), block(256);
-  if (ctx->arith == RL_ARITH_REFERENCE && k == 5)          // the oracle's bits (orc_track_constraint)
-    hipLaunchKernelGGL(rl::k_constraint_strict<5>, grid, block, 0, ctx->stream, td, cx, cy, dpts.p, idx, db.p, dl.p, du.p);
-  else if (k == 3)
-    hipLaunchKernelGGL(rl::k_constraint<3>, grid, block, 0, ctx->stream, td, cx, cy, dpts.p, idx, db.p, dl.p, du.p);
-  else
-    hipLaunchKernelGGL(rl::k_constraint<5>, grid, block, 0, ctx->stream, td, cx, cy, dpts.p, idx, db.p, dl.p, du.p);
-  RL_HIP(hipGetLastError());
-  RL_HIP(hipMemcpyAsync(b, db.p, m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipMemcpyAsync(lba, dl.p, (size_t)2 * m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipMemcpyAsync(uba, du.p, (size_t)2 * m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipStreamSynchronize(ctx->stream));
-  return RL_OK;
+  const bool strict = ctx->arith == RL_ARITH_REFERENCE && k == 5;        // the oracle's bits (orc_track_constraint)
+  Staging sg(ctx);
+  const double* dpts = sg.in(points, (size_t)N * RL_NCOL);
+  double *db = sg.out(b, m), *dl = sg.out(lba, (size_t)2 * m), *du = sg.out(uba, (size_t)2 * m);
+  sg.run([&] {
+    if (strict) if (int rc = ensure_strict_tables(ctx, trk)) return rc;
+    const rl::TrackDev td = trk->dev();
+    const double *cx = trk->c0.p, *cy = trk->c0.p + trk->n;
+    const dim3 grid((m + 255) / 256), block(256);
+    if (strict) return launch(ctx, rl::k_constraint_strict<5>, grid, block, 0, td, cx, cy, dpts, idx, db, dl, du);
+    return by_degree(k, [&](auto kc) { return launch(ctx, rl::k_constraint<RL_DEGREE(kc)>, grid, block, 0, td, cx, cy, dpts, idx, db, dl, du); });
+  });
+  return sg.finish();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -804,14 +571,9 @@ static int solve_batch_common(rl_ctx* ctx, const rl_track* trk, int form, const 
                                     : "i_start outside [k//2, n-(k-k//2)) (optimizer.py:301-303)");
   if (joint) {  // the window rows live in registers: 3 per thread
     int widest = 0;
-    const double step = 1.0 / (double)N;
     for (int kk = i_min; kk < i_max; ++kk) {
-      const double ts = trk->t_host[kk], te = trk->t_host[kk + 4 + k + 1];
-      int a0 = 0;
-      while (a0 < N && !((double)a0 * step >= ts)) ++a0;
-      int b0 = a0;
-      while (b0 < N && (double)b0 * step < te) ++b0;
-      if (b0 - a0 > widest) widest = b0 - a0;
+      const SupportRange w = support_range(trk->t_host, k, N, kk, 5);
+      widest = std::max(widest, w.s1 - w.s0);
     }
     if (widest > rl::kJointRowsPerThread * 256)
       return fail(RL_ERR_UNSUPPORTED, "sliding-window variant: a window spans more than 768 samples");
@@ -834,17 +596,9 @@ static int solve_batch_common(rl_ctx* ctx, const rl_track* trk, int form, const 
   a.B = B;
   a.form = form;
   a.in = in_dev;
-  if (form == RL_BOUNDS_SHARED_RINGS) {
-    if (trk->nL == 0) return fail(RL_ERR_ARG, "rl_track_set_rings was not called");
-    a.ringL = reinterpret_cast<const double2*>(trk->ringL.p);
-    a.ringR = reinterpret_cast<const double2*>(trk->ringR.p);
-    a.nL = trk->nL; a.nR = trk->nR;
-  } else if (form == RL_BOUNDS_WIDTHS || form == RL_BOUNDS_POINTS) {
-    if (!in_dev) return fail(RL_ERR_ARG, "bounds input is null");
-    a.nL = N; a.nR = N;
-  } else {
-    return fail(RL_ERR_ARG, "bad bounds_form");
-  }
+  Bounds bd;
+  if (int rc = resolve_bounds(trk, form, in_dev, bd)) return rc;
+  a.ringL = bd.ringL; a.ringR = bd.ringR; a.nL = bd.nL; a.nR = bd.nR;
   a.max_iter = max_iter;
   for (int j = 0; j < max_iter; ++j) a.i_start[j] = i_start[j];
   a.search = search;
@@ -925,34 +679,18 @@ int rl_mincurv_solve_batch_host(rl_ctx* ctx, const rl_track* trk, int bounds_for
                                 rl_stats* stats) {
   if (!ctx || !trk || !out_ctrl || !out_xy) return fail(RL_ERR_ARG, "null argument");
   if (B <= 0) return fail(RL_ERR_ARG, "B <= 0");
-  RL_HIP(hipSetDevice(ctx->device));
   const int n = trk->n, N = trk->N;
-  const int cols = bounds_form == RL_BOUNDS_WIDTHS ? 2 : (bounds_form == RL_BOUNDS_POINTS ? 4 : 0);
-  PoolBuf<double> din(ctx), dctrl(ctx), dxy(ctx);
-  PoolBuf<int> dns(ctx), dst(ctx);
-  if (cols) {
-    if (!in) return fail(RL_ERR_ARG, "bounds input is null");
-    RL_HIP(din.alloc((size_t)B * N * cols));
-    RL_HIP(hipMemcpyAsync(din.p, in, din.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  }
-  RL_HIP(dctrl.alloc((size_t)B * n * 2)); RL_HIP(dxy.alloc((size_t)B * N * 2));
-  RL_HIP(dns.alloc((size_t)B * 2 * (max_iter > 0 ? max_iter : 1))); RL_HIP(dst.alloc(B));
-  RL_HIP(hipEventRecord(ctx->ev0, ctx->stream));
-  int rc = solve_batch_common(ctx, trk, bounds_form, din.p, B, i_start, max_iter, search, dctrl.p, dxy.p,
-                              nullptr, dns.p, dst.p, stats, nullptr);
-  if (rc) return rc;
-  RL_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-  RL_HIP(hipMemcpyAsync(out_ctrl, dctrl.p, dctrl.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipMemcpyAsync(out_xy, dxy.p, dxy.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (n_success) RL_HIP(hipMemcpyAsync(n_success, dns.p, (size_t)B * 2 * max_iter * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  if (status) RL_HIP(hipMemcpyAsync(status, dst.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipStreamSynchronize(ctx->stream));
-  if (stats) {
-    float ms = 0.f;
-    RL_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    stats->kernel_ms = ms;
-  }
-  return RL_OK;
+  const int cols = bounds_cols(bounds_form);
+  if (cols && !in) return fail(RL_ERR_ARG, "bounds input is null");
+  Staging sg(ctx);
+  const double* din = cols ? sg.in(in, (size_t)B * N * cols) : nullptr;
+  double *dctrl = sg.out(out_ctrl, (size_t)B * n * 2), *dxy = sg.out(out_xy, (size_t)B * N * 2);
+  int* dns = sg.out_optional(n_success, (size_t)B * 2 * (max_iter > 0 ? max_iter : 1));
+  int* dst = sg.out_optional(status, B);
+  sg.run_timed([&] {
+    return solve_batch_common(ctx, trk, bounds_form, din, B, i_start, max_iter, search, dctrl, dxy, nullptr, dns, dst, stats, nullptr);
+  });
+  return sg.finish(stats);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1011,37 +749,16 @@ int global_tables(const rl_ctx* ctx, const rl_track* trk) {
   RL_HIP(hipMemcpyAsync(trk->gq_chunk.p, chunk.data(), chunk.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
   RL_HIP(hipMemcpyAsync(trk->gq_span.p, span.data(), span.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
   const rl::TrackDev td = trk->dev();
-  if (k == 3) {
-    hipLaunchKernelGGL(rl::k_global_normals<3>, dim3((np + 63) / 64), dim3(64), 0, ctx->stream, td, np, trk->gq_nu.p);
-    hipLaunchKernelGGL(rl::k_global_rows<3>, dim3((N + 127) / 128), dim3(128), 0, ctx->stream, td, np, trk->gq_nu.p, trk->gq_A.p);
-  } else {
-    hipLaunchKernelGGL(rl::k_global_normals<5>, dim3((np + 63) / 64), dim3(64), 0, ctx->stream, td, np, trk->gq_nu.p);
-    hipLaunchKernelGGL(rl::k_global_rows<5>, dim3((N + 127) / 128), dim3(128), 0, ctx->stream, td, np, trk->gq_nu.p, trk->gq_A.p);
-  }
-  RL_HIP(hipGetLastError());
+  if (int rc = by_degree(k, [&](auto kc) {
+        if (int rc = launch(ctx, rl::k_global_normals<RL_DEGREE(kc)>, dim3((np + 63) / 64), dim3(64), 0, td, np, trk->gq_nu.p)) return rc;
+        return launch(ctx, rl::k_global_rows<RL_DEGREE(kc)>, dim3((N + 127) / 128), dim3(128), 0, td, np, trk->gq_nu.p, trk->gq_A.p);
+      }))
+    return rc;
   RL_HIP(hipStreamSynchronize(ctx->stream));  // chunk / span are host vectors
   trk->gq_nc = nc;
   trk->gq2_nc = nc2;
   trk->gq2_rows = rows2;
   trk->gq_valid = true;
-  return RL_OK;
-}
-
-template <int K, int MAXB>
-int launch_global_t(const rl_ctx* ctx, const rl::GlobalArgs& a, int B, int block, size_t lds) {
-  auto kern = rl::k_global_qp<K, MAXB>;
-  RL_HIP(grant_dyn_lds(const_cast<rl_ctx*>(ctx), reinterpret_cast<const void*>(kern), lds));
-  hipLaunchKernelGGL(kern, dim3(B), dim3(block), lds, ctx->stream, a);
-  RL_HIP(hipGetLastError());
-  return RL_OK;
-}
-
-template <int K, int R, int G, bool AREG>
-int launch_global2_t(const rl_ctx* ctx, const rl::GlobalArgs& a, int B, int block, size_t lds) {
-  auto kern = rl::k_global_qp2<K, R, G, AREG>;
-  RL_HIP(grant_dyn_lds(const_cast<rl_ctx*>(ctx), reinterpret_cast<const void*>(kern), lds));
-  hipLaunchKernelGGL(kern, dim3(B), dim3(block), lds, ctx->stream, a);
-  RL_HIP(hipGetLastError());
   return RL_OK;
 }
 
@@ -1070,16 +787,13 @@ int global_common(rl_ctx* ctx, const rl_track* trk, const double* widths, int B,
       if (R != 10 || groups == 1) {
         a.chunk = trk->gq2_chunk.p; a.span_ch0 = trk->gq2_span.p; a.nc = trk->gq2_nc;
         if (stats) { stats->lds_bytes = (int)lds2; stats->block_threads = block2; stats->rings_in_lds = 0; }
-#define RL_G2_LAUNCH(KK, RR, GG, AR) return launch_global2_t<KK, RR, GG, AR>(ctx, a, B, block2, lds2)
-        if (trk->k == 3) {
-          if (R == 5) { if (groups == 1) RL_G2_LAUNCH(3, 5, 1, true); RL_G2_LAUNCH(3, 5, 3, true); }
-          if (R == 6) { if (groups == 1) RL_G2_LAUNCH(3, 6, 1, true); RL_G2_LAUNCH(3, 6, 3, true); }
-          RL_G2_LAUNCH(3, 10, 1, false);
-        }
-        if (R == 5) { if (groups == 1) RL_G2_LAUNCH(5, 5, 1, true); RL_G2_LAUNCH(5, 5, 3, true); }
-        if (R == 6) { if (groups == 1) RL_G2_LAUNCH(5, 6, 1, true); RL_G2_LAUNCH(5, 6, 3, true); }
-        RL_G2_LAUNCH(5, 10, 1, false);
-#undef RL_G2_LAUNCH
+        return by_degree(trk->k, [&](auto kc) {
+          constexpr int K = RL_DEGREE(kc);
+          const dim3 grid(B), blk(block2);
+          if (R == 5) return groups == 1 ? launch(ctx, rl::k_global_qp2<K, 5, 1, true>, grid, blk, lds2, a) : launch(ctx, rl::k_global_qp2<K, 5, 3, true>, grid, blk, lds2, a);
+          if (R == 6) return groups == 1 ? launch(ctx, rl::k_global_qp2<K, 6, 1, true>, grid, blk, lds2, a) : launch(ctx, rl::k_global_qp2<K, 6, 3, true>, grid, blk, lds2, a);
+          return launch(ctx, rl::k_global_qp2<K, 10, 1, false>, grid, blk, lds2, a);
+        });
       }
     }
   }
@@ -1087,14 +801,12 @@ int global_common(rl_ctx* ctx, const rl_track* trk, const double* widths, int B,
   const size_t lds = (size_t)rl::global_layout(trk->k, trk->n, a.np, block).total * sizeof(double);
   if (lds > (size_t)ctx->max_lds) return fail(RL_ERR_UNSUPPORTED, "global QP does not fit LDS");
   if (stats) { stats->lds_bytes = (int)lds; stats->block_threads = block; stats->rings_in_lds = 0; }
-  if (trk->k == 3) {
-    if (block <= 384) return launch_global_t<3, 384>(ctx, a, B, block, lds);
-    if (block <= 640) return launch_global_t<3, 640>(ctx, a, B, block, lds);
-    return launch_global_t<3, 1024>(ctx, a, B, block, lds);
-  }
-  if (block <= 384) return launch_global_t<5, 384>(ctx, a, B, block, lds);
-  if (block <= 640) return launch_global_t<5, 640>(ctx, a, B, block, lds);
-  return launch_global_t<5, 1024>(ctx, a, B, block, lds);
+  return by_degree(trk->k, [&](auto kc) {
+    constexpr int K = RL_DEGREE(kc);
+    if (block <= 384) return launch(ctx, rl::k_global_qp<K, 384>, dim3(B), dim3(block), lds, a);
+    if (block <= 640) return launch(ctx, rl::k_global_qp<K, 640>, dim3(B), dim3(block), lds, a);
+    return launch(ctx, rl::k_global_qp<K, 1024>, dim3(B), dim3(block), lds, a);
+  });
 }
 
 // ---- the two-coordinate formulation (rl_global_xy.hpp)
@@ -1135,20 +847,12 @@ int global_xy_tables(const rl_ctx* ctx, const rl_track* trk) {
   const int K1 = k + 1;
   RL_HIP(trk->gxy_bbx.alloc((size_t)N * (K1 * (K1 + 1) / 2 + K1)));
   const rl::TrackDev td = trk->dev();
-  if (k == 3) hipLaunchKernelGGL(rl::k_global_xy_pairs<3>, dim3((N + 127) / 128), dim3(128), 0, ctx->stream, td, trk->gxy_bbx.p);
-  else hipLaunchKernelGGL(rl::k_global_xy_pairs<5>, dim3((N + 127) / 128), dim3(128), 0, ctx->stream, td, trk->gxy_bbx.p);
-  RL_HIP(hipGetLastError());
+  if (int rc = by_degree(k, [&](auto kc) {
+        return launch(ctx, rl::k_global_xy_pairs<RL_DEGREE(kc)>, dim3((N + 127) / 128), dim3(128), 0, td, trk->gxy_bbx.p);
+      }))
+    return rc;
   RL_HIP(hipStreamSynchronize(ctx->stream));  // `first`, `cf`, `sc0` are host vectors
   trk->gxy_valid = true;
-  return RL_OK;
-}
-
-template <int K, int NT>
-int launch_global_xy_t(const rl_ctx* ctx, const rl::GlobalXYArgs& a, int B, size_t lds) {
-  auto kern = rl::k_global_xy<K, NT>;
-  RL_HIP(grant_dyn_lds(const_cast<rl_ctx*>(ctx), reinterpret_cast<const void*>(kern), lds));
-  hipLaunchKernelGGL(kern, dim3(B), dim3(NT), lds, ctx->stream, a);
-  RL_HIP(hipGetLastError());
   return RL_OK;
 }
 
@@ -1172,8 +876,28 @@ int global_xy_common(rl_ctx* ctx, const rl_track* trk, const double* widths, int
   const size_t lds = (size_t)rl::global_xy_layout(trk->k, trk->n, a.np, trk->N, a.nch).total * sizeof(double);
   if (lds > (size_t)ctx->max_lds) return fail(RL_ERR_UNSUPPORTED, "global QP (dof 2) does not fit LDS");
   if (stats) { stats->lds_bytes = (int)lds; stats->block_threads = block; stats->rings_in_lds = 0; }
-  if (trk->k == 3) return block == 512 ? launch_global_xy_t<3, 512>(ctx, a, B, lds) : launch_global_xy_t<3, 1024>(ctx, a, B, lds);
-  return block == 512 ? launch_global_xy_t<5, 512>(ctx, a, B, lds) : launch_global_xy_t<5, 1024>(ctx, a, B, lds);
+  return by_degree(trk->k, [&](auto kc) {
+    constexpr int K = RL_DEGREE(kc);
+    return block == 512 ? launch(ctx, rl::k_global_xy<K, 512>, dim3(B), dim3(512), lds, a) : launch(ctx, rl::k_global_xy<K, 1024>, dim3(B), dim3(1024), lds, a);
+  });
+}
+
+// The two global QPs with host buffers: the same staging around their table builder and their `_common` call.  `opt_width`:
+// doubles per free control point of the optional third output (a [B, n-k]: 1, z [B, n-k, 2]: 2).  The table build stays in
+// front of the timed region.
+template <typename Tables, typename Common>
+int global_batch_host(rl_ctx* ctx, const rl_track* trk, const double* widths, int B, int opt_width, double* out_ctrl,
+                             double* out_xy, double* out_opt, double* out_stats, rl_stats* stats, Tables tables, Common common) {
+  if (!ctx || !trk || !widths || !out_ctrl || !out_stats) return fail(RL_ERR_ARG, "null argument");
+  if (B <= 0) return fail(RL_ERR_ARG, "B <= 0");
+  const int n = trk->n, N = trk->N;
+  Staging sg(ctx);
+  const double* dw = sg.in(widths, (size_t)B * N * 2);
+  double *dctrl = sg.out(out_ctrl, (size_t)B * n * 2), *dxy = sg.out(out_xy, (size_t)B * N * 2);
+  double *dopt = sg.out(out_opt, (size_t)B * (n - trk->k) * opt_width), *dst = sg.out(out_stats, (size_t)B * 8);
+  sg.run([&] { return tables(ctx, trk); });
+  sg.run_timed([&] { return common(dw, dctrl, dxy, dopt, dst); });
+  return sg.finish(stats);
 }
 
 }  // namespace
@@ -1188,31 +912,10 @@ int rl_mincurv_global_xy_batch_dev(rl_ctx* ctx, const rl_track* trk, const doubl
 int rl_mincurv_global_xy_batch_host(rl_ctx* ctx, const rl_track* trk, const double* widths, int B, double margin, double lon,
                                     int n_outer, double* out_ctrl, double* out_xy, double* out_z, double* out_stats,
                                     rl_stats* stats) {
-  if (!ctx || !trk || !widths || !out_ctrl || !out_stats) return fail(RL_ERR_ARG, "null argument");
-  if (B <= 0) return fail(RL_ERR_ARG, "B <= 0");
-  RL_HIP(hipSetDevice(ctx->device));
-  const int n = trk->n, N = trk->N, np = n - trk->k;
-  PoolBuf<double> dw(ctx), dctrl(ctx), dxy(ctx), dz(ctx), dst(ctx);
-  RL_HIP(dw.alloc((size_t)B * N * 2)); RL_HIP(dctrl.alloc((size_t)B * n * 2));
-  if (out_xy) RL_HIP(dxy.alloc((size_t)B * N * 2));
-  if (out_z) RL_HIP(dz.alloc((size_t)B * np * 2));
-  RL_HIP(dst.alloc((size_t)B * 8));
-  RL_HIP(hipMemcpyAsync(dw.p, widths, dw.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  if (int rc = global_xy_tables(ctx, trk)) return rc;  // keeps the table build out of the timed region
-  RL_HIP(hipEventRecord(ctx->ev0, ctx->stream));
-  if (int rc = global_xy_common(ctx, trk, dw.p, B, margin, lon, n_outer, dctrl.p, dxy.p, dz.p, dst.p, stats)) return rc;
-  RL_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-  RL_HIP(hipMemcpyAsync(out_ctrl, dctrl.p, dctrl.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (out_xy) RL_HIP(hipMemcpyAsync(out_xy, dxy.p, dxy.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (out_z) RL_HIP(hipMemcpyAsync(out_z, dz.p, dz.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipMemcpyAsync(out_stats, dst.p, dst.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipStreamSynchronize(ctx->stream));
-  if (stats) {
-    float ms = 0.f;
-    RL_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    stats->kernel_ms = ms;
-  }
-  return RL_OK;
+  return global_batch_host(ctx, trk, widths, B, 2, out_ctrl, out_xy, out_z, out_stats, stats, global_xy_tables,
+                           [&](const double* w, double* c, double* xy, double* z, double* st) {
+                             return global_xy_common(ctx, trk, w, B, margin, lon, n_outer, c, xy, z, st, stats);
+                           });
 }
 
 int rl_mincurv_global_batch_dev(rl_ctx* ctx, const rl_track* trk, const double* widths, int B,
@@ -1224,31 +927,10 @@ int rl_mincurv_global_batch_dev(rl_ctx* ctx, const rl_track* trk, const double* 
 int rl_mincurv_global_batch_host(rl_ctx* ctx, const rl_track* trk, const double* widths, int B,
                                  double margin, int n_outer, double* out_ctrl, double* out_xy,
                                  double* out_a, double* out_stats, rl_stats* stats) {
-  if (!ctx || !trk || !widths || !out_ctrl || !out_stats) return fail(RL_ERR_ARG, "null argument");
-  if (B <= 0) return fail(RL_ERR_ARG, "B <= 0");
-  RL_HIP(hipSetDevice(ctx->device));
-  const int n = trk->n, N = trk->N, np = n - trk->k;
-  PoolBuf<double> dw(ctx), dctrl(ctx), dxy(ctx), da(ctx), dst(ctx);
-  RL_HIP(dw.alloc((size_t)B * N * 2)); RL_HIP(dctrl.alloc((size_t)B * n * 2));
-  if (out_xy) RL_HIP(dxy.alloc((size_t)B * N * 2));
-  if (out_a) RL_HIP(da.alloc((size_t)B * np));
-  RL_HIP(dst.alloc((size_t)B * 8));
-  RL_HIP(hipMemcpyAsync(dw.p, widths, dw.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  if (int rc = global_tables(ctx, trk)) return rc;  // keeps the table build out of the timed region
-  RL_HIP(hipEventRecord(ctx->ev0, ctx->stream));
-  if (int rc = global_common(ctx, trk, dw.p, B, margin, n_outer, dctrl.p, dxy.p, da.p, dst.p, stats)) return rc;
-  RL_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-  RL_HIP(hipMemcpyAsync(out_ctrl, dctrl.p, dctrl.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (out_xy) RL_HIP(hipMemcpyAsync(out_xy, dxy.p, dxy.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (out_a) RL_HIP(hipMemcpyAsync(out_a, da.p, da.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipMemcpyAsync(out_stats, dst.p, dst.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipStreamSynchronize(ctx->stream));
-  if (stats) {
-    float ms = 0.f;
-    RL_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    stats->kernel_ms = ms;
-  }
-  return RL_OK;
+  return global_batch_host(ctx, trk, widths, B, 1, out_ctrl, out_xy, out_a, out_stats, stats, global_tables,
+                           [&](const double* w, double* c, double* xy, double* a, double* st) {
+                             return global_common(ctx, trk, w, B, margin, n_outer, c, xy, a, st, stats);
+                           });
 }
 
 int rl_mincurv_sweep(rl_ctx* ctx, rl_track* trk, const int* i_start, int max_iter,
@@ -1301,9 +983,9 @@ static int region_launch(rl_ctx* ctx, const double* xy, long long stride, long l
   a.xy = xy; a.stride = stride; a.n = n;
   a.verts = reinterpret_cast<const double2*>(dv); a.offsets = doff; a.box = reinterpret_cast<const double4*>(dbox); a.R = R;
   a.out = out; a.codes = dcode; a.tag = tag; a.tag_stride = tag_stride;
-  hipLaunchKernelGGL(rl::k_region_index, dim3((unsigned)((n + rl::kRegionBlock - 1) / rl::kRegionBlock)),
-                     dim3(rl::kRegionBlock), 0, ctx->stream, a);
-  RL_HIP(hipGetLastError());
+  if (int rc = launch(ctx, rl::k_region_index, dim3((unsigned)((n + rl::kRegionBlock - 1) / rl::kRegionBlock)),
+                      dim3(rl::kRegionBlock), 0, a))
+    return rc;
   RL_HIP(ar.end());
   return RL_OK;
 }
@@ -1315,16 +997,12 @@ int rl_fill_region(rl_ctx* ctx, double* points, int B, int N, const double* vert
   if (int rc = region_check(verts, offsets, R)) return rc;
   if (R == 0 || B == 0 || N == 0) return RL_OK;
   if (!points || !codes) return fail(RL_ERR_ARG, "null argument");
-  RL_HIP(hipSetDevice(ctx->device));
   const long long n = (long long)B * N;
-  PoolBuf<double> dpts(ctx);
-  RL_HIP(dpts.alloc((size_t)n * RL_NCOL));
-  RL_HIP(hipMemcpyAsync(dpts.p, points, dpts.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  Staging sg(ctx);
+  double* dpts = sg.inout(points, (size_t)n * RL_NCOL);
   // REGION is column 8 (models/trajectory.py)
-  if (int rc = region_launch(ctx, dpts.p, RL_NCOL, n, verts, offsets, R, codes, nullptr, dpts.p + 8, RL_NCOL)) return rc;
-  RL_HIP(hipMemcpyAsync(points, dpts.p, dpts.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipStreamSynchronize(ctx->stream));
-  return RL_OK;
+  sg.run([&] { return region_launch(ctx, dpts, RL_NCOL, n, verts, offsets, R, codes, nullptr, dpts + 8, RL_NCOL); });
+  return sg.finish();
 }
 
 int rl_region_index_dev(rl_ctx* ctx, const double* xy, int B, int N, int stride, const double* verts, const int* offsets,
@@ -1418,17 +1096,10 @@ int rl_qss_sim_dev(rl_ctx* ctx, double* points, int B, int N, const double* acc_
 #endif
     // waves of the (one) workgroup an instance's tables leave room for: four is the fastest at every size measured
     // (DESIGN_HISTORY.md 3c); one and two exist for the tests (rl_ctx_set_option "qss_df_waves")
-    if (ctx->qss_df_waves == 1) {
-      RL_HIP(grant_dyn_lds(ctx, reinterpret_cast<const void*>(rl::k_qss_dfw<1>), lds_df));
-      hipLaunchKernelGGL(rl::k_qss_dfw<1>, dim3(B), dim3(64), lds_df, ctx->stream, a);
-    } else if (ctx->qss_df_waves == 2) {
-      RL_HIP(grant_dyn_lds(ctx, reinterpret_cast<const void*>(rl::k_qss_dfw<2>), lds_df));
-      hipLaunchKernelGGL(rl::k_qss_dfw<2>, dim3(B), dim3(128), lds_df, ctx->stream, a);
-    } else {
-      RL_HIP(grant_dyn_lds(ctx, reinterpret_cast<const void*>(rl::k_qss_dfw<4>), lds_df));
-      hipLaunchKernelGGL(rl::k_qss_dfw<4>, dim3(B), dim3(256), lds_df, ctx->stream, a);
-    }
-    RL_HIP(hipGetLastError());
+    if (int rc = ctx->qss_df_waves == 1   ? launch(ctx, rl::k_qss_dfw<1>, dim3(B), dim3(64), lds_df, a)
+                 : ctx->qss_df_waves == 2 ? launch(ctx, rl::k_qss_dfw<2>, dim3(B), dim3(128), lds_df, a)
+                                          : launch(ctx, rl::k_qss_dfw<4>, dim3(B), dim3(256), lds_df, a))
+      return rc;
     if (ddbg) {   // diagnostic build only: synchronous
       std::vector<int> hd((size_t)B * 12);
       RL_HIP(hipStreamSynchronize(ctx->stream));
@@ -1444,9 +1115,7 @@ int rl_qss_sim_dev(rl_ctx* ctx, double* points, int B, int N, const double* acc_
     }
     a.redo = 1;
   }
-  RL_HIP(grant_dyn_lds(ctx, reinterpret_cast<const void*>(rl::k_qss_sim), lds));
-  hipLaunchKernelGGL(rl::k_qss_sim, dim3(B), dim3(64), lds, ctx->stream, a);
-  RL_HIP(hipGetLastError());
+  if (int rc = launch(ctx, rl::k_qss_sim, dim3(B), dim3(64), lds, a)) return rc;
   RL_HIP(ar.end());
   return RL_OK;
 }
@@ -1456,32 +1125,15 @@ int rl_qss_sim(rl_ctx* ctx, double* points, int B, int N, const double* acc_x, c
                int* iters) {
   if (!ctx || !points || !iters) return fail(RL_ERR_ARG, "null argument");
   if (B <= 0 || N < 2) return fail(RL_ERR_ARG, "bad sizes");
-  RL_HIP(hipSetDevice(ctx->device));
-  PoolBuf<double> dpts(ctx);
-  PoolBuf<int> dit(ctx);
-  RL_HIP(dpts.alloc((size_t)B * N * RL_NCOL)); RL_HIP(dit.alloc(B));
-  RL_HIP(hipMemcpyAsync(dpts.p, points, dpts.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  if (int rc = rl_qss_sim_dev(ctx, dpts.p, B, N, acc_x, acc_c, acc_m, dcc_x, dcc_c, dcc_m, params, dit.p)) return rc;
-  RL_HIP(hipMemcpyAsync(points, dpts.p, dpts.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipMemcpyAsync(iters, dit.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipStreamSynchronize(ctx->stream));
-  return RL_OK;
+  Staging sg(ctx);
+  double* dpts = sg.inout(points, (size_t)B * N * RL_NCOL);
+  int* dit = sg.out(iters, B);
+  sg.run([&] { return rl_qss_sim_dev(ctx, dpts, B, N, acc_x, acc_c, acc_m, dcc_x, dcc_c, dcc_m, params, dit); });
+  return sg.finish();
 }
 
 // ------------------------------------------------------------------------------------------------
 // tables of a solved batch and their summary (csrc/rl_tables.hpp)
-extern "C++" {
-template <int K>
-static int launch_tables(rl_ctx* ctx, const rl::TablesArgs& a, bool rings_lds, size_t lds) {
-  const void* fn = rings_lds ? reinterpret_cast<const void*>(rl::k_tables<K, true>) : reinterpret_cast<const void*>(rl::k_tables<K, false>);
-  RL_HIP(grant_dyn_lds(ctx, fn, lds));
-  if (rings_lds) hipLaunchKernelGGL((rl::k_tables<K, true>), dim3(a.B), dim3(rl::kTablesThreads), lds, ctx->stream, a);
-  else hipLaunchKernelGGL((rl::k_tables<K, false>), dim3(a.B), dim3(rl::kTablesThreads), lds, ctx->stream, a);
-  RL_HIP(hipGetLastError());
-  return RL_OK;
-}
-}  // extern "C++"
-
 int rl_tables_batch_dev(rl_ctx* ctx, const rl_track* trk, const double* ctrl, int B, int bounds_form, const double* bounds,
                         double length, const double* bank, int bank_per_instance, double* points) {
   if (!ctx || !trk || !ctrl || !points) return fail(RL_ERR_ARG, "null argument");
@@ -1491,17 +1143,9 @@ int rl_tables_batch_dev(rl_ctx* ctx, const rl_track* trk, const double* ctrl, in
   rl::TablesArgs a;
   std::memset(&a, 0, sizeof(a));
   a.ctrl = ctrl; a.B = B; a.form = bounds_form; a.in = bounds;
-  if (bounds_form == RL_BOUNDS_SHARED_RINGS) {
-    if (trk->nL == 0) return fail(RL_ERR_ARG, "rl_track_set_rings was not called");
-    a.ringL = reinterpret_cast<const double2*>(trk->ringL.p);
-    a.ringR = reinterpret_cast<const double2*>(trk->ringR.p);
-    a.nL = trk->nL; a.nR = trk->nR;
-  } else if (bounds_form == RL_BOUNDS_WIDTHS || bounds_form == RL_BOUNDS_POINTS) {
-    if (!bounds) return fail(RL_ERR_ARG, "bounds input is null");
-    a.nL = N; a.nR = N;
-  } else {
-    return fail(RL_ERR_ARG, "bad bounds_form");
-  }
+  Bounds bd;
+  if (int rc = resolve_bounds(trk, bounds_form, bounds, bd)) return rc;
+  a.ringL = bd.ringL; a.ringR = bd.ringR; a.nL = bd.nL; a.nR = bd.nR;
   RL_HIP(hipSetDevice(ctx->device));
   // width-form rings in the arithmetic the sweep of this context builds them with: the reference-order tables where that
   // arithmetic exists (degree 5) and was not switched off, the fast tables elsewhere
@@ -1526,7 +1170,12 @@ int rl_tables_batch_dev(rl_ctx* ctx, const rl_track* trk, const double* ctrl, in
     RL_HIP(ar.reserve(Arena::pad(a.gscratch_stride * (size_t)B * sizeof(double))));
     a.gscratch = ar.take<double>(a.gscratch_stride * (size_t)B);
   }
-  if (int rc = (k == 3 ? launch_tables<3>(ctx, a, rings_lds, lds) : launch_tables<5>(ctx, a, rings_lds, lds))) return rc;
+  if (int rc = by_degree(k, [&](auto kc) {
+        constexpr int K = RL_DEGREE(kc);
+        const dim3 grid(B), block(rl::kTablesThreads);
+        return rings_lds ? launch(ctx, rl::k_tables<K, true>, grid, block, lds, a) : launch(ctx, rl::k_tables<K, false>, grid, block, lds, a);
+      }))
+    return rc;
   if (!rings_lds) RL_HIP(ar.end());
   return RL_OK;
 }
@@ -1535,25 +1184,16 @@ int rl_tables_batch_host(rl_ctx* ctx, const rl_track* trk, const double* ctrl, i
                          double length, const double* bank, int bank_per_instance, double* points) {
   if (!ctx || !trk || !ctrl || !points) return fail(RL_ERR_ARG, "null argument");
   if (B <= 0) return fail(RL_ERR_ARG, "B <= 0");
-  const int cols = bounds_form == RL_BOUNDS_WIDTHS ? 2 : (bounds_form == RL_BOUNDS_POINTS ? 4 : 0);
+  const int cols = bounds_cols(bounds_form);
   if (cols && !bounds) return fail(RL_ERR_ARG, "bounds input is null");
-  RL_HIP(hipSetDevice(ctx->device));
   const int n = trk->n, N = trk->N;
-  PoolBuf<double> dctrl(ctx), din(ctx), dbank(ctx), dpts(ctx);
-  RL_HIP(dctrl.alloc((size_t)B * n * 2)); RL_HIP(dpts.alloc((size_t)B * N * RL_NCOL));
-  RL_HIP(hipMemcpyAsync(dctrl.p, ctrl, dctrl.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  if (cols) {
-    RL_HIP(din.alloc((size_t)B * N * cols));
-    RL_HIP(hipMemcpyAsync(din.p, bounds, din.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  }
-  if (bank) {
-    RL_HIP(dbank.alloc((size_t)(bank_per_instance ? B : 1) * N));
-    RL_HIP(hipMemcpyAsync(dbank.p, bank, dbank.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  }
-  if (int rc = rl_tables_batch_dev(ctx, trk, dctrl.p, B, bounds_form, din.p, length, dbank.p, bank_per_instance, dpts.p)) return rc;
-  RL_HIP(hipMemcpyAsync(points, dpts.p, dpts.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipStreamSynchronize(ctx->stream));
-  return RL_OK;
+  Staging sg(ctx);
+  const double* dctrl = sg.in(ctrl, (size_t)B * n * 2);
+  double* dpts = sg.out(points, (size_t)B * N * RL_NCOL);
+  const double* din = cols ? sg.in(bounds, (size_t)B * N * cols) : nullptr;
+  const double* dbank = sg.in(bank, (size_t)(bank_per_instance ? B : 1) * N);
+  sg.run([&] { return rl_tables_batch_dev(ctx, trk, dctrl, B, bounds_form, din, length, dbank, bank_per_instance, dpts); });
+  return sg.finish();
 }
 
 int rl_table_summary_dev(rl_ctx* ctx, const double* points, int B, int N, const int* iters, double* out) {
@@ -1562,61 +1202,54 @@ int rl_table_summary_dev(rl_ctx* ctx, const double* points, int B, int N, const 
   const size_t lds = (size_t)N * sizeof(double);
   if (lds > (size_t)ctx->max_lds) return fail(RL_ERR_UNSUPPORTED, "table summary: trajectory too long for the LDS-resident TIME column");
   RL_HIP(hipSetDevice(ctx->device));
-  RL_HIP(grant_dyn_lds(ctx, reinterpret_cast<const void*>(rl::k_table_summary), lds));
-  hipLaunchKernelGGL(rl::k_table_summary, dim3(B), dim3(rl::kWave), lds, ctx->stream, points, N, iters, out);
-  RL_HIP(hipGetLastError());
-  return RL_OK;
+  return launch(ctx, rl::k_table_summary, dim3(B), dim3(rl::kWave), lds, points, N, iters, out);
 }
 
 int rl_table_summary_host(rl_ctx* ctx, const double* points, int B, int N, const int* iters, double* out) {
   if (!ctx || !points || !out) return fail(RL_ERR_ARG, "null argument");
   if (B <= 0 || N <= 0) return fail(RL_ERR_ARG, "bad sizes");
-  RL_HIP(hipSetDevice(ctx->device));
-  PoolBuf<double> dpts(ctx), dout(ctx);
-  PoolBuf<int> dit(ctx);
-  RL_HIP(dpts.alloc((size_t)B * N * RL_NCOL)); RL_HIP(dout.alloc((size_t)B * 8));
-  RL_HIP(hipMemcpyAsync(dpts.p, points, dpts.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  if (iters) {
-    RL_HIP(dit.alloc(B));
-    RL_HIP(hipMemcpyAsync(dit.p, iters, (size_t)B * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-  }
-  if (int rc = rl_table_summary_dev(ctx, dpts.p, B, N, dit.p, dout.p)) return rc;
-  RL_HIP(hipMemcpyAsync(out, dout.p, dout.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipStreamSynchronize(ctx->stream));
+  Staging sg(ctx);
+  const double* dpts = sg.in(points, (size_t)B * N * RL_NCOL);
+  double* dout = sg.out(out, (size_t)B * 8);
+  const int* dit = sg.in(iters, B);
+  sg.run([&] { return rl_table_summary_dev(ctx, dpts, B, N, dit, dout); });
+  return sg.finish();
+}
+
+// rl_dt_eval_nodes / rl_dt_eval_jac: the checks of what they share, then its staging and the DtArgs fill
+static int dt_check(const rl_ctx* ctx, const double* model, int B, int N, const double* s, const double* kappa, const double* left,
+                    const double* right, double track_length, const double* X, const double* U, const double* T, bool outputs) {
+  static_assert((int)RL_DT_NPARAM == (int)rl::DT_NPARAM, "parameter tables out of step");
+  if (!ctx || !model || !s || !kappa || !left || !right || !X || !U || !T || !outputs) return fail(RL_ERR_ARG, "null argument");
+  if (B <= 0 || N < 2 || !(track_length > 0.0)) return fail(RL_ERR_ARG, "bad sizes");
   return RL_OK;
+}
+
+static rl::DtArgs dt_stage(Staging& sg, const double* model, int B, int N, const double* s, const double* kappa, const double* left,
+                           const double* right, double margin, double track_length, const double* X, const double* U,
+                           const double* T) {
+  const size_t bn = (size_t)B * N;
+  rl::DtArgs a;
+  for (int i = 0; i < rl::DT_NPARAM; ++i) a.p[i] = model[i];
+  a.B = B; a.N = N; a.margin = margin; a.track_length = track_length;
+  a.s = sg.in(s, N); a.kappa = sg.in(kappa, N); a.left = sg.in(left, N); a.right = sg.in(right, N);
+  a.X = sg.in(X, bn * 6); a.U = sg.in(U, bn * 4); a.T = sg.in(T, bn);
+  a.eq = nullptr; a.ineq = nullptr; a.cost_part = nullptr;
+  return a;
 }
 
 int rl_dt_eval_nodes(rl_ctx* ctx, const double* model, int B, int N, const double* s, const double* kappa,
                      const double* left, const double* right, double margin, double track_length,
                      const double* X, const double* U, const double* T, double* eq, double* ineq,
                      double* cost) {
-  static_assert((int)RL_DT_NPARAM == (int)rl::DT_NPARAM, "parameter tables out of step");
-  if (!ctx || !model || !s || !kappa || !left || !right || !X || !U || !T || !eq || !ineq || !cost)
-    return fail(RL_ERR_ARG, "null argument");
-  if (B <= 0 || N < 2 || !(track_length > 0.0)) return fail(RL_ERR_ARG, "bad sizes");
-  RL_HIP(hipSetDevice(ctx->device));
+  if (int rc = dt_check(ctx, model, B, N, s, kappa, left, right, track_length, X, U, T, eq && ineq && cost)) return rc;
   const size_t bn = (size_t)B * N;
-  PoolBuf<double> ds(ctx), dk(ctx), dl(ctx), dr(ctx), dX(ctx), dU(ctx), dT(ctx), deq(ctx), dg(ctx), dc(ctx);
-  RL_HIP(ds.alloc(N)); RL_HIP(dk.alloc(N)); RL_HIP(dl.alloc(N)); RL_HIP(dr.alloc(N));
-  RL_HIP(dX.alloc(bn * 6)); RL_HIP(dU.alloc(bn * 4)); RL_HIP(dT.alloc(bn));
-  RL_HIP(deq.alloc(bn * rl::kDtNeq)); RL_HIP(dg.alloc(bn * rl::kDtNineq)); RL_HIP(dc.alloc(bn));
-  auto up = [&](PoolBuf<double>& d, const double* h) {
-    return hipMemcpyAsync(d.p, h, d.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-  };
-  RL_HIP(up(ds, s)); RL_HIP(up(dk, kappa)); RL_HIP(up(dl, left)); RL_HIP(up(dr, right));
-  RL_HIP(up(dX, X)); RL_HIP(up(dU, U)); RL_HIP(up(dT, T));
-  rl::DtArgs a;
-  for (int i = 0; i < rl::DT_NPARAM; ++i) a.p[i] = model[i];
-  a.B = B; a.N = N; a.s = ds.p; a.kappa = dk.p; a.left = dl.p; a.right = dr.p; a.margin = margin;
-  a.track_length = track_length; a.X = dX.p; a.U = dU.p; a.T = dT.p;
-  a.eq = deq.p; a.ineq = dg.p; a.cost_part = dc.p;
-  hipLaunchKernelGGL(rl::k_dt_eval_nodes, dim3((N + 127) / 128, B), dim3(128), 0, ctx->stream, a);
-  RL_HIP(hipGetLastError());
   std::vector<double> part(bn);
-  RL_HIP(hipMemcpyAsync(eq, deq.p, deq.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipMemcpyAsync(ineq, dg.p, dg.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipMemcpyAsync(part.data(), dc.p, bn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipStreamSynchronize(ctx->stream));
+  Staging sg(ctx);
+  rl::DtArgs a = dt_stage(sg, model, B, N, s, kappa, left, right, margin, track_length, X, U, T);
+  a.eq = sg.out(eq, bn * rl::kDtNeq); a.ineq = sg.out(ineq, bn * rl::kDtNineq); a.cost_part = sg.out(part.data(), bn);
+  sg.run([&] { return launch(ctx, rl::k_dt_eval_nodes, dim3((N + 127) / 128, B), dim3(128), 0, a); });
+  if (int rc = sg.finish()) return rc;
   for (int b = 0; b < B; ++b) {  // the objective is a plain sum over the nodes, in node order
     double c = 0.0;
     for (int j = 0; j < N; ++j) c += part[(size_t)b * N + j];
@@ -1629,36 +1262,16 @@ int rl_dt_eval_jac(rl_ctx* ctx, const double* model, int B, int N, const double*
                    const double* left, const double* right, double margin, double track_length,
                    const double* X, const double* U, const double* T, double* jac_eq, double* jac_ineq,
                    double* grad_cost) {
-  if (!ctx || !model || !s || !kappa || !left || !right || !X || !U || !T || !jac_eq || !jac_ineq || !grad_cost)
-    return fail(RL_ERR_ARG, "null argument");
-  if (B <= 0 || N < 2 || !(track_length > 0.0)) return fail(RL_ERR_ARG, "bad sizes");
-  RL_HIP(hipSetDevice(ctx->device));
+  if (int rc = dt_check(ctx, model, B, N, s, kappa, left, right, track_length, X, U, T, jac_eq && jac_ineq && grad_cost)) return rc;
   const size_t bn = (size_t)B * N;
-  PoolBuf<double> ds(ctx), dk(ctx), dl(ctx), dr(ctx), dX(ctx), dU(ctx), dT(ctx), dje(ctx), dji(ctx), dgc(ctx);
-  RL_HIP(ds.alloc(N)); RL_HIP(dk.alloc(N)); RL_HIP(dl.alloc(N)); RL_HIP(dr.alloc(N));
-  RL_HIP(dX.alloc(bn * 6)); RL_HIP(dU.alloc(bn * 4)); RL_HIP(dT.alloc(bn));
-  RL_HIP(dje.alloc(bn * rl::kDtNeq * rl::kDtNvar)); RL_HIP(dji.alloc(bn * rl::kDtNineq * rl::kDtNvar));
-  RL_HIP(dgc.alloc(bn * rl::kDtNvar));
-  auto up = [&](PoolBuf<double>& d, const double* h) {
-    return hipMemcpyAsync(d.p, h, d.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-  };
-  RL_HIP(up(ds, s)); RL_HIP(up(dk, kappa)); RL_HIP(up(dl, left)); RL_HIP(up(dr, right));
-  RL_HIP(up(dX, X)); RL_HIP(up(dU, U)); RL_HIP(up(dT, T));
+  Staging sg(ctx);
   rl::DtJacArgs ja;
-  rl::DtArgs& a = ja.f;
-  for (int i = 0; i < rl::DT_NPARAM; ++i) a.p[i] = model[i];
-  a.B = B; a.N = N; a.s = ds.p; a.kappa = dk.p; a.left = dl.p; a.right = dr.p; a.margin = margin;
-  a.track_length = track_length; a.X = dX.p; a.U = dU.p; a.T = dT.p;
-  a.eq = nullptr; a.ineq = nullptr; a.cost_part = nullptr;
-  ja.jac_eq = dje.p; ja.jac_ineq = dji.p; ja.grad_cost = dgc.p;
+  ja.f = dt_stage(sg, model, B, N, s, kappa, left, right, margin, track_length, X, U, T);
+  ja.jac_eq = sg.out(jac_eq, bn * rl::kDtNeq * rl::kDtNvar); ja.jac_ineq = sg.out(jac_ineq, bn * rl::kDtNineq * rl::kDtNvar);
+  ja.grad_cost = sg.out(grad_cost, bn * rl::kDtNvar);
   const int slices = (rl::kDtNvar + rl::kDtJacND - 1) / rl::kDtJacND;
-  hipLaunchKernelGGL(rl::k_dt_eval_jac, dim3((N + 127) / 128, B, slices), dim3(128), 0, ctx->stream, ja);
-  RL_HIP(hipGetLastError());
-  RL_HIP(hipMemcpyAsync(jac_eq, dje.p, dje.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipMemcpyAsync(jac_ineq, dji.p, dji.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipMemcpyAsync(grad_cost, dgc.p, dgc.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipStreamSynchronize(ctx->stream));
-  return RL_OK;
+  sg.run([&] { return launch(ctx, rl::k_dt_eval_jac, dim3((N + 127) / 128, B, slices), dim3(128), 0, ja); });
+  return sg.finish();
 }
 
 int rl_mintime_solve_batch_dev(rl_ctx* ctx, const double* model, int B, int N, const double* s, const double* kappa,
@@ -1879,27 +1492,21 @@ int rl_mintime_solve_batch(rl_ctx* ctx, const double* model, int B, int N, const
                            double* T, int max_iter, double tol, double* stats) {
   if (!ctx || !model || !s || !kappa || !left || !right || !X || !U || !T || !stats) return fail(RL_ERR_ARG, "null argument");
   if (B <= 0 || N < 8) return fail(RL_ERR_ARG, "bad sizes (N >= 8 nodes)");
-  RL_HIP(hipSetDevice(ctx->device));
   const size_t bn = (size_t)B * N, nb_ = bounds_per_instance ? bn : (size_t)N;
   for (size_t i = 0; i < nb_; ++i)
     if (!(right[i] + margin < left[i] - margin)) return fail(RL_ERR_ARG, "track narrower than the vehicle plus margins (min_time_optimizer.py:135)");
-  PoolBuf<double> ds(ctx), dk(ctx), dl(ctx), dr(ctx), dX(ctx), dU(ctx), dT(ctx), dst(ctx);
-  RL_HIP(ds.alloc(N)); RL_HIP(dk.alloc(N)); RL_HIP(dl.alloc(nb_)); RL_HIP(dr.alloc(nb_));
-  RL_HIP(dX.alloc(bn * 6)); RL_HIP(dU.alloc(bn * 4)); RL_HIP(dT.alloc(bn)); RL_HIP(dst.alloc((size_t)B * 12));
-  auto up = [&](PoolBuf<double>& d, const double* h) { return hipMemcpyAsync(d.p, h, d.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream); };
-  RL_HIP(up(ds, s)); RL_HIP(up(dk, kappa)); RL_HIP(up(dl, left)); RL_HIP(up(dr, right));
-  RL_HIP(up(dX, X)); RL_HIP(up(dU, U)); RL_HIP(up(dT, T));
-  ctx->mt_poll = true;
-  const int rc = rl_mintime_solve_batch_dev(ctx, model, B, N, ds.p, dk.p, dl.p, dr.p, bounds_per_instance, margin, track_length,
-                                            average_track_width, speed_cap, dX.p, dU.p, dT.p, max_iter, tol, dst.p);
-  ctx->mt_poll = false;
-  if (rc) return rc;
-  RL_HIP(hipMemcpyAsync(X, dX.p, dX.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipMemcpyAsync(U, dU.p, dU.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipMemcpyAsync(T, dT.p, dT.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipMemcpyAsync(stats, dst.p, dst.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipStreamSynchronize(ctx->stream));
-  return RL_OK;
+  Staging sg(ctx);
+  const double *ds = sg.in(s, N), *dk = sg.in(kappa, N), *dl = sg.in(left, nb_), *dr = sg.in(right, nb_);
+  double *dX = sg.inout(X, bn * 6), *dU = sg.inout(U, bn * 4), *dT = sg.inout(T, bn);
+  double* dst = sg.out(stats, (size_t)B * 12);
+  sg.run([&] {
+    ctx->mt_poll = true;
+    const int rc = rl_mintime_solve_batch_dev(ctx, model, B, N, ds, dk, dl, dr, bounds_per_instance, margin, track_length,
+                                              average_track_width, speed_cap, dX, dU, dT, max_iter, tol, dst);
+    ctx->mt_poll = false;
+    return rc;
+  });
+  return sg.finish();
 }
 
 
@@ -1922,20 +1529,13 @@ int rl_bicycle_eval_nodes(rl_ctx* ctx, const double* model, int B, int N, const 
   if (B <= 0 || N < 8) return fail(RL_ERR_ARG, "bad sizes (N >= 8 nodes)");
   rl::BkProblem P{};
   if (int rc = bk_problem(model, N, P)) return rc;
-  RL_HIP(hipSetDevice(ctx->device));
   const size_t bn = (size_t)B * N;
-  PoolBuf<double> dP0(ctx), dyaw(ctx), dX(ctx), dU(ctx), dT(ctx), deq(ctx), din(ctx);
-  RL_HIP(dP0.alloc((size_t)2 * N)); RL_HIP(dyaw.alloc(N)); RL_HIP(dX.alloc(bn * 5)); RL_HIP(dU.alloc(bn * 2));
-  RL_HIP(dT.alloc(bn)); RL_HIP(deq.alloc(bn * rl::kBkNe)); RL_HIP(din.alloc(bn * 2));
-  auto up = [&](PoolBuf<double>& d, const double* h) { return hipMemcpyAsync(d.p, h, d.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream); };
-  RL_HIP(up(dP0, P0)); RL_HIP(up(dyaw, yaw)); RL_HIP(up(dX, X)); RL_HIP(up(dU, U)); RL_HIP(up(dT, T));
-  P.P0 = dP0.p; P.yaw = dyaw.p;
-  hipLaunchKernelGGL(rl::k_bk_eval, dim3((N + 63) / 64, B), dim3(64), 0, ctx->stream, P, B, (const double*)dX.p,
-                     (const double*)dU.p, (const double*)dT.p, deq.p, din.p);
-  RL_HIP(hipGetLastError());
-  RL_HIP(hipMemcpyAsync(eq, deq.p, deq.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipMemcpyAsync(ineq, din.p, din.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipStreamSynchronize(ctx->stream));
+  Staging sg(ctx);
+  P.P0 = sg.in(P0, (size_t)2 * N); P.yaw = sg.in(yaw, N);
+  const double *dX = sg.in(X, bn * 5), *dU = sg.in(U, bn * 2), *dT = sg.in(T, bn);
+  double *deq = sg.out(eq, bn * rl::kBkNe), *din = sg.out(ineq, bn * 2);
+  sg.run([&] { return launch(ctx, rl::k_bk_eval, dim3((N + 63) / 64, B), dim3(64), 0, P, B, dX, dU, dT, deq, din); });
+  if (int rc = sg.finish()) return rc;
   for (int b = 0; b < B; ++b) {   // min_time_cost (:9-10), summed in node order
     double c = 0.0;
     for (int j = 0; j < N; ++j) c += T[(size_t)b * N + j];
@@ -1988,22 +1588,14 @@ int rl_bicycle_solve_batch(rl_ctx* ctx, const double* model, int B, int N, const
   const size_t bn = (size_t)B * N, nb_ = bounds_per_instance ? bn : (size_t)N;
   for (size_t i = 0; i < nb_; ++i)
     if (!(dr[i] < dl[i])) return fail(RL_ERR_ARG, "bounds: need dr < dl at every node (min_time_optimizer.py:66-68)");
-  RL_HIP(hipSetDevice(ctx->device));
-  PoolBuf<double> dP0(ctx), dyaw(ctx), ddl(ctx), ddr(ctx), dX(ctx), dU(ctx), dT(ctx), dst(ctx);
-  RL_HIP(dP0.alloc((size_t)2 * N)); RL_HIP(dyaw.alloc(N)); RL_HIP(ddl.alloc(nb_)); RL_HIP(ddr.alloc(nb_));
-  RL_HIP(dX.alloc(bn * 5)); RL_HIP(dU.alloc(bn * 2)); RL_HIP(dT.alloc(bn)); RL_HIP(dst.alloc((size_t)B * 12));
-  auto up = [&](PoolBuf<double>& d, const double* h) { return hipMemcpyAsync(d.p, h, d.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream); };
-  RL_HIP(up(dP0, P0)); RL_HIP(up(dyaw, yaw)); RL_HIP(up(ddl, dl)); RL_HIP(up(ddr, dr));
-  RL_HIP(up(dX, X)); RL_HIP(up(dU, U)); RL_HIP(up(dT, T));
-  const int rc = rl_bicycle_solve_batch_dev(ctx, model, B, N, dP0.p, dyaw.p, ddl.p, ddr.p, bounds_per_instance, dX.p, dU.p,
-                                            dT.p, max_iter, tol, dst.p);
-  if (rc) return rc;
-  RL_HIP(hipMemcpyAsync(X, dX.p, dX.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipMemcpyAsync(U, dU.p, dU.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipMemcpyAsync(T, dT.p, dT.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipMemcpyAsync(stats, dst.p, dst.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipStreamSynchronize(ctx->stream));
-  return RL_OK;
+  Staging sg(ctx);
+  const double *dP0 = sg.in(P0, (size_t)2 * N), *dyaw = sg.in(yaw, N), *ddl = sg.in(dl, nb_), *ddr = sg.in(dr, nb_);
+  double *dX = sg.inout(X, bn * 5), *dU = sg.inout(U, bn * 2), *dT = sg.inout(T, bn);
+  double* dst = sg.out(stats, (size_t)B * 12);
+  sg.run([&] {
+    return rl_bicycle_solve_batch_dev(ctx, model, B, N, dP0, dyaw, ddl, ddr, bounds_per_instance, dX, dU, dT, max_iter, tol, dst);
+  });
+  return sg.finish();
 }
 
 }  // extern "C"
@@ -2011,40 +1603,39 @@ int rl_bicycle_solve_batch(rl_ctx* ctx, const double* model, int B, int N, const
 static int sweep_single(rl_ctx* ctx, rl_track* trk, const int* i_start, int max_iter, double* cx, double* cy,
                         double* points, int* n_success, rl_stats* stats, bool joint) {
   if (!ctx || !trk || !cx || !cy) return fail(RL_ERR_ARG, "null argument");
-  RL_HIP(hipSetDevice(ctx->device));
   const int n = trk->n, N = trk->N;
   if (int rc = rl_track_set_control_points(trk, cx, cy)) return rc;
-  PoolBuf<double> dctrl(ctx), dpts(ctx);
-  PoolBuf<int> dns(ctx), dst(ctx);
-  RL_HIP(dctrl.alloc((size_t)n * 2)); RL_HIP(dpts.alloc((size_t)N * RL_NCOL));
-  RL_HIP(dns.alloc((size_t)2 * (max_iter > 0 ? max_iter : 1))); RL_HIP(dst.alloc(1));
-  RL_HIP(hipMemsetAsync(dpts.p, 0, dpts.n * sizeof(double), ctx->stream));
-  RL_HIP(hipEventRecord(ctx->ev0, ctx->stream));
-  int rc = solve_batch_common(ctx, trk, RL_BOUNDS_SHARED_RINGS, nullptr, 1, i_start, max_iter,
-                              RL_SEARCH_WINDOWED, dctrl.p, nullptr, dpts.p, dns.p, dst.p, stats, nullptr, joint);
-  if (rc) return rc;
-  RL_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-  PoolBuf<double> dseg(ctx), dcx(ctx);
+  std::vector<double> ctrl((size_t)2 * n);
+  std::vector<int> ns_host((size_t)2 * (max_iter > 0 ? max_iter : 1));
+  Staging sg(ctx);
+  double* dctrl = sg.out(ctrl.data(), ctrl.size());
+  double* dpts = sg.out_optional(points, (size_t)N * RL_NCOL);
+  int* dns = sg.out(ns_host.data(), ns_host.size());
+  int* dst = sg.scratch<int>(1);
+  sg.run([&]() -> int {
+    RL_HIP(hipMemsetAsync(dpts, 0, (size_t)N * RL_NCOL * sizeof(double), ctx->stream));
+    return RL_OK;
+  });
+  sg.run_timed([&] {
+    return solve_batch_common(ctx, trk, RL_BOUNDS_SHARED_RINGS, nullptr, 1, i_start, max_iter, RL_SEARCH_WINDOWED, dctrl, nullptr, dpts,
+                              dns, dst, stats, nullptr, joint);
+  });
   if (points && trk->length > 0.0) {
     // DIST_TO_SF_BWD / _FWD of the final table (models/trajectory.py:283-289): GK21 segment lengths of the
     // optimised spline, accumulated in the reference's order; DIST_FWD uses the length the spline object
     // was CONSTRUCTED with (set_control_point never updates _length, trajectory.py:296-298)
-    RL_HIP(dseg.alloc(N)); RL_HIP(dcx.alloc((size_t)2 * n));
-    hipLaunchKernelGGL(rl::k_split_ctrl, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, dctrl.p, n, dcx.p);
-    const dim3 grid((N + 127) / 128), block(128);
-    if (trk->k == 3)
-      hipLaunchKernelGGL(rl::k_sample_geometry<3>, grid, block, 0, ctx->stream, trk->t.p, trk->nt, dcx.p, dcx.p + n, (const double*)nullptr, N, (double*)nullptr, dseg.p);
-    else
-      hipLaunchKernelGGL(rl::k_sample_geometry<5>, grid, block, 0, ctx->stream, trk->t.p, trk->nt, dcx.p, dcx.p + n, (const double*)nullptr, N, (double*)nullptr, dseg.p);
-    hipLaunchKernelGGL(rl::k_sample_cumsum, dim3(1), dim3(64), 0, ctx->stream, dseg.p, N, trk->length, dpts.p);
-    RL_HIP(hipGetLastError());
+    double *dseg = sg.scratch<double>(N), *dcx = sg.scratch<double>((size_t)2 * n);
+    sg.run([&] {
+      if (int rc = launch(ctx, rl::k_split_ctrl, dim3((n + 63) / 64), dim3(64), 0, dctrl, n, dcx)) return rc;
+      if (int rc = by_degree(trk->k, [&](auto kc) {
+            return launch(ctx, rl::k_sample_geometry<RL_DEGREE(kc)>, dim3((N + 127) / 128), dim3(128), 0, trk->t.p, trk->nt, dcx, dcx + n,
+                          nullptr, N, nullptr, dseg);
+          }))
+        return rc;
+      return launch(ctx, rl::k_sample_cumsum, dim3(1), dim3(64), 0, dseg, N, trk->length, dpts);
+    });
   }
-  std::vector<double> ctrl((size_t)2 * n);
-  RL_HIP(hipMemcpyAsync(ctrl.data(), dctrl.p, ctrl.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (points) RL_HIP(hipMemcpyAsync(points, dpts.p, dpts.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  std::vector<int> ns_host((size_t)2 * (max_iter > 0 ? max_iter : 1));
-  RL_HIP(hipMemcpyAsync(ns_host.data(), dns.p, (size_t)2 * max_iter * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  RL_HIP(hipStreamSynchronize(ctx->stream));
+  if (int rc = sg.finish(stats)) return rc;
   for (int j = 0; j < n; ++j) { cx[j] = ctrl[2 * j]; cy[j] = ctrl[2 * j + 1]; }
   if (n_success) {  // sweep: [max_iter][fwd,bwd]; sliding window: [max_iter]
     if (joint) for (int j = 0; j < max_iter; ++j) n_success[j] = ns_host[2 * j];
@@ -2052,11 +1643,6 @@ static int sweep_single(rl_ctx* ctx, rl_track* trk, const int* i_start, int max_
   }
   if (points) {
     for (int i = 0; i < N; ++i) { points[(size_t)i * RL_NCOL + 17] = (double)i; points[(size_t)i * RL_NCOL + 18] = -1.0; }
-  }
-  if (stats) {
-    float ms = 0.f;
-    RL_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    stats->kernel_ms = ms;
   }
   return RL_OK;
 }

@@ -28,7 +28,8 @@ namespace rl {
 // parameter slots (include/rl_mincurv.h: RL_BK_*)
 enum BkParam { BK_LR, BK_L, BK_DELTA_MAX, BK_V_MAX, BK_A_LON_MAX, BK_A_LON_MIN, BK_DELTA_DOT_MAX, BK_ACC_MAX, BK_NPARAM };
 constexpr int kBkNv = 8, kBkNe = 6, kBkNb = 10, kBkK = 14, kBkKK = kBkK * kBkK;
-constexpr int kBkThreads = 256, kBkFilter = 256, kBkScal = 16;
+constexpr int kBkThreads = 256, kBkFilter = 256, kBkScal = 16, kBkStats = 12;   // kBkStats: doubles per instance of the caller's report, scal 0-11
+constexpr int kBkNd = 2, kBkJd = kBkNd * kBkNv;   // the two inequality functions (lateral, traction) and their Jacobian rows
 static_assert(kBkKK <= kBkThreads, "one thread per entry of a 14 x 14 block");
 // the reference's variable scaling (:33-35)
 __device__ constexpr double kBkSx[5] = {10.0, 10.0, 3.14, 0.1, 80.0};
@@ -56,24 +57,30 @@ struct BkProblem {
   double tol;
 };
 
-struct BkState {         // per-instance device arrays, instance-major
+struct BkState {         // per-instance device arrays, instance-major; their shapes are kBkArrays below
   int B, N;
-  double* p;     // [B,N,10] unknowns w (8, scaled) and the slacks of the lateral and traction rows
-  double* yc;    // [B,N,6]  multipliers of the equalities
-  double* yd;    // [B,N,2]  multipliers of (inequality function - slack) = 0
-  double* zl;    // [B,N,10] bound multipliers (0 where the bound is infinite)
-  double* zu;    // [B,N,10]
-  double* D;     // [B,N,196] node KKT blocks before regularisation
-  double* r;     // [B,N,14]  gradient of the Lagrangian w/o bounds (8) and equality values (6), then the Newton rhs
-  double* Dinv;  // [B,N,196] inverses of the pivot blocks
-  double* Tk;    // [B,N,196] border multipliers (block of the last node times Dinv)
-  double* v;     // [B,N,14]  forward-solve values, then the Newton step (dw, dyc)
-  double* Jd;    // [B,N,16]  Jacobian of the two inequality functions
-  double* dcur;  // [B,N,2]   the inequality functions at the current point
-  double* dp;    // [B,N,10]  primal step (unknowns and slacks)
-  double* scal;  // [B,16]
-  double* filt;  // [B,kBkFilter,2]
+  double *p, *yc, *yd, *zl, *zu, *D, *r, *Dinv, *Tk, *v, *Jd, *dcur, *dp, *scal, *filt;
 };
+
+// The one statement of BkState's shapes (StateArray, rl_dtrack.hpp), in the order the host carves them.
+constexpr StateArray<BkState> kBkArrays[] = {
+    {&BkState::p, kBkNb, 0},       // [B,N,10] unknowns w (8, scaled) and the slacks of the lateral and traction rows
+    {&BkState::yc, kBkNe, 0},      // [B,N,6]  multipliers of the equalities
+    {&BkState::yd, kBkNd, 0},      // [B,N,2]  multipliers of (inequality function - slack) = 0
+    {&BkState::zl, kBkNb, 0},      // [B,N,10] bound multipliers (0 where the bound is infinite)
+    {&BkState::zu, kBkNb, 0},      // [B,N,10]
+    {&BkState::D, kBkKK, 0},       // [B,N,196] node KKT blocks before regularisation
+    {&BkState::r, kBkK, 0},        // [B,N,14]  gradient of the Lagrangian w/o bounds (8) and equality values (6), then the Newton rhs
+    {&BkState::Dinv, kBkKK, 0},    // [B,N,196] inverses of the pivot blocks
+    {&BkState::Tk, kBkKK, 0},      // [B,N,196] border multipliers (block of the last node times Dinv)
+    {&BkState::v, kBkK, 0},        // [B,N,14]  forward-solve values, then the Newton step (dw, dyc)
+    {&BkState::Jd, kBkJd, 0},      // [B,N,16]  Jacobian of the two inequality functions
+    {&BkState::dcur, kBkNd, 0},    // [B,N,2]   the inequality functions at the current point
+    {&BkState::dp, kBkNb, 0},      // [B,N,10]  primal step (unknowns and slacks)
+    {&BkState::scal, 0, kBkScal},  // [B,16]    (BS_* above)
+    {&BkState::filt, 0, kBkFilter * 2},   // [B,kBkFilter,2]
+};
+static_assert(sizeof(kBkArrays) / sizeof(kBkArrays[0]) == (sizeof(BkState) - offsetof(BkState, p)) / sizeof(double*), "every array of BkState has its row");
 
 __device__ __forceinline__ double bk_tan(double x) { return tan(x); }
 template <int ND, typename T>
@@ -286,7 +293,7 @@ __device__ __forceinline__ void bk_node_derivs(const BkProblem& P, const BkState
     if (isfinite(lo[i])) { const double gz = (w[i] - lo[i]) * zl[i]; gzmax = fmax(gzmax, gz); gzmin = fmin(gzmin, gz); comp0 = fmax(comp0, fabs(gz)); }
     if (isfinite(hi[i])) { const double gz = (hi[i] - w[i]) * zu[i]; gzmax = fmax(gzmax, gz); gzmin = fmin(gzmin, gz); comp0 = fmax(comp0, fabs(gz)); }
   }
-  for (int k = 0; k < kBkNv; ++k) { st.Jd[n * 16 + k] = Jd[0][k]; st.Jd[n * 16 + 8 + k] = Jd[1][k]; }
+  for (int k = 0; k < kBkNv; ++k) { st.Jd[n * kBkJd + k] = Jd[0][k]; st.Jd[n * kBkJd + 8 + k] = Jd[1][k]; }
   st.dcur[n * 2] = d[0]; st.dcur[n * 2 + 1] = d[1];
   lap += w[7];
 }
@@ -381,7 +388,7 @@ __global__ void __launch_bounds__(kBkThreads) k_bk_iter(BkProblem P, BkState st,
     const double* w = st.p + n * kBkNb;
     const double* zl = st.zl + n * kBkNb;
     const double* zu = st.zu + n * kBkNb;
-    const double* Jd = st.Jd + n * 16;
+    const double* Jd = st.Jd + n * kBkJd;
     double lo[kBkNb], hi[kBkNb], sig[kBkNb], bar[kBkNb];
     bk_bounds(P, b, j, lo, hi);
     for (int i = 0; i < kBkNb; ++i) {
@@ -517,7 +524,7 @@ __global__ void __launch_bounds__(kBkThreads) k_bk_iter(BkProblem P, BkState st,
     const double* w = st.p + n * kBkNb;
     const double* zl = st.zl + n * kBkNb;
     const double* zu = st.zu + n * kBkNb;
-    const double* Jd = st.Jd + n * 16;
+    const double* Jd = st.Jd + n * kBkJd;
     const double* sol = vb + (size_t)j * kBkK;
     double lo[kBkNb], hi[kBkNb], dp[kBkNb];
     bk_bounds(P, b, j, lo, hi);
@@ -642,7 +649,7 @@ __global__ void k_bk_unpack(BkProblem P, BkState st, double* X, double* U, doubl
     for (int i = 2; i < 5; ++i) X[n * 5 + i] = w[i] * kBkSx[i];
     U[n * 2] = w[5] * kBkSu[0]; U[n * 2 + 1] = w[6] * kBkSu[1]; T[n] = w[7];
   }
-  if (blockIdx.x == 0 && threadIdx.x < 12) stats[(size_t)b * 12 + threadIdx.x] = st.scal[(size_t)b * kBkScal + threadIdx.x];
+  if (blockIdx.x == 0 && threadIdx.x < kBkStats) stats[(size_t)b * kBkStats + threadIdx.x] = st.scal[(size_t)b * kBkScal + threadIdx.x];
 }
 
 // functions at a given physical point, one thread per (instance, node): eq [B,N,6], ineq [B,N,2] (lateral coordinate,

@@ -25,6 +25,21 @@ enum DtParam {
 constexpr int kDtNx = 6, kDtNu = 4, kDtNeq = 8, kDtNineq = 14;
 constexpr double kDtGravity = 9.8;  // double_track.py:7
 
+// Shared by the NLP solvers built on this file (rl_mintime.hpp, rl_bicycle.hpp): one row of a state's table of device arrays; array p has B x (N x per_node + per_instance) doubles.
+template <typename S> struct StateArray { double* S::*p; int per_node, per_instance; };
+template <typename S> constexpr size_t state_doubles(const StateArray<S>& a, size_t B, size_t N) { return B * (N * a.per_node + a.per_instance); }
+// all arrays of a batch out of an arena (take<double>(count)), in the order of the table's rows
+template <typename A, typename S, size_t K> void carve(A& arena, S& st, const StateArray<S> (&table)[K], int B, int N) {
+  st.B = B; st.N = N;
+  for (const auto& a : table) st.*a.p = arena.template take<double>(state_doubles(a, B, N));
+}
+// the view of instances [b0, b0 + nb)
+template <typename S, size_t K> S slice(S st, const StateArray<S> (&table)[K], int b0, int nb) {
+  for (const auto& a : table) st.*a.p += state_doubles(a, b0, st.N);
+  st.B = nb;
+  return st;
+}
+
 struct DtArgs {
   double p[DT_NPARAM];
   int B, N;

@@ -1,11 +1,8 @@
 // rl_host.hpp -- host plumbing of rl_mincurv.hip: error reporting, device buffers, the context, and the two helpers every
 // entry point goes through: launch() for one kernel, Staging for the device copies of a host-pointer call.
 //
-// The rules stated here once ("Boundary"):
-//   * a pool block goes back to the pool only when the context's stream is idle (Staging::finish after its
-//     synchronisation; PoolBuf's destructor on an early return);
-//   * after the first failed step of a call nothing further is enqueued -- no copy, no kernel on a block that was never made;
-//   * the timed events bracket the device work handed to Staging::run_timed and nothing else (table builds run before it).
+// The rules they keep -- when a block or the arena is free again, nothing enqueued after a failure, what the timed events
+// bracket, forked streams joined on every exit -- are stated once, in DESIGN section 2 ("Boundary").
 #pragma once
 
 #include "../../include/rl_mincurv.h"
@@ -33,6 +30,7 @@ int fail(int code, const std::string& msg) {
       return fail(RL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));         \
     }                                                                                     \
   } while (0)
+#define RL_TRY(expr) do { if (int _rc = (expr)) return _rc; } while (0)   // a step that returns an rl status: the first failure returns
 
 template <typename T>
 struct DevBuf {
@@ -79,7 +77,7 @@ struct rl_ctx {
   size_t arena_cap = 0;
   // The arena is handed out from offset 0 by every *_dev call, so two calls may only overlap in time if they are
   // ordered on the device: each call records `arena_ev` behind its last use, and a call made after
-  // rl_ctx_set_stream switched to another stream first makes that stream wait for the event (Arena::begin).
+  // rl_ctx_set_stream switched to another stream first makes that stream wait for the event (Arena::carve).
   hipEvent_t arena_ev = nullptr;
   hipStream_t arena_stream = nullptr;
   bool arena_busy = false;       // arena_ev has been recorded at least once
@@ -87,7 +85,6 @@ struct rl_ctx {
   static constexpr int kMaxGroups = 8;
   hipStream_t aux_stream[kMaxGroups - 1] = {};
   hipEvent_t ev_fork = nullptr, ev_join[kMaxGroups - 1] = {};
-  bool mt_poll = false;          // set by the HOST entry point of the min-time solve around its call of the _dev one: poll for early exit
   // the poll never drains the queues: the status words of a chunk of 8 iterations are copied by a side stream into pinned
   // memory while the next chunk is already enqueued, and looked at one chunk later
   hipStream_t poll_stream = nullptr;
@@ -125,14 +122,18 @@ hipError_t grant_dyn_lds(const rl_ctx* ctx, const void* fn, size_t bytes) {
   return r;
 }
 
-// One kernel on the context's stream: the dynamic-LDS grant where the launch asks for any, the launch, its error.  The
+// One kernel on `stream`: the dynamic-LDS grant where the launch asks for any, the launch, its error.  The
 // arguments are converted to the kernel's parameter types (a double* for a const double*, nullptr for a pointer).
 template <typename... P, typename... A>
-int launch(const rl_ctx* ctx, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds_bytes, A&&... args) {
+int launch(const rl_ctx* ctx, hipStream_t stream, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds_bytes, A&&... args) {
   if (lds_bytes > 0) RL_HIP(grant_dyn_lds(ctx, reinterpret_cast<const void*>(kernel), lds_bytes));
-  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, ctx->stream, static_cast<P>(std::forward<A>(args))...);
+  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, static_cast<P>(std::forward<A>(args))...);
   RL_HIP(hipGetLastError());
   return RL_OK;
+}
+template <typename... P, typename... A>
+int launch(const rl_ctx* ctx, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds_bytes, A&&... args) {   // on the context's stream
+  return launch(ctx, ctx->stream, kernel, grid, block, lds_bytes, std::forward<A>(args)...);
 }
 
 // one device staging block from the context's pool (Staging below hands them out)
@@ -268,43 +269,60 @@ class Staging {
   Down down_[kMaxBlocks];
 };
 
-// sequential carve-out of the context's scratch arena; reserve() first with the total
+// Sequential carve-out of the context's scratch arena.  carve() takes the layout as a callable that only calls take(): it runs once to
+// measure (integer offsets, null pointers) and, the total reserved, once to hand out.  From then on leaving the scope records `arena_ev` unless end() already has.
 struct Arena {
-  rl_ctx* ctx; size_t off = 0;
+  rl_ctx* ctx; size_t off = 0; bool open = false;   // open: handing out; before, take() only measures
   explicit Arena(rl_ctx* c) : ctx(c) {}
-  static size_t pad(size_t b) { return (b + 255) & ~(size_t)255; }
-  // order this call behind the previous user of the arena if that one ran on another stream
-  hipError_t begin() {
-    if (!ctx->arena_ev) {
-      const hipError_t e = hipEventCreateWithFlags(&ctx->arena_ev, hipEventDisableTiming);
+  Arena(const Arena&) = delete;
+  ~Arena() { if (open) (void)end(); }
+  template <typename T> T* take(size_t count) {
+    T* p = open ? reinterpret_cast<T*>(static_cast<char*>(ctx->arena) + off) : nullptr;
+    off += (count * sizeof(T) + 255) & ~(size_t)255;
+    return p;
+  }
+  template <typename F> hipError_t carve(F&& layout) {
+    layout(*this);   // then: behind the previous user of the arena if that one ran on another stream, the block grown if need be
+    hipError_t e = ctx->arena_ev ? hipSuccess : hipEventCreateWithFlags(&ctx->arena_ev, hipEventDisableTiming);
+    if (e == hipSuccess && ctx->arena_busy && ctx->arena_stream != ctx->stream) e = hipStreamWaitEvent(ctx->stream, ctx->arena_ev, 0);
+    if (e == hipSuccess && off > ctx->arena_cap) {
+      if (ctx->arena_busy) e = hipEventSynchronize(ctx->arena_ev);   // the last user, whatever its stream
+      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);    // nothing in flight may still use the old block
       if (e != hipSuccess) return e;
+      if (ctx->arena) (void)hipFree(ctx->arena);
+      ctx->arena = nullptr; ctx->arena_cap = 0;
+      if ((e = hipMalloc(&ctx->arena, off)) == hipSuccess) ctx->arena_cap = off;
     }
-    if (ctx->arena_busy && ctx->arena_stream != ctx->stream) return hipStreamWaitEvent(ctx->stream, ctx->arena_ev, 0);
+    if (e != hipSuccess) return e;
+    off = 0; open = true;
+    layout(*this);
     return hipSuccess;
   }
-  // record "the arena is free again once everything enqueued so far on the context's stream has run"
-  hipError_t end() {
+  hipError_t end() {   // record "the arena is free again once everything enqueued so far on the context's stream has run"
+    open = false;
     const hipError_t e = hipEventRecord(ctx->arena_ev, ctx->stream);
     if (e == hipSuccess) { ctx->arena_busy = true; ctx->arena_stream = ctx->stream; }
     return e;
   }
-  hipError_t reserve(size_t bytes) {
-    hipError_t e = begin();
-    if (e != hipSuccess) return e;
-    if (bytes <= ctx->arena_cap) return hipSuccess;
-    if (ctx->arena_busy) { e = hipEventSynchronize(ctx->arena_ev); if (e != hipSuccess) return e; }   // the last user, whatever its stream
-    e = hipStreamSynchronize(ctx->stream);                     // nothing in flight may still use the old block
-    if (e != hipSuccess) return e;
-    if (ctx->arena) (void)hipFree(ctx->arena);
-    ctx->arena = nullptr; ctx->arena_cap = 0;
-    e = hipMalloc(&ctx->arena, bytes);
-    if (e == hipSuccess) ctx->arena_cap = bytes;
-    return e;
+};
+
+// The context's stream (g = 0) and the auxiliary streams a call forked from it: join_streams() makes the context's stream
+// continue behind everything enqueued on them; every stream is tried once, the first error returned.
+inline hipStream_t fork_stream(const rl_ctx* ctx, int g) { return g == 0 ? ctx->stream : ctx->aux_stream[g - 1]; }
+inline hipError_t join_streams(rl_ctx* ctx, int n) {
+  hipError_t first = hipSuccess;
+  for (int g = 1; g < n; ++g) {
+    hipError_t e = hipEventRecord(ctx->ev_join[g - 1], fork_stream(ctx, g));
+    if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->ev_join[g - 1], 0);
+    if (first == hipSuccess) first = e;
   }
-  template <typename T> T* take(size_t count) {
-    T* p = reinterpret_cast<T*>(static_cast<char*>(ctx->arena) + off);
-    off += pad(count * sizeof(T));
-    return p;
-  }
+  return first;
+}
+// After a fork every exit joins and waits for the poll stream if a copy into the pinned buffer may be in flight; the success
+// path does both itself and clears the members.  Declared AFTER the Arena, so that the arena's event is recorded behind all of it.
+struct StreamFork {
+  rl_ctx* ctx; int n = 1; bool polled = false;
+  StreamFork(const StreamFork&) = delete;
+  ~StreamFork() { (void)join_streams(ctx, n); if (polled) (void)hipStreamSynchronize(ctx->poll_stream); }
 };
 }  // namespace

@@ -971,10 +971,12 @@ static int region_launch(rl_ctx* ctx, const double* xy, long long stride, long l
     box[4 * r] = x0; box[4 * r + 1] = y0; box[4 * r + 2] = x1; box[4 * r + 3] = y1;
   }
   Arena ar(ctx);
-  RL_HIP(ar.reserve(Arena::pad(box.size() * 8) + Arena::pad((size_t)V * 16) + Arena::pad((size_t)(R + 1) * 4) +
-                    Arena::pad((size_t)R * 4)));
-  double* dbox = ar.take<double>(box.size()); double* dv = ar.take<double>((size_t)2 * V);
-  int* doff = ar.take<int>(R + 1); int* dcode = ar.take<int>(R);
+  double *dbox = nullptr, *dv = nullptr;
+  int *doff = nullptr, *dcode = nullptr;
+  RL_HIP(ar.carve([&](Arena& x) {
+    dbox = x.take<double>(box.size()); dv = x.take<double>((size_t)2 * V);
+    doff = x.take<int>(R + 1); dcode = x.take<int>(R);
+  }));
   RL_HIP(hipMemcpyAsync(dbox, box.data(), box.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   RL_HIP(hipMemcpyAsync(dv, verts, (size_t)2 * V * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   RL_HIP(hipMemcpyAsync(doff, offsets, (size_t)(R + 1) * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
@@ -983,9 +985,8 @@ static int region_launch(rl_ctx* ctx, const double* xy, long long stride, long l
   a.xy = xy; a.stride = stride; a.n = n;
   a.verts = reinterpret_cast<const double2*>(dv); a.offsets = doff; a.box = reinterpret_cast<const double4*>(dbox); a.R = R;
   a.out = out; a.codes = dcode; a.tag = tag; a.tag_stride = tag_stride;
-  if (int rc = launch(ctx, rl::k_region_index, dim3((unsigned)((n + rl::kRegionBlock - 1) / rl::kRegionBlock)),
-                      dim3(rl::kRegionBlock), 0, a))
-    return rc;
+  RL_TRY(launch(ctx, rl::k_region_index, dim3((unsigned)((n + rl::kRegionBlock - 1) / rl::kRegionBlock)),
+                dim3(rl::kRegionBlock), 0, a));
   RL_HIP(ar.end());
   return RL_OK;
 }
@@ -1039,20 +1040,22 @@ int rl_qss_sim_dev(rl_ctx* ctx, double* points, int B, int N, const double* acc_
   const int tab_n = (acc_m + 1) + 4 * acc_m + (dcc_m + 1) + 4 * dcc_m;
   const bool by_value = tab_n <= rl::kQssTabMax;
   Arena ar(ctx);
-  RL_HIP(ar.reserve((by_value ? 0 : Arena::pad((acc_m + 1) * 8) + Arena::pad((size_t)4 * acc_m * 8) + Arena::pad((dcc_m + 1) * 8) +
-                                    Arena::pad((size_t)4 * dcc_m * 8)) +
-                    Arena::pad((size_t)B * cap * 5 * 4) + Arena::pad((size_t)B * cap * 4) + Arena::pad((size_t)B * 3 * N * 8)));
-  double *dax = nullptr, *dac = nullptr, *ddx = nullptr, *ddc = nullptr;
+  double *dax = nullptr, *dac = nullptr, *ddx = nullptr, *ddc = nullptr, *dcst = nullptr;
+  int *dfl = nullptr, *dnw = nullptr;
+  RL_HIP(ar.carve([&](Arena& x) {
+    if (!by_value) {
+      dax = x.take<double>(acc_m + 1); dac = x.take<double>((size_t)4 * acc_m);
+      ddx = x.take<double>(dcc_m + 1); ddc = x.take<double>((size_t)4 * dcc_m);
+    }
+    dfl = x.take<int>((size_t)B * cap * 5); dnw = x.take<int>((size_t)B * cap);
+    dcst = x.take<double>((size_t)B * 3 * N);
+  }));
   if (!by_value) {
-    dax = ar.take<double>(acc_m + 1); dac = ar.take<double>((size_t)4 * acc_m);
-    ddx = ar.take<double>(dcc_m + 1); ddc = ar.take<double>((size_t)4 * dcc_m);
     RL_HIP(hipMemcpyAsync(dax, acc_x, (acc_m + 1) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     RL_HIP(hipMemcpyAsync(dac, acc_c, (size_t)4 * acc_m * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     RL_HIP(hipMemcpyAsync(ddx, dcc_x, (dcc_m + 1) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     RL_HIP(hipMemcpyAsync(ddc, dcc_c, (size_t)4 * dcc_m * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   }
-  int* dfl = ar.take<int>((size_t)B * cap * 5); int* dnw = ar.take<int>((size_t)B * cap);
-  double* dcst = ar.take<double>((size_t)B * 3 * N);
   rl::QssArgs a;
   a.points = points; a.B = B; a.N = N;
   a.acc_x = dax; a.acc_c = dac; a.acc_m = acc_m;
@@ -1096,10 +1099,9 @@ int rl_qss_sim_dev(rl_ctx* ctx, double* points, int B, int N, const double* acc_
 #endif
     // waves of the (one) workgroup an instance's tables leave room for: four is the fastest at every size measured
     // (DESIGN_HISTORY.md 3c); one and two exist for the tests (rl_ctx_set_option "qss_df_waves")
-    if (int rc = ctx->qss_df_waves == 1   ? launch(ctx, rl::k_qss_dfw<1>, dim3(B), dim3(64), lds_df, a)
-                 : ctx->qss_df_waves == 2 ? launch(ctx, rl::k_qss_dfw<2>, dim3(B), dim3(128), lds_df, a)
-                                          : launch(ctx, rl::k_qss_dfw<4>, dim3(B), dim3(256), lds_df, a))
-      return rc;
+    RL_TRY(ctx->qss_df_waves == 1   ? launch(ctx, rl::k_qss_dfw<1>, dim3(B), dim3(64), lds_df, a)
+           : ctx->qss_df_waves == 2 ? launch(ctx, rl::k_qss_dfw<2>, dim3(B), dim3(128), lds_df, a)
+                                    : launch(ctx, rl::k_qss_dfw<4>, dim3(B), dim3(256), lds_df, a));
     if (ddbg) {   // diagnostic build only: synchronous
       std::vector<int> hd((size_t)B * 12);
       RL_HIP(hipStreamSynchronize(ctx->stream));
@@ -1115,7 +1117,7 @@ int rl_qss_sim_dev(rl_ctx* ctx, double* points, int B, int N, const double* acc_
     }
     a.redo = 1;
   }
-  if (int rc = launch(ctx, rl::k_qss_sim, dim3(B), dim3(64), lds, a)) return rc;
+  RL_TRY(launch(ctx, rl::k_qss_sim, dim3(B), dim3(64), lds, a));
   RL_HIP(ar.end());
   return RL_OK;
 }
@@ -1167,15 +1169,13 @@ int rl_tables_batch_dev(rl_ctx* ctx, const rl_track* trk, const double* ctrl, in
   Arena ar(ctx);
   if (!rings_lds) {
     a.gscratch_stride = rl::tables_ring_scratch_doubles(a.nL, a.nR);
-    RL_HIP(ar.reserve(Arena::pad(a.gscratch_stride * (size_t)B * sizeof(double))));
-    a.gscratch = ar.take<double>(a.gscratch_stride * (size_t)B);
+    RL_HIP(ar.carve([&](Arena& x) { a.gscratch = x.take<double>(a.gscratch_stride * (size_t)B); }));
   }
-  if (int rc = by_degree(k, [&](auto kc) {
-        constexpr int K = RL_DEGREE(kc);
-        const dim3 grid(B), block(rl::kTablesThreads);
-        return rings_lds ? launch(ctx, rl::k_tables<K, true>, grid, block, lds, a) : launch(ctx, rl::k_tables<K, false>, grid, block, lds, a);
-      }))
-    return rc;
+  RL_TRY(by_degree(k, [&](auto kc) {
+    constexpr int K = RL_DEGREE(kc);
+    const dim3 grid(B), block(rl::kTablesThreads);
+    return rings_lds ? launch(ctx, rl::k_tables<K, true>, grid, block, lds, a) : launch(ctx, rl::k_tables<K, false>, grid, block, lds, a);
+  }));
   if (!rings_lds) RL_HIP(ar.end());
   return RL_OK;
 }
@@ -1274,10 +1274,71 @@ int rl_dt_eval_jac(rl_ctx* ctx, const double* model, int B, int N, const double*
   return sg.finish();
 }
 
-int rl_mintime_solve_batch_dev(rl_ctx* ctx, const double* model, int B, int N, const double* s, const double* kappa,
-                               const double* left, const double* right, int bounds_per_instance, double margin,
-                               double track_length, double average_track_width, double speed_cap, double* X, double* U,
-                               double* T, int max_iter, double tol, double* stats) {
+// ---- the min-time double-track NLP (rl_mintime.hpp)
+namespace {
+// A sub-batch: its stream, its views of the problem, the state and the caller's arrays, the grids most kernels share (y: the instance).
+struct MtGroup { hipStream_t q; rl::MtProblem P; rl::MtState st; double *X, *U, *T, *stats; dim3 rows, per_node, per_inst; };
+using MtKernel = void (*)(rl::MtProblem, rl::MtState);
+int mt_run(const rl_ctx* ctx, const MtGroup& G, MtKernel kernel, dim3 grid, int threads) {
+  return launch(ctx, G.q, kernel, grid, dim3(threads), 0, G.P, G.st);
+}
+
+// One iteration of one group on its stream; finished instances return at once from every kernel.  Three pipelines: the
+// default (k_mt_node), and the cross-checks RL_MT_HES_SWEEP=1 / RL_MT_UNFUSED=1 with the separate assembly kernels.
+int mt_enqueue_iteration(const rl_ctx* ctx, const MtGroup& G) {
+  const int N = G.P.N, nb = G.st.B;
+  if (ctx->mt_hes_sweep) {   // cross-check: forward (over forward) duals through the whole pair function
+    RL_TRY(mt_run(ctx, G, rl::k_mt_derivs<0>, G.rows, 64));
+    RL_TRY(mt_run(ctx, G, rl::k_mt_derivs<1>, dim3(G.rows.x, nb, rl::kMtJacSlices), 64));
+    RL_TRY(mt_run(ctx, G, rl::k_mt_derivs<2>, dim3(G.rows.x, nb, rl::kMtHesSlices), 64));
+  } else {
+    RL_TRY(mt_run(ctx, G, rl::k_mt_values, G.rows, 64));   // functions; values of the dynamics at the two ends -> midpoint
+    RL_TRY(mt_run(ctx, G, rl::k_mt_jac_dirs, dim3(rl::mt_jac_blocks(N), nb, 3), 64));
+    if (ctx->mt_unfused) RL_TRY(mt_run(ctx, G, rl::k_mt_jac_assemble, G.per_node, 64));
+    RL_TRY(mt_run(ctx, G, rl::k_mt_hes_point<0>, dim3(rl::mt_hes_blocks(N), nb, 1), 64));
+    RL_TRY(mt_run(ctx, G, rl::k_mt_hes_point<1>, dim3(rl::mt_hes_blocks(N), nb, 2), 64));
+    if (ctx->mt_unfused) {
+      RL_TRY(mt_run(ctx, G, rl::k_mt_hes_assemble, G.per_node, 64));
+    } else {   // Jacobian, Hessian, blocks and right-hand side in one pass over the pairs
+      RL_TRY(mt_run(ctx, G, rl::k_mt_node, dim3(rl::mt_node_blocks(N), nb), 64));
+      RL_TRY(mt_run(ctx, G, rl::k_mt_prepare2, G.per_inst, 256));
+    }
+  }
+  if (ctx->mt_hes_sweep || ctx->mt_unfused) {
+    RL_TRY(mt_run(ctx, G, rl::k_mt_prepare, G.per_inst, 64));
+    RL_TRY(mt_run(ctx, G, rl::k_mt_assemble, G.per_node, 64));
+    RL_TRY(mt_run(ctx, G, rl::k_mt_gc_pack, G.per_node, 64));
+  }
+  if (ctx->mt_kkt4 && N >= 64) RL_TRY(mt_run(ctx, G, rl::k_mt_kkt4, G.per_inst, 256));
+  else RL_TRY(mt_run(ctx, G, rl::k_mt_kkt, G.per_inst, 128));
+  RL_TRY(mt_run(ctx, G, rl::k_mt_dir, dim3(rl::kMtDirBlocks(N), nb), 64));
+  RL_TRY(mt_run(ctx, G, rl::k_mt_trial, G.rows, 64));
+  RL_TRY(mt_run(ctx, G, rl::k_mt_step, G.per_inst, 256));
+  RL_TRY(mt_run(ctx, G, rl::k_mt_trial_b, G.rows, 64));        // halvings of the instances whose first trial point was rejected
+  return mt_run(ctx, G, rl::k_mt_step_b, G.per_inst, 256);
+}
+
+// the closing pass of one group: final residuals of the instances still running (status 0 = iteration limit), the caller's arrays, the report
+int mt_enqueue_closing(const rl_ctx* ctx, const MtGroup& G) {
+  const int N = G.P.N, nb = G.st.B;
+  RL_TRY(mt_run(ctx, G, rl::k_mt_derivs<0>, G.rows, 64));
+  if (ctx->mt_hes_sweep) {
+    RL_TRY(mt_run(ctx, G, rl::k_mt_derivs<1>, dim3(G.rows.x, nb, rl::kMtJacSlices), 64));
+  } else {
+    RL_TRY(mt_run(ctx, G, rl::k_mt_hes_values, G.rows, 64));
+    RL_TRY(mt_run(ctx, G, rl::k_mt_jac_dirs, dim3(rl::mt_jac_blocks(N), nb, 3), 64));
+    RL_TRY(mt_run(ctx, G, rl::k_mt_jac_assemble, G.per_node, 64));
+  }
+  RL_TRY(mt_run(ctx, G, rl::k_mt_residuals, G.per_inst, 64));
+  RL_TRY(launch(ctx, G.q, rl::k_mt_unpack, G.rows, dim3(64), 0, G.P, G.st, G.X, G.U, G.T));
+  return launch(ctx, G.q, rl::k_mt_stats, dim3((nb + 63) / 64), dim3(64), 0, G.st, G.stats);
+}
+
+// Both entry points of the solve, on device pointers.  poll: stop enqueueing once every instance has finished (the host
+// entry point, which synchronises anyway); without it all max_iter iterations are enqueued and the call does not wait.
+int mintime_solve_common(rl_ctx* ctx, const double* model, int B, int N, const double* s, const double* kappa, const double* left,
+                         const double* right, int bounds_per_instance, double margin, double track_length, double average_track_width,
+                         double speed_cap, double* X, double* U, double* T, int max_iter, double tol, double* stats, bool poll) {
   if (!ctx || !model || !s || !kappa || !left || !right || !X || !U || !T || !stats) return fail(RL_ERR_ARG, "null argument");
   if (B <= 0 || N < 8 || !(track_length > 0.0) || max_iter < 1 || !(tol > 0.0)) return fail(RL_ERR_ARG, "bad sizes (N >= 8 nodes)");
   if (!(average_track_width > 0.0) || !(speed_cap > 0.0)) return fail(RL_ERR_ARG, "bad scales");
@@ -1295,153 +1356,81 @@ int rl_mintime_solve_batch_dev(rl_ctx* ctx, const double* model, int B, int N, c
   for (int c = 0; c < 6; ++c) P.se[c] = 1.0 / sx[c];
   P.se[6] = 1.0 / su[3];
   P.s = s; P.kappa = kappa; P.left = left; P.right = right;
-  const size_t bn = (size_t)B * N;
-  const size_t counts[] = {bn * rl::kMtNv, bn * rl::kMtNi, bn * rl::kMtNe, bn * rl::kMtNi, bn * rl::kMtNf,
-                           bn * rl::kMtNf * rl::kMtLoc, bn * rl::kMtLoc * rl::kMtLoc, bn * rl::kMtNv, bn * rl::kMtNe,
-                           bn * 3 * 256, bn * 16, (size_t)B * 16, bn * 256, bn * 256, bn * 16, (size_t)B * 2 * rl::kMtFilter, bn * rl::kMtHw, bn * 16, bn * rl::kMtGc};
-  size_t total = 0;
-  for (size_t c : counts) total += Arena::pad(c * sizeof(double));
   Arena ar(ctx);
-  RL_HIP(ar.reserve(total));
   rl::MtState st;
-  st.B = B; st.N = N;
-  st.w = ar.take<double>(counts[0]); st.s = ar.take<double>(counts[1]); st.y = ar.take<double>(counts[2]);
-  st.z = ar.take<double>(counts[3]); st.fun = ar.take<double>(counts[4]); st.jac = ar.take<double>(counts[5]);
-  st.hes = ar.take<double>(counts[6]); st.dw = ar.take<double>(counts[7]); st.dy = ar.take<double>(counts[8]);
-  st.blk = ar.take<double>(counts[9]); st.vec = ar.take<double>(counts[10]); st.scal = ar.take<double>(counts[11]);
-  st.dblk = ar.take<double>(counts[12]); st.eblk = ar.take<double>(counts[13]); st.rhs = ar.take<double>(counts[14]);
-  st.filt = ar.take<double>(counts[15]); st.hw = ar.take<double>(counts[16]); st.r1 = ar.take<double>(counts[17]); st.gc = ar.take<double>(counts[18]);
+  RL_HIP(ar.carve([&](Arena& x) { rl::carve(x, st, rl::kMtArrays, B, N); }));
   st.tol = tol;
-
-  double mt_mu0, mt_delta0;
-  {
-    // Strategy constants of the line search / barrier update.  Measured on 1024 width-perturbed MGKT tracks:
-    // (d_up, a_lo, mu_kappa) = (5, 0.3, 10) 96.5 iterations on average, (3, 0.2, 30) 77.8 (round 2).  Round 4: the damping
-    // delta came down only after a step longer than a_hi = 0.9 -- but for dozens of iterations per barrier problem the
-    // step is cut by the fraction-to-the-boundary rule to 0.3 .. 0.5 and accepted without a halving (iteration history,
-    // tools/mintime_history.py), so delta stayed at 0.5 and the iteration crawled.  (a_hi, a_lo) = (0.25, 0.1): 82.1 -> 55.9
-    // iterations on the benchmark batch, the same optima (lap times equal to 1e-12), 89.4 -> 66.8 on the 768 instances of
-    // tools/mintime_robustness.py, all converged; a plateau: a_hi 0.11 .. 0.25, a_lo 0.05 .. 0.1, d_down 0.2 .. 0.5, d_up 2 .. 3 all
-    // give 55 .. 57.  mu_kappa 60 or mu0 0.05 would take off three more; left alone.  They are COMPILE-TIME constants of the
-    // product; only a diagnostic build (hipcc -DRL_ABLATION) reads RL_MT_* overrides from the environment.
+  // Strategy constants of the line search / barrier update.  Measured on 1024 width-perturbed MGKT tracks:
+  // (d_up, a_lo, mu_kappa) = (5, 0.3, 10) 96.5 iterations on average, (3, 0.2, 30) 77.8 (round 2).  Round 4: the damping
+  // delta came down only after a step longer than a_hi = 0.9 -- but for dozens of iterations per barrier problem the
+  // step is cut by the fraction-to-the-boundary rule to 0.3 .. 0.5 and accepted without a halving (iteration history,
+  // tools/mintime_history.py), so delta stayed at 0.5 and the iteration crawled.  (a_hi, a_lo) = (0.25, 0.1): 82.1 -> 55.9
+  // iterations on the benchmark batch, the same optima (lap times equal to 1e-12), 89.4 -> 66.8 on the 768 instances of
+  // tools/mintime_robustness.py, all converged; a plateau: a_hi 0.11 .. 0.25, a_lo 0.05 .. 0.1, d_down 0.2 .. 0.5, d_up 2 .. 3 all
+  // give 55 .. 57.  mu_kappa 60 or mu0 0.05 would take off three more; left alone.  They are COMPILE-TIME constants of the
+  // product; only a diagnostic build (hipcc -DRL_ABLATION) reads RL_MT_* overrides from the environment.
 #ifdef RL_ABLATION
-    auto knob = [](const char* name, double dflt) { const char* v = getenv(name); return v ? atof(v) : dflt; };
+  auto knob = [](const char* name, double dflt) { const char* v = getenv(name); return v ? atof(v) : dflt; };
 #else
-    auto knob = [](const char*, double dflt) { return dflt; };
+  auto knob = [](const char*, double dflt) { return dflt; };
 #endif
-    st.d_down = knob("RL_MT_D_DOWN", 0.4); st.d_up = knob("RL_MT_D_UP", 3.0);
-    st.a_hi = knob("RL_MT_A_HI", 0.25); st.a_lo = knob("RL_MT_A_LO", 0.1);
-    st.mu_fac = knob("RL_MT_MU_FAC", 0.2); st.mu_pow = knob("RL_MT_MU_POW", 1.5); st.mu_kappa = knob("RL_MT_MU_KAPPA", 30.0);
-    // dual step length <= dual_cap x primal step length (0 = uncoupled): with 1 all 768 instances of tools/mintime_robustness.py
-    // converge (750 uncoupled: the multipliers ran away while the primal step was cut to a few per cent), at 82 instead of 78
-    // iterations on the benchmark batch
-    st.dual_cap = knob("RL_MT_DUAL_CAP", 1.0);
-    st.th_filter = knob("RL_MT_TH_FILTER", 1e-4);   // 2e-5 .. 1e-3 all converge for mu0 = 0.05, 0.1, 0.2; 1e-2 blocks the early phase
-    mt_mu0 = knob("RL_MT_MU0", 1e-1); mt_delta0 = knob("RL_MT_DELTA0", 1e-4);
-  }
-  RL_HIP(hipMemsetAsync(st.scal, 0, counts[11] * sizeof(double), ctx->stream));
-  if (ctx->mt_hes_sweep) RL_HIP(hipMemsetAsync(st.hes, 0, counts[6] * sizeof(double), ctx->stream));
+  st.d_down = knob("RL_MT_D_DOWN", 0.4); st.d_up = knob("RL_MT_D_UP", 3.0);
+  st.a_hi = knob("RL_MT_A_HI", 0.25); st.a_lo = knob("RL_MT_A_LO", 0.1);
+  st.mu_fac = knob("RL_MT_MU_FAC", 0.2); st.mu_pow = knob("RL_MT_MU_POW", 1.5); st.mu_kappa = knob("RL_MT_MU_KAPPA", 30.0);
+  // dual step length <= dual_cap x primal step length (0 = uncoupled): with 1 all 768 instances of tools/mintime_robustness.py
+  // converge (750 uncoupled: the multipliers ran away while the primal step was cut to a few per cent), at 82 instead of 78
+  // iterations on the benchmark batch
+  st.dual_cap = knob("RL_MT_DUAL_CAP", 1.0);
+  st.th_filter = knob("RL_MT_TH_FILTER", 1e-4);   // 2e-5 .. 1e-3 all converge for mu0 = 0.05, 0.1, 0.2; 1e-2 blocks the early phase
+  const double mt_mu0 = knob("RL_MT_MU0", 1e-1), mt_delta0 = knob("RL_MT_DELTA0", 1e-4);
+  const size_t nscal = (size_t)B * rl::kMtScal;
+  RL_HIP(hipMemsetAsync(st.scal, 0, nscal * sizeof(double), ctx->stream));
+  if (ctx->mt_hes_sweep) RL_HIP(hipMemsetAsync(st.hes, 0, (size_t)B * N * rl::kMtLoc * rl::kMtLoc * sizeof(double), ctx->stream));
   // A few sub-batches on as many streams: the KKT elimination is one wave per instance and latency bound (its time
   // does not depend on the batch), the derivative kernels are throughput bound -- with the sub-batches offset by the
   // in-order queues one's elimination runs beside another's derivatives.  Instances are independent, so the split
   // changes no result.  The extra streams fork from / join into the context's stream with events:
   // for the caller everything is still "enqueued on the context's stream".
   const int ngrp = B >= 4 * ctx->mt_groups ? ctx->mt_groups : 1;
-  for (int g = 0; g + 1 < ngrp; ++g) {
-    if (!ctx->aux_stream[g]) {
-      RL_HIP(hipStreamCreateWithFlags(&ctx->aux_stream[g], hipStreamNonBlocking));
-      RL_HIP(hipEventCreateWithFlags(&ctx->ev_join[g], hipEventDisableTiming));
-    }
-  }
-  if (ngrp > 1 && !ctx->ev_fork) RL_HIP(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-  struct Grp { int b0, nb; rl::MtProblem P; rl::MtState st; hipStream_t q; double *X, *U, *T, *stats; };
-  Grp grp[rl_ctx::kMaxGroups];
-  for (int g = 0; g < ngrp; ++g) {
-    Grp& G = grp[g];
-    G.b0 = (int)((long long)B * g / ngrp);
-    G.nb = (int)((long long)B * (g + 1) / ngrp) - G.b0;
-    G.q = g == 0 ? ctx->stream : ctx->aux_stream[g - 1];
-    const size_t o = (size_t)G.b0 * N;
-    G.P = P;
-    if (P.bounds_per_instance) { G.P.left = left + o; G.P.right = right + o; }
-    G.st = st; G.st.B = G.nb;
-    G.st.w = st.w + o * rl::kMtNv; G.st.s = st.s + o * rl::kMtNi; G.st.y = st.y + o * rl::kMtNe; G.st.z = st.z + o * rl::kMtNi;
-    G.st.fun = st.fun + o * rl::kMtNf; G.st.jac = st.jac + o * rl::kMtNf * rl::kMtLoc; G.st.hes = st.hes + o * rl::kMtLoc * rl::kMtLoc;
-    G.st.dw = st.dw + o * rl::kMtNv; G.st.dy = st.dy + o * rl::kMtNe; G.st.blk = st.blk + o * 3 * 256; G.st.vec = st.vec + o * 16;
-    G.st.scal = st.scal + (size_t)G.b0 * 16; G.st.filt = st.filt + (size_t)G.b0 * 2 * rl::kMtFilter; G.st.hw = st.hw + o * rl::kMtHw; G.st.dblk = st.dblk + o * 256; G.st.eblk = st.eblk + o * 256; G.st.rhs = st.rhs + o * 16; G.st.r1 = st.r1 + o * 16; G.st.gc = st.gc + o * rl::kMtGc;
-    G.X = X + o * 6; G.U = U + o * 4; G.T = T + o; G.stats = stats + (size_t)G.b0 * 12;
-  }
-  if (ngrp > 1) {   // fork: the other streams start after everything already enqueued on the first
-    RL_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
-    for (int g = 1; g < ngrp; ++g) RL_HIP(hipStreamWaitEvent(grp[g].q, ctx->ev_fork, 0));
-  }
-  auto join = [&]() -> hipError_t {   // the first stream continues after everything enqueued on the others
-    for (int g = 1; g < ngrp; ++g) {
-      hipError_t e = hipEventRecord(ctx->ev_join[g - 1], grp[g].q);
-      if (e != hipSuccess) return e;
-      e = hipStreamWaitEvent(ctx->stream, ctx->ev_join[g - 1], 0);
-      if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-  };
-  const dim3 bn64(64);
-  for (int g = 0; g < ngrp; ++g) {
-    const Grp& G = grp[g];
-    const dim3 gn((N + 63) / 64, G.nb);
-    hipLaunchKernelGGL(rl::k_mt_pack, gn, bn64, 0, G.q, G.P, G.st, (const double*)G.X, (const double*)G.U, (const double*)G.T);
-    hipLaunchKernelGGL(rl::k_mt_derivs<0>, gn, bn64, 0, G.q, G.P, G.st);
-    hipLaunchKernelGGL(rl::k_mt_init, dim3((N * rl::kMtNi + 255) / 256, G.nb), dim3(256), 0, G.q, G.P, G.st, mt_mu0, mt_delta0);
-  }
-  RL_HIP(hipGetLastError());
-  if (ctx->mt_poll) {
-    if (!ctx->poll_stream) RL_HIP(hipStreamCreateWithFlags(&ctx->poll_stream, hipStreamNonBlocking));
-    for (int g = 0; g < ngrp; ++g)
-      if (!ctx->ev_chunk[g]) RL_HIP(hipEventCreateWithFlags(&ctx->ev_chunk[g], hipEventDisableTiming));
-    for (auto& e : ctx->ev_poll)
-      if (!e) RL_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (ctx->poll_cap < (size_t)B * 16) {
+  auto stream = [](hipStream_t& q) { return q ? hipSuccess : hipStreamCreateWithFlags(&q, hipStreamNonBlocking); };
+  auto event = [](hipEvent_t& e) { return e ? hipSuccess : hipEventCreateWithFlags(&e, hipEventDisableTiming); };
+  for (int g = 0; g + 1 < ngrp; ++g) { RL_HIP(stream(ctx->aux_stream[g])); RL_HIP(event(ctx->ev_join[g])); }
+  if (ngrp > 1) RL_HIP(event(ctx->ev_fork));
+  if (poll) {   // what the poll keeps on the context: its stream, its events, the pinned buffer of two slots
+    RL_HIP(stream(ctx->poll_stream));
+    for (int g = 0; g < ngrp; ++g) RL_HIP(event(ctx->ev_chunk[g]));
+    for (auto& e : ctx->ev_poll) RL_HIP(event(e));
+    if (ctx->poll_cap < nscal) {
       if (ctx->poll_host) RL_HIP(hipHostFree(ctx->poll_host));
       ctx->poll_host = nullptr; ctx->poll_cap = 0;
-      RL_HIP(hipHostMalloc(reinterpret_cast<void**>(&ctx->poll_host), 2 * (size_t)B * 16 * sizeof(double), hipHostMallocDefault));
-      ctx->poll_cap = (size_t)B * 16;
+      RL_HIP(hipHostMalloc(reinterpret_cast<void**>(&ctx->poll_host), 2 * nscal * sizeof(double), hipHostMallocDefault));
+      ctx->poll_cap = nscal;
     }
   }
-  for (int it = 0; it < max_iter; ++it) {   // finished instances return at once from every kernel
-    for (int g = 0; g < ngrp; ++g) {
-      const Grp& G = grp[g];
-      const dim3 gn((N + 63) / 64, G.nb);
-      if (ctx->mt_hes_sweep) {   // cross-check: forward (over forward) duals through the whole pair function
-        hipLaunchKernelGGL(rl::k_mt_derivs<0>, gn, bn64, 0, G.q, G.P, G.st);
-        hipLaunchKernelGGL(rl::k_mt_derivs<1>, dim3((N + 63) / 64, G.nb, rl::kMtJacSlices), bn64, 0, G.q, G.P, G.st);
-        hipLaunchKernelGGL(rl::k_mt_derivs<2>, dim3((N + 63) / 64, G.nb, rl::kMtHesSlices), bn64, 0, G.q, G.P, G.st);
-      } else {
-        hipLaunchKernelGGL(rl::k_mt_values, gn, bn64, 0, G.q, G.P, G.st);   // functions; values of the dynamics at the two ends -> midpoint
-        hipLaunchKernelGGL(rl::k_mt_jac_dirs, dim3((N + rl::kMtJacNodes - 1) / rl::kMtJacNodes, G.nb, 3), bn64, 0, G.q, G.P, G.st);
-        if (ctx->mt_unfused) hipLaunchKernelGGL(rl::k_mt_jac_assemble, dim3(N, G.nb), bn64, 0, G.q, G.P, G.st);
-        hipLaunchKernelGGL(rl::k_mt_hes_point<0>, dim3(rl::mt_hes_blocks(N), G.nb, 1), bn64, 0, G.q, G.P, G.st);
-        hipLaunchKernelGGL(rl::k_mt_hes_point<1>, dim3(rl::mt_hes_blocks(N), G.nb, 2), bn64, 0, G.q, G.P, G.st);
-        if (ctx->mt_unfused) {
-          hipLaunchKernelGGL(rl::k_mt_hes_assemble, dim3(N, G.nb), bn64, 0, G.q, G.P, G.st);
-        } else {   // Jacobian, Hessian, blocks and right-hand side in one pass over the pairs
-          hipLaunchKernelGGL(rl::k_mt_node, dim3(((N + rl::kMtRun - 1) / rl::kMtRun + rl::kMtNodeGroups - 1) / rl::kMtNodeGroups, G.nb), bn64, 0, G.q, G.P, G.st);
-          hipLaunchKernelGGL(rl::k_mt_prepare2, dim3(G.nb), dim3(256), 0, G.q, G.P, G.st);
-        }
-      }
-      if (ctx->mt_hes_sweep || ctx->mt_unfused) {
-        hipLaunchKernelGGL(rl::k_mt_prepare, dim3(G.nb), dim3(64), 0, G.q, G.P, G.st);
-        hipLaunchKernelGGL(rl::k_mt_assemble, dim3(N, G.nb), dim3(64), 0, G.q, G.P, G.st);
-        hipLaunchKernelGGL(rl::k_mt_gc_pack, dim3(N, G.nb), dim3(64), 0, G.q, G.P, G.st);
-      }
-      if (ctx->mt_kkt4 && N >= 64) hipLaunchKernelGGL(rl::k_mt_kkt4, dim3(G.nb), dim3(256), 0, G.q, G.P, G.st);
-      else hipLaunchKernelGGL(rl::k_mt_kkt, dim3(G.nb), dim3(128), 0, G.q, G.P, G.st);
-      hipLaunchKernelGGL(rl::k_mt_dir, dim3(rl::kMtDirBlocks(N), G.nb), bn64, 0, G.q, G.P, G.st);
-      hipLaunchKernelGGL(rl::k_mt_trial, gn, bn64, 0, G.q, G.P, G.st);
-      hipLaunchKernelGGL(rl::k_mt_step, dim3(G.nb), dim3(256), 0, G.q, G.P, G.st);
-      hipLaunchKernelGGL(rl::k_mt_trial_b, gn, bn64, 0, G.q, G.P, G.st);        // halvings of the instances whose first trial point was rejected
-      hipLaunchKernelGGL(rl::k_mt_step_b, dim3(G.nb), dim3(256), 0, G.q, G.P, G.st);
-    }
-    if (ctx->mt_poll && (it & 7) == 7) {   // host entry point only: stop once every instance has finished
+  StreamFork fork{ctx, ngrp};   // after `ar`: joined before the arena's event is recorded, on every exit
+  MtGroup grp[rl_ctx::kMaxGroups];
+  for (int g = 0; g < ngrp; ++g) {
+    const int b0 = (int)((long long)B * g / ngrp), nb = (int)((long long)B * (g + 1) / ngrp) - b0;
+    const size_t o = (size_t)b0 * N;
+    MtGroup& G = grp[g];
+    G.q = fork_stream(ctx, g); G.P = P; G.st = rl::slice(st, rl::kMtArrays, b0, nb);
+    if (P.bounds_per_instance) { G.P.left = left + o; G.P.right = right + o; }
+    G.X = X + o * 6; G.U = U + o * 4; G.T = T + o; G.stats = stats + (size_t)b0 * rl::kMtStats;
+    G.rows = dim3(rl::mt_row_blocks(N), nb); G.per_node = dim3(N, nb); G.per_inst = dim3(nb);
+  }
+  if (ngrp > 1) RL_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));   // the auxiliary streams start behind what is already enqueued
+  for (int g = 1; g < ngrp; ++g) RL_HIP(hipStreamWaitEvent(grp[g].q, ctx->ev_fork, 0));
+  for (int g = 0; g < ngrp; ++g) {
+    const MtGroup& G = grp[g];
+    RL_TRY(launch(ctx, G.q, rl::k_mt_pack, G.rows, dim3(64), 0, G.P, G.st, G.X, G.U, G.T));
+    RL_TRY(mt_run(ctx, G, rl::k_mt_derivs<0>, G.rows, 64));
+    RL_TRY(launch(ctx, G.q, rl::k_mt_init, dim3(rl::mt_init_blocks(N), G.st.B), dim3(256), 0, G.P, G.st, mt_mu0, mt_delta0));
+  }
+  for (int it = 0; it < max_iter; ++it) {
+    for (int g = 0; g < ngrp; ++g) RL_TRY(mt_enqueue_iteration(ctx, grp[g]));
+    if (poll && (it & 7) == 7) {   // host entry point only: stop once every instance has finished
       const int chunk = it >> 3, slot = chunk & 1;
+      fork.polled = true;
       for (int g = 0; g < ngrp; ++g) {
         RL_HIP(hipEventRecord(ctx->ev_chunk[g], grp[g].q));
         RL_HIP(hipStreamWaitEvent(ctx->poll_stream, ctx->ev_chunk[g], 0));
@@ -1451,46 +1440,38 @@ int rl_mintime_solve_batch_dev(rl_ctx* ctx, const double* model, int B, int N, c
       // (status: 0 -> 1 / 2, written once, never back; an aligned 8-byte word is copied whole), so a stale value can only
       // delay the early exit by one chunk and a fresh one cannot end it early: `all` needs EVERY instance finished, and a
       // finished instance's kernels return at their first line.
-      RL_HIP(hipMemcpyAsync(ctx->poll_host + (size_t)slot * ctx->poll_cap, st.scal, (size_t)B * 16 * sizeof(double),
-                            hipMemcpyDeviceToHost, ctx->poll_stream));
+      RL_HIP(hipMemcpyAsync(ctx->poll_host + (size_t)slot * ctx->poll_cap, st.scal, nscal * sizeof(double), hipMemcpyDeviceToHost, ctx->poll_stream));
       RL_HIP(hipEventRecord(ctx->ev_poll[slot], ctx->poll_stream));
       if (chunk >= 1) {   // the chunk before this one: its copy is done, or nearly, while this chunk keeps the GPU busy
         RL_HIP(hipEventSynchronize(ctx->ev_poll[slot ^ 1]));
         const double* h = ctx->poll_host + (size_t)(slot ^ 1) * ctx->poll_cap;
         bool all = true;
-        for (int b = 0; b < B && all; ++b) all = h[(size_t)b * 16 + 5] != 0.0;
+        for (int b = 0; b < B && all; ++b) all = h[(size_t)b * rl::kMtScal + rl::kMtStatus] != 0.0;
         if (all) break;
       }
     }
   }
-  if (ctx->mt_poll) RL_HIP(hipStreamSynchronize(ctx->poll_stream));   // no copy in flight into the pinned buffer when the call returns
-  // final residuals of the instances still running (status 0 = iteration limit)
-  for (int g = 0; g < ngrp; ++g) {
-    const Grp& G = grp[g];
-    const dim3 gn((N + 63) / 64, G.nb);
-    hipLaunchKernelGGL(rl::k_mt_derivs<0>, gn, bn64, 0, G.q, G.P, G.st);
-    if (ctx->mt_hes_sweep) {
-      hipLaunchKernelGGL(rl::k_mt_derivs<1>, dim3((N + 63) / 64, G.nb, rl::kMtJacSlices), bn64, 0, G.q, G.P, G.st);
-    } else {
-      hipLaunchKernelGGL(rl::k_mt_hes_values, gn, bn64, 0, G.q, G.P, G.st);
-      hipLaunchKernelGGL(rl::k_mt_jac_dirs, dim3((N + rl::kMtJacNodes - 1) / rl::kMtJacNodes, G.nb, 3), bn64, 0, G.q, G.P, G.st);
-      hipLaunchKernelGGL(rl::k_mt_jac_assemble, dim3(N, G.nb), bn64, 0, G.q, G.P, G.st);
-    }
-    hipLaunchKernelGGL(rl::k_mt_residuals, dim3(G.nb), dim3(64), 0, G.q, G.P, G.st);
-    hipLaunchKernelGGL(rl::k_mt_unpack, gn, bn64, 0, G.q, G.P, G.st, G.X, G.U, G.T);
-    hipLaunchKernelGGL(rl::k_mt_stats, dim3((G.nb + 63) / 64), bn64, 0, G.q, G.st, G.stats);
-  }
-  RL_HIP(hipGetLastError());
-  RL_HIP(join());
+  if (poll) { fork.polled = false; RL_HIP(hipStreamSynchronize(ctx->poll_stream)); }   // no copy in flight into the pinned buffer when the call returns
+  for (int g = 0; g < ngrp; ++g) RL_TRY(mt_enqueue_closing(ctx, grp[g]));
+  RL_HIP(join_streams(ctx, std::exchange(fork.n, 1)));
   RL_HIP(ar.end());
   return RL_OK;
+}
+}  // namespace
+
+int rl_mintime_solve_batch_dev(rl_ctx* ctx, const double* model, int B, int N, const double* s, const double* kappa,
+                               const double* left, const double* right, int bounds_per_instance, double margin,
+                               double track_length, double average_track_width, double speed_cap, double* X, double* U,
+                               double* T, int max_iter, double tol, double* stats) {
+  return mintime_solve_common(ctx, model, B, N, s, kappa, left, right, bounds_per_instance, margin, track_length,
+                              average_track_width, speed_cap, X, U, T, max_iter, tol, stats, false);
 }
 
 int rl_mintime_solve_batch(rl_ctx* ctx, const double* model, int B, int N, const double* s, const double* kappa,
                            const double* left, const double* right, int bounds_per_instance, double margin,
                            double track_length, double average_track_width, double speed_cap, double* X, double* U,
                            double* T, int max_iter, double tol, double* stats) {
-  if (!ctx || !model || !s || !kappa || !left || !right || !X || !U || !T || !stats) return fail(RL_ERR_ARG, "null argument");
+  if (!ctx || !left || !right) return fail(RL_ERR_ARG, "null argument");   // what is read here; the shared function checks the rest
   if (B <= 0 || N < 8) return fail(RL_ERR_ARG, "bad sizes (N >= 8 nodes)");
   const size_t bn = (size_t)B * N, nb_ = bounds_per_instance ? bn : (size_t)N;
   for (size_t i = 0; i < nb_; ++i)
@@ -1498,17 +1479,13 @@ int rl_mintime_solve_batch(rl_ctx* ctx, const double* model, int B, int N, const
   Staging sg(ctx);
   const double *ds = sg.in(s, N), *dk = sg.in(kappa, N), *dl = sg.in(left, nb_), *dr = sg.in(right, nb_);
   double *dX = sg.inout(X, bn * 6), *dU = sg.inout(U, bn * 4), *dT = sg.inout(T, bn);
-  double* dst = sg.out(stats, (size_t)B * 12);
+  double* dst = sg.out(stats, (size_t)B * rl::kMtStats);
   sg.run([&] {
-    ctx->mt_poll = true;
-    const int rc = rl_mintime_solve_batch_dev(ctx, model, B, N, ds, dk, dl, dr, bounds_per_instance, margin, track_length,
-                                              average_track_width, speed_cap, dX, dU, dT, max_iter, tol, dst);
-    ctx->mt_poll = false;
-    return rc;
+    return mintime_solve_common(ctx, model, B, N, ds, dk, dl, dr, bounds_per_instance, margin, track_length,
+                                average_track_width, speed_cap, dX, dU, dT, max_iter, tol, dst, true);
   });
   return sg.finish();
 }
-
 
 // ---- the bicycle min-time NLP (rl_bicycle.hpp)
 static int bk_problem(const double* model, int N, rl::BkProblem& P) {
@@ -1554,28 +1531,15 @@ int rl_bicycle_solve_batch_dev(rl_ctx* ctx, const double* model, int B, int N, c
   RL_HIP(hipSetDevice(ctx->device));
   P.per = bounds_per_instance ? 1 : 0;
   P.P0 = P0; P.yaw = yaw; P.dl = dl; P.dr = dr; P.tol = tol;
-  const size_t bn = (size_t)B * N;
-  const size_t counts[] = {bn * rl::kBkNb, bn * rl::kBkNe, bn * 2, bn * rl::kBkNb, bn * rl::kBkNb, bn * rl::kBkKK,
-                           bn * rl::kBkK, bn * rl::kBkKK, bn * rl::kBkKK, bn * rl::kBkK, bn * 16, bn * 2, bn * rl::kBkNb,
-                           (size_t)B * rl::kBkScal, (size_t)B * rl::kBkFilter * 2};
-  size_t total = 0;
-  for (size_t c : counts) total += Arena::pad(c * sizeof(double));
   Arena ar(ctx);
-  RL_HIP(ar.reserve(total));
   rl::BkState st;
-  st.B = B; st.N = N;
-  st.p = ar.take<double>(counts[0]); st.yc = ar.take<double>(counts[1]); st.yd = ar.take<double>(counts[2]);
-  st.zl = ar.take<double>(counts[3]); st.zu = ar.take<double>(counts[4]); st.D = ar.take<double>(counts[5]);
-  st.r = ar.take<double>(counts[6]); st.Dinv = ar.take<double>(counts[7]); st.Tk = ar.take<double>(counts[8]);
-  st.v = ar.take<double>(counts[9]); st.Jd = ar.take<double>(counts[10]); st.dcur = ar.take<double>(counts[11]);
-  st.dp = ar.take<double>(counts[12]); st.scal = ar.take<double>(counts[13]); st.filt = ar.take<double>(counts[14]);
+  RL_HIP(ar.carve([&](Arena& x) { rl::carve(x, st, rl::kBkArrays, B, N); }));
   const dim3 grid(B), block(rl::kBkThreads);
-  hipLaunchKernelGGL(rl::k_bk_init, grid, block, 0, ctx->stream, P, st, (const double*)X, (const double*)U, (const double*)T);
+  RL_TRY(launch(ctx, rl::k_bk_init, grid, block, 0, P, st, X, U, T));
   // exactly max_iter iterations are enqueued; an instance that has converged or failed returns from each at once
-  for (int it = 0; it < max_iter; ++it) hipLaunchKernelGGL(rl::k_bk_iter, grid, block, 0, ctx->stream, P, st, 0);
-  hipLaunchKernelGGL(rl::k_bk_iter, grid, block, 0, ctx->stream, P, st, 1);
-  hipLaunchKernelGGL(rl::k_bk_unpack, dim3((N + 63) / 64, B), dim3(64), 0, ctx->stream, P, st, X, U, T, stats);
-  RL_HIP(hipGetLastError());
+  for (int it = 0; it < max_iter; ++it) RL_TRY(launch(ctx, rl::k_bk_iter, grid, block, 0, P, st, 0));
+  RL_TRY(launch(ctx, rl::k_bk_iter, grid, block, 0, P, st, 1));
+  RL_TRY(launch(ctx, rl::k_bk_unpack, dim3((N + 63) / 64, B), dim3(64), 0, P, st, X, U, T, stats));
   RL_HIP(ar.end());
   return RL_OK;
 }
@@ -1591,7 +1555,7 @@ int rl_bicycle_solve_batch(rl_ctx* ctx, const double* model, int B, int N, const
   Staging sg(ctx);
   const double *dP0 = sg.in(P0, (size_t)2 * N), *dyaw = sg.in(yaw, N), *ddl = sg.in(dl, nb_), *ddr = sg.in(dr, nb_);
   double *dX = sg.inout(X, bn * 5), *dU = sg.inout(U, bn * 2), *dT = sg.inout(T, bn);
-  double* dst = sg.out(stats, (size_t)B * 12);
+  double* dst = sg.out(stats, (size_t)B * rl::kBkStats);
   sg.run([&] {
     return rl_bicycle_solve_batch_dev(ctx, model, B, N, dP0, dyaw, ddl, ddr, bounds_per_instance, dX, dU, dT, max_iter, tol, dst);
   });

@@ -66,6 +66,8 @@ constexpr int kMtHesSlices = mt_hes_slices();   // 113 of the 171 pairs
 constexpr double kMtEpsReg = 1e-8;  // dual regularisation of the KKT system
 constexpr double kMtThetaGrowth = 2.0, kMtThetaFloor = 1e-5;
 constexpr int kMtFilter = 8;   // entries of the filter (a ring: the oldest is overwritten)
+// the other strides of the state arrays (kMtArrays below, where each is described), the status word and the caller's report
+constexpr int kMtBlk = kMtNb * kMtNb, kMtBlkStride = 3 * kMtBlk, kMtScal = 16, kMtStatus = 5, kMtStats = 12, kMtGc = 64, kMtHw = 336;
 constexpr double kMtCostDiag = 2e-4 + 4e-1, kMtCostOff = -2e-1;  // Hessian of 1e-4 |U|^2 + 1e-1 |dU|^2 (:119-123)
 
 struct MtProblem {
@@ -180,32 +182,37 @@ __device__ __forceinline__ void mt_pair(const MtProblem& P, int j, const S (&wo)
 }
 
 // ------------------------------------------------------------------------------------------------
-struct MtState {       // per-batch device arrays, instance-major
+struct MtState {       // per-batch device arrays, instance-major; their shapes are kMtArrays below
   int B, N;
-  double* w;      // [B,N,9]  scaled unknowns
-  double* s;      // [B,N,17] slacks
-  double* y;      // [B,N,7]  equality multipliers
-  double* z;      // [B,N,17] inequality multipliers
-  double* fun;    // [B,N,24] eq | g at w
-  double* jac;    // [B,N,24,18]
-  double* hes;    // [B,N,18,18] Hessian of y.eq + z.g of the pair
-  double* dw;     // [B,N,9]
-  double* dy;     // [B,N,7]
-  double* blk;    // [B,N,3,256] factor blocks of k_mt_kkt, per node: P [256], Q [256], a' [16] (+ padding)
-  double* vec;    // [B,N,16] right-hand side / solution scratch
-  double* dblk;   // [B,N,256] assembled diagonal blocks D_j (without delta)
-  double* eblk;   // [B,N,256] assembled coupling blocks E_j = M[j+1][j]
-  double* rhs;    // [B,N,16]  assembled right-hand sides
-  double* r1;     // [B,N,16]  k_mt_node: 0..8 the coefficient of mu in the right-hand side, 9 the node's max |r_d|
-  double* gc;     // [B,N,64]  the 60 entries of the inequality Jacobian that can be non-zero (kMtGc*), what k_mt_dir reads
-  double* hw;     // [B,N,kMtHw] work array of the chain-rule Hessian (k_mt_hes_*)
-  double* filt;   // [B,16] filter: (infeasibility, barrier objective) of up to 8 earlier iterates of the current barrier problem
-  double* scal;   // [B,16] per-instance scalars: 0 mu, 1 delta, 2 kkt, 3 viol, 4 compl, 5 status (0 run, 1 converged,
-                  //        2 failed), 6 iterations, 7 last alpha, 8 theta0, 9 phi0, 10 refactorisations, 11 lap time
+  double *w, *s, *y, *z, *fun, *jac, *hes, *dw, *dy, *blk, *vec, *dblk, *eblk, *rhs, *r1, *gc, *hw, *filt, *scal;
   double tol;
-  // strategy constants (defaults in rl_mincurv.hip; the RL_MT_* environment switches exist for experiments)
+  // strategy constants: compile-time constants of the product (rl_mincurv.hip); RL_MT_* overrides only with -DRL_ABLATION
   double d_down, d_up, a_hi, a_lo, mu_fac, mu_pow, mu_kappa, th_filter, dual_cap;
 };
+
+// The one statement of MtState's shapes (StateArray, rl_dtrack.hpp), in the order the host carves them.
+constexpr StateArray<MtState> kMtArrays[] = {
+    {&MtState::w, kMtNv, 0},               // [B,N,9]  scaled unknowns
+    {&MtState::s, kMtNi, 0},               // [B,N,17] slacks
+    {&MtState::y, kMtNe, 0},               // [B,N,7]  equality multipliers
+    {&MtState::z, kMtNi, 0},               // [B,N,17] inequality multipliers
+    {&MtState::fun, kMtNf, 0},             // [B,N,24] eq | g at w
+    {&MtState::jac, kMtNf * kMtLoc, 0},    // [B,N,24,18]
+    {&MtState::hes, kMtLoc * kMtLoc, 0},   // [B,N,18,18] Hessian of y.eq + z.g of the pair
+    {&MtState::dw, kMtNv, 0},              // [B,N,9]
+    {&MtState::dy, kMtNe, 0},              // [B,N,7]
+    {&MtState::blk, kMtBlkStride, 0},      // [B,N,3,256] factor blocks of k_mt_kkt, per node: P [256], Q [256], a' [16] (+ padding)
+    {&MtState::vec, kMtNb, 0},             // [B,N,16] right-hand side / solution scratch
+    {&MtState::scal, 0, kMtScal},          // 0 mu, 1 delta, 2 kkt, 3 viol, 4 compl, 5 status (0 run, 1 converged, 2 failed), 6 iterations, 7 last alpha, 8 theta0, 9 phi0, 10 refactorisations, 11 lap time
+    {&MtState::dblk, kMtBlk, 0},           // [B,N,256] assembled diagonal blocks D_j (without delta)
+    {&MtState::eblk, kMtBlk, 0},           // [B,N,256] assembled coupling blocks E_j = M[j+1][j]
+    {&MtState::rhs, kMtNb, 0},             // [B,N,16]  assembled right-hand sides
+    {&MtState::filt, 0, 2 * kMtFilter},    // [B,8,2] filter: (infeasibility, barrier objective) of up to 8 earlier iterates of the current barrier problem
+    {&MtState::hw, kMtHw, 0},              // [B,N,kMtHw] work array of the chain-rule Hessian (k_mt_hes_*)
+    {&MtState::r1, kMtNb, 0},              // [B,N,16]  k_mt_node: 0..8 the coefficient of mu in the right-hand side, 9 the node's max |r_d|
+    {&MtState::gc, kMtGc, 0},              // [B,N,64]  the 60 entries of the inequality Jacobian that can be non-zero (kMtGc*), what k_mt_dir reads
+};
+static_assert(sizeof(kMtArrays) / sizeof(kMtArrays[0]) == (offsetof(MtState, tol) - offsetof(MtState, w)) / sizeof(double*), "every array of MtState has its row");
 
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void mt_instance(MtProblem& P, int b) {
@@ -221,7 +228,7 @@ __global__ void __launch_bounds__(64) k_mt_derivs(MtProblem P, MtState st) {
   const int b = blockIdx.y;
   const int slice = KIND == 0 ? 0 : (KIND == 1 ? 1 + (int)blockIdx.z : 1 + kMtJacSlices + (int)blockIdx.z);
   if (j >= P.N) return;
-  if (st.scal[(size_t)b * 16 + 5] != 0.0) return;   // instance finished
+  if (st.scal[(size_t)b * kMtScal + kMtStatus] != 0.0) return;   // instance finished
   mt_instance(P, b);
   const int N = P.N, jn = j + 1 == N ? 0 : j + 1;
   const double* wo_ = st.w + ((size_t)b * N + j) * kMtNv;
@@ -339,7 +346,7 @@ __global__ void __launch_bounds__(64) k_mt_derivs(MtProblem P, MtState st) {
 // with M = d(Ym,U)/d(Y,U,t,Y').  3.1 times fewer instructions than the sweep, and fewer live values per thread.
 constexpr int kMtPv = 8;
 constexpr int kMtHwXm = 0, kMtHwDf = 5, kMtHwGm = 10, kMtHwHm = 18, kMtHwJ1 = 54, kMtHwJ2 = 102, kMtHwH1 = 150, kMtHwH2 = 186,
-              kMtHwJm = 222, kMtHwOw = 270, kMtHwF = 318, kMtHw = 336;   // Jm [6][8], own-row gradients [6][8], f1 f2 fm [3][6]
+              kMtHwJm = 222, kMtHwOw = 270, kMtHwF = 318;   // ends at kMtHw = 336: Jm [6][8], own-row gradients [6][8], f1 f2 fm [3][6]
 
 __device__ __forceinline__ int mt_tri8(int a, int b) {               // index of the pair (a, b) of 8, any order: row-wise upper triangle
   const int lo = a < b ? a : b, hi = a < b ? b : a;
@@ -429,13 +436,13 @@ __device__ __forceinline__ void mt_fun_body(MtProblem P, const MtState& st, int 
 // grid (node blocks, B): values of the two end evaluations -> midpoint and F1 - F2
 __global__ void __launch_bounds__(64) k_mt_hes_values(MtProblem P, MtState st) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
-  if (j >= P.N || st.scal[(size_t)b * 16 + 5] != 0.0) return;
+  if (j >= P.N || st.scal[(size_t)b * kMtScal + kMtStatus] != 0.0) return;
   mt_hes_values_body(P, st, b, j);
 }
 // grid (node blocks, B): both of the above in one launch (the first kernel of an iteration of the default path)
 __global__ void __launch_bounds__(64) k_mt_values(MtProblem P, MtState st) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
-  if (j >= P.N || st.scal[(size_t)b * 16 + 5] != 0.0) return;
+  if (j >= P.N || st.scal[(size_t)b * kMtScal + kMtStatus] != 0.0) return;
   mt_fun_body(P, st, b, j);
   mt_hes_values_body(P, st, b, j);
 }
@@ -470,7 +477,7 @@ __global__ void __launch_bounds__(64) k_mt_jac_dirs(MtProblem P, MtState st) {
   const int nl = (int)threadIdx.x / kMtJacDirs, dl = (int)threadIdx.x - kMtJacDirs * nl;
   const int j = blockIdx.x * kMtJacNodes + nl, b = blockIdx.y, N = P.N;
   const int pt = blockIdx.z, d = 2 + dl;
-  if (nl >= kMtJacNodes || j >= N || st.scal[(size_t)b * 16 + 5] != 0.0) return;
+  if (nl >= kMtJacNodes || j >= N || st.scal[(size_t)b * kMtScal + kMtStatus] != 0.0) return;
   const int jn = j + 1 == N ? 0 : j + 1;
   double Y[5], Yn[5], U[3], t;
   mt_phys(P, st.w + ((size_t)b * N + j) * kMtNv, st.w + ((size_t)b * N + jn) * kMtNv, Y, Yn, U, t);
@@ -518,7 +525,7 @@ __global__ void __launch_bounds__(64) k_mt_jac_dirs(MtProblem P, MtState st) {
 __global__ void __launch_bounds__(64) k_mt_jac_assemble(MtProblem P, MtState st) {
   __shared__ double M[kMtPv][14], JM[6][14];
   const int j = blockIdx.x, b = blockIdx.y, lane = threadIdx.x, N = P.N;
-  if (st.scal[(size_t)b * 16 + 5] != 0.0) return;
+  if (st.scal[(size_t)b * kMtScal + kMtStatus] != 0.0) return;
   const int jn = j + 1 == N ? 0 : j + 1;
   const size_t o = (size_t)b * N + j;
   const double* wo = st.w + o * kMtNv;
@@ -609,7 +616,7 @@ __global__ void __launch_bounds__(64, 2) k_mt_hes_point(MtProblem P, MtState st)
   const int nl = (int)threadIdx.x / kMtDynPairs, q = (int)threadIdx.x - kMtDynPairs * nl;
   const int j = blockIdx.x * kMtHesNodes + nl, b = blockIdx.y, N = P.N;
   const int pt = ENDS ? (int)blockIdx.z : 0;
-  if (nl >= kMtHesNodes || j >= N || st.scal[(size_t)b * 16 + 5] != 0.0) return;
+  if (nl >= kMtHesNodes || j >= N || st.scal[(size_t)b * kMtScal + kMtStatus] != 0.0) return;
   const int jn = j + 1 == N ? 0 : j + 1;
   const size_t o = (size_t)b * N + j;
   double Y[5], Yn[5], U[3], t;
@@ -674,7 +681,7 @@ __global__ void __launch_bounds__(64, 2) k_mt_hes_point(MtProblem P, MtState st)
 __global__ void __launch_bounds__(64) k_mt_hes_assemble(MtProblem P, MtState st) {
   __shared__ double M[kMtPv][14], T[kMtPv][14], Hm[kMtPv][kMtPv], g[kMtPv], gpsi[14], gphi[2][kMtPv], gF[2][kMtPv];
   const int j = blockIdx.x, b = blockIdx.y, lane = threadIdx.x, N = P.N;
-  if (st.scal[(size_t)b * 16 + 5] != 0.0) return;
+  if (st.scal[(size_t)b * kMtScal + kMtStatus] != 0.0) return;
   const int jn = j + 1 == N ? 0 : j + 1;
   const size_t o = (size_t)b * N + j;
   const double* wo = st.w + o * kMtNv;
@@ -900,8 +907,8 @@ __device__ __forceinline__ void mt_residuals(const MtProblem& P, const double* w
 // convergence test, barrier update (everything the assembly of the right-hand side needs to know)
 __global__ void __launch_bounds__(64) k_mt_prepare(MtProblem P, MtState st) {
   const int b = blockIdx.x, lane = threadIdx.x, N = P.N;
-  double* scal = st.scal + (size_t)b * 16;
-  if (scal[5] != 0.0) return;
+  double* scal = st.scal + (size_t)b * kMtScal;
+  if (scal[kMtStatus] != 0.0) return;
   mt_instance(P, b);
   double mu = scal[0];
   double kkt, viol, compl_, errmu, lap;
@@ -910,7 +917,7 @@ __global__ void __launch_bounds__(64) k_mt_prepare(MtProblem P, MtState st) {
                mu, lane, kkt, viol, compl_, errmu, lap);
   if (lane == 0) { scal[2] = kkt; scal[3] = viol; scal[4] = compl_; scal[11] = lap; }
   if (fmax(kkt, fmax(viol, compl_)) <= st.tol) {
-    if (lane == 0) scal[5] = 1.0;
+    if (lane == 0) scal[kMtStatus] = 1.0;
     return;
   }
   // monotone barrier update once the barrier problem is solved to mu_kappa mu; no lower than compl <= tol needs
@@ -935,8 +942,8 @@ struct MtAsmLds { double Do[81], Dn[81], Ct[81], w[2][kMtNi], zeta[2][kMtNi], Go
 __global__ void __launch_bounds__(64) k_mt_assemble(MtProblem P, MtState st) {
   __shared__ MtAsmLds L;
   const int j = blockIdx.x, b = blockIdx.y, lane = threadIdx.x, N = P.N;
-  const double* scal = st.scal + (size_t)b * 16;
-  if (scal[5] != 0.0) return;
+  const double* scal = st.scal + (size_t)b * kMtScal;
+  if (scal[kMtStatus] != 0.0) return;
   const int jp = j == 0 ? N - 1 : j - 1;
   const double* w = st.w + (size_t)b * N * kMtNv;
   const double* sv = st.s + (size_t)b * N * kMtNi;
@@ -972,8 +979,8 @@ __global__ void __launch_bounds__(64) k_mt_assemble(MtProblem P, MtState st) {
     L.Do[e] = doo; L.Ct[e] = cno; L.Dn[e] = dnn;
   }
   __syncthreads();
-  double* Dg = st.dblk + ((size_t)b * N + j) * 256;
-  double* Eg = st.eblk + ((size_t)b * N + j) * 256;
+  double* Dg = st.dblk + ((size_t)b * N + j) * kMtBlk;
+  double* Eg = st.eblk + ((size_t)b * N + j) * kMtBlk;
   for (int e = lane; e < 256; e += 64) {
     const int i = e >> 4, c = e & 15;
     double d = 0.0, ev = 0.0;
@@ -1001,7 +1008,7 @@ __global__ void __launch_bounds__(64) k_mt_assemble(MtProblem P, MtState st) {
     } else {
       r = fun[j * kMtNf + (lane - 9)];
     }
-    st.rhs[((size_t)b * N + j) * 16 + lane] = -r;
+    st.rhs[((size_t)b * N + j) * kMtNb + lane] = -r;
   }
 }
 
@@ -1045,14 +1052,14 @@ __host__ __device__ constexpr int mt_map2(int zi) { return zi >= 9 ? zi - 9 : (z
 
 // Compact inequality Jacobian of a pair: slots 0..39 = rows 0..4 x columns 0..7 (tyre ellipses, power: the node's (Y, U)),
 // slots 40..59 = the one to three entries of the other rows (mt_g_has), in row order.
-constexpr int kMtGc = 64, kMtGcSparse = 20;
+constexpr int kMtGcSparse = 20;
 __device__ constexpr unsigned char kMtGcRow[kMtGcSparse] = {5, 6, 7, 8, 9, 10, 10, 10, 11, 11, 11, 12, 12, 12, 13, 13, 13, 14, 15, 16};
 __device__ constexpr unsigned char kMtGcCol[kMtGcSparse] = {4, 5, 5, 6, 6, 5, 8, 14, 5, 8, 14, 6, 8, 15, 6, 8, 15, 0, 0, 8};
 
 // cross-check paths (full Jacobian from k_mt_derivs<1> / k_mt_jac_assemble): gather the compact form; grid (N, B)
 __global__ void __launch_bounds__(64) k_mt_gc_pack(MtProblem P, MtState st) {
   const int j = blockIdx.x, b = blockIdx.y, l = threadIdx.x, N = P.N;
-  if (st.scal[(size_t)b * 16 + 5] != 0.0 || l >= 40 + kMtGcSparse) return;
+  if (st.scal[(size_t)b * kMtScal + kMtStatus] != 0.0 || l >= 40 + kMtGcSparse) return;
   const size_t o = (size_t)b * N + j;
   const double* Jg = st.jac + (o * kMtNf + kMtNe) * kMtLoc;
   const int row = l < 40 ? l >> 3 : kMtGcRow[l - 40], col = l < 40 ? l & 7 : kMtGcCol[l - 40];
@@ -1065,7 +1072,7 @@ static_assert(kMtHesNodes * kMtDynPairs <= 64 && kMtJacNodes * kMtJacDirs <= 64,
 __global__ void __launch_bounds__(64) k_mt_node(MtProblem P, MtState st) {
   __shared__ MtNodeGrp LG[kMtNodeGroups];
   const int b = blockIdx.y, lane = threadIdx.x, N = P.N;
-  if (st.scal[(size_t)b * 16 + 5] != 0.0) return;
+  if (st.scal[(size_t)b * kMtScal + kMtStatus] != 0.0) return;
   const int c = lane & 15;
   MtNodeGrp& L = LG[lane >> 4];
   const int run0 = ((int)blockIdx.x * kMtNodeGroups + (lane >> 4)) * kMtRun;
@@ -1287,8 +1294,8 @@ __global__ void __launch_bounds__(64) k_mt_node(MtProblem P, MtState st) {
     // ---- E: the node's blocks and right-hand side (its own pair + the carry of the previous one)
     {
       const int ct = c >= 9 ? c - 9 : 0, cl = c < 9 ? c : 0;
-      double* Dg = st.dblk + o * 256;
-      double* Eg = st.eblk + o * 256;
+      double* Dg = st.dblk + o * kMtBlk;
+      double* Eg = st.eblk + o * kMtBlk;
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         double d, ev = 0.0;
@@ -1317,8 +1324,8 @@ __global__ void __launch_bounds__(64) k_mt_node(MtProblem P, MtState st) {
 #pragma unroll
       for (int m = 8; m >= 1; m >>= 1) rdv = fmax(rdv, __shfl_xor(rdv, m, 16));
       if (own) {
-        st.rhs[o * 16 + c] = -r0;
-        st.r1[o * 16 + c] = c == kMtNv ? rdv : r1;
+        st.rhs[o * kMtNb + c] = -r0;
+        st.r1[o * kMtNb + c] = c == kMtNv ? rdv : r1;
       }
     }
     __syncthreads();
@@ -1375,17 +1382,17 @@ __device__ __forceinline__ void mt_block_reduce_n(double (&v)[NV], const int (&o
 template <int BLOCK>
 __device__ __forceinline__ bool mt_prepare2(const MtProblem& P, const MtState& st, int b, int tid, double* red) {
   const int N = P.N;
-  double* scal = st.scal + (size_t)b * 16;
+  double* scal = st.scal + (size_t)b * kMtScal;
   const double* w = st.w + (size_t)b * N * kMtNv;
   const double* sv = st.s + (size_t)b * N * kMtNi;
   const double* zv = st.z + (size_t)b * N * kMtNi;
   const double* fun = st.fun + (size_t)b * N * kMtNf;
-  const double* r1 = st.r1 + (size_t)b * N * 16;
-  double* rhs = st.rhs + (size_t)b * N * 16;
+  const double* r1 = st.r1 + (size_t)b * N * kMtNb;
+  double* rhs = st.rhs + (size_t)b * N * kMtNb;
   double mu = scal[0];
   double kkt = 0.0, viol = 0.0, compl_ = 0.0, errmu = 0.0, lap = 0.0;
   for (int j = tid; j < N; j += BLOCK) {
-    kkt = fmax(kkt, r1[(size_t)j * 16 + kMtNv]);
+    kkt = fmax(kkt, r1[(size_t)j * kMtNb + kMtNv]);
     lap += w[(size_t)j * kMtNv + 8] * P.sw[8];
   }
   for (int idx = tid; idx < N * kMtNe; idx += BLOCK) {
@@ -1407,7 +1414,7 @@ __device__ __forceinline__ bool mt_prepare2(const MtProblem& P, const MtState& s
   }
   if (tid == 0) { scal[2] = kkt; scal[3] = viol; scal[4] = compl_; scal[11] = lap; }
   if (fmax(kkt, fmax(viol, compl_)) <= st.tol) {
-    if (tid == 0) scal[5] = 1.0;
+    if (tid == 0) scal[kMtStatus] = 1.0;
     return true;
   }
   if (fmax(fmax(kkt, viol), errmu) <= st.mu_kappa * mu) {
@@ -1418,7 +1425,7 @@ __device__ __forceinline__ bool mt_prepare2(const MtProblem& P, const MtState& s
   if (tid == 0) scal[0] = mu;
   for (int idx = tid; idx < N * kMtNv; idx += BLOCK) {
     const int j = idx / kMtNv, a = idx - j * kMtNv;
-    rhs[(size_t)j * 16 + a] = fma(-mu, r1[(size_t)j * 16 + a], rhs[(size_t)j * 16 + a]);
+    rhs[(size_t)j * kMtNb + a] = fma(-mu, r1[(size_t)j * kMtNb + a], rhs[(size_t)j * kMtNb + a]);
   }
   __syncthreads();
   return false;
@@ -1427,7 +1434,7 @@ __device__ __forceinline__ bool mt_prepare2(const MtProblem& P, const MtState& s
 
 __global__ void __launch_bounds__(256) k_mt_prepare2(MtProblem P, MtState st) {
   __shared__ double red[5 * 4];
-  if (st.scal[(size_t)blockIdx.x * 16 + 5] != 0.0) return;
+  if (st.scal[(size_t)blockIdx.x * kMtScal + kMtStatus] != 0.0) return;
   (void)mt_prepare2<256>(P, st, blockIdx.x, threadIdx.x, red);
 }
 
@@ -1453,13 +1460,13 @@ __global__ void __launch_bounds__(128) k_mt_kkt(MtProblem P, MtState st) {
   __shared__ MtKktShare X;
   const int b = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, N = P.N;
   const int i = lane & 15, q = lane >> 4;
-  double* scal = st.scal + (size_t)b * 16;
-  if (scal[5] != 0.0) return;
-  const double* Dg = st.dblk + (size_t)b * N * 256;
-  const double* Eg = st.eblk + (size_t)b * N * 256;
-  const double* Rg = st.rhs + (size_t)b * N * 16;
-  double* blk = st.blk + (size_t)b * N * 3 * 256;   // per node: P [256], Q [256], a' [16]
-  double* vec = st.vec + (size_t)b * N * 16;
+  double* scal = st.scal + (size_t)b * kMtScal;
+  if (scal[kMtStatus] != 0.0) return;
+  const double* Dg = st.dblk + (size_t)b * N * kMtBlk;
+  const double* Eg = st.eblk + (size_t)b * N * kMtBlk;
+  const double* Rg = st.rhs + (size_t)b * N * kMtNb;
+  double* blk = st.blk + (size_t)b * N * kMtBlkStride;   // per node: P [256], Q [256], a' [16]
+  double* vec = st.vec + (size_t)b * N * kMtNb;
   double delta = scal[1];
   auto ld = [&](const double* G) { MtBlk Z;      // row-major block -> A-layout
 #pragma unroll
@@ -1481,41 +1488,41 @@ __global__ void __launch_bounds__(128) k_mt_kkt(MtProblem P, MtState st) {
   const int cnt = wave == 0 ? m : N - 2 - m;         // nodes of this front
   auto node = [&](int s_) { return wave == 0 ? s_ : N - 2 - s_; };
   // coupling of node j to the NEXT node of its front, in the role of E_j of the ascending recursion
-  auto ld_e = [&](int j) { return wave == 0 ? ld(Eg + (size_t)j * 256) : ld_t(Eg + (size_t)(j - 1) * 256); };
+  auto ld_e = [&](int j) { return wave == 0 ? ld(Eg + (size_t)j * kMtBlk) : ld_t(Eg + (size_t)(j - 1) * kMtBlk); };
 
   int attempt = 0, fails = 0;
   bool ok = false;
   for (; attempt < 12 && !ok; ++attempt) {
     bool bad = false;
     int n_neg = 0;
-    MtBlk S = ld_t(Dg + (size_t)node(0) * 256); shift(S);
+    MtBlk S = ld_t(Dg + (size_t)node(0) * kMtBlk); shift(S);
     // border block of the front's first node: M[N-1][0] = E_{N-1}'  /  M[N-1][N-2] = E_{N-2}
-    MtBlk F = wave == 0 ? ld_t(Eg + (size_t)(N - 1) * 256) : ld(Eg + (size_t)(N - 2) * 256);
+    MtBlk F = wave == 0 ? ld_t(Eg + (size_t)(N - 1) * kMtBlk) : ld(Eg + (size_t)(N - 2) * kMtBlk);
     MtBlk SlC = zero, Tx = zero, Fx = zero;   // contributions to S_last; what the meeting node receives
     double rlC = 0.0, rx = 0.0;
     double rk[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) rk[r] = Rg[(size_t)node(0) * 16 + 4 * r + q];
-    MtBlk eN = ld_e(node(0)), dN = cnt > 1 ? ld_t(Dg + (size_t)node(1) * 256) : zero;   // blocks of the next step, in flight
-    double rN = cnt > 1 ? Rg[(size_t)node(1) * 16 + i] : 0.0;
+    for (int r = 0; r < 4; ++r) rk[r] = Rg[(size_t)node(0) * kMtNb + 4 * r + q];
+    MtBlk eN = ld_e(node(0)), dN = cnt > 1 ? ld_t(Dg + (size_t)node(1) * kMtBlk) : zero;   // blocks of the next step, in flight
+    double rN = cnt > 1 ? Rg[(size_t)node(1) * kMtNb + i] : 0.0;
     for (int s_ = 0; s_ < cnt && !bad; ++s_) {
       const int j = node(s_);
       const MtBlk E = eN, dC = dN;
       const double rC = rN;
       if (s_ + 1 < cnt) {                // prefetch for the next step
         eN = ld_e(node(s_ + 1));
-        dN = s_ + 2 < cnt ? ld_t(Dg + (size_t)node(s_ + 2) * 256) : zero;
-        rN = s_ + 2 < cnt ? Rg[(size_t)node(s_ + 2) * 16 + i] : 0.0;
+        dN = s_ + 2 < cnt ? ld_t(Dg + (size_t)node(s_ + 2) * kMtBlk) : zero;
+        rN = s_ + 2 < cnt ? Rg[(size_t)node(s_ + 2) * kMtNb + i] : 0.0;
       }
       const int neg = mt_invert(S, lane);                   // S_j^-1
       if (neg < 0) { bad = true; break; }
       n_neg += neg;
       const double aj = mt_gemv(S, rk);                     // a_j = S_j^-1 r_j
-      if (q == 0) vec[(size_t)j * 16 + i] = aj;
+      if (q == 0) vec[(size_t)j * kMtNb + i] = aj;
       const MtBlk Pm = mt_mul_t(S, E);                      // P_j = E S_j^-1
       const MtBlk Qm = mt_mul_t(S, F);                      // Q_j = F_j S_j^-1
-      double* Bj = blk + (size_t)j * 3 * 256;
-      st_rm(Bj, Pm); st_rm(Bj + 256, Qm);
+      double* Bj = blk + (size_t)j * kMtBlkStride;
+      st_rm(Bj, Pm); st_rm(Bj + kMtBlk, Qm);
       rlC -= mt_gemv(Qm, rk);                               // r_last -= Q_j r_j
       {
         const MtBlk U = mt_mul_t(F, Qm);                    // S_last -= Q_j F_j'
@@ -1547,8 +1554,8 @@ __global__ void __launch_bounds__(128) k_mt_kkt(MtProblem P, MtState st) {
     if (fronts_ok && wave == 0) {
       // ---- meeting node m, then the border
       bool okm = true;
-      MtBlk Sm = ld_t(Dg + (size_t)m * 256); shift(Sm);
-      MtBlk Fm, Sl = ld_t(Dg + (size_t)(N - 1) * 256);
+      MtBlk Sm = ld_t(Dg + (size_t)m * kMtBlk); shift(Sm);
+      MtBlk Fm, Sl = ld_t(Dg + (size_t)(N - 1) * kMtBlk);
       shift(Sl);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -1557,17 +1564,17 @@ __global__ void __launch_bounds__(128) k_mt_kkt(MtProblem P, MtState st) {
         Sl.v[r] += SlC.v[r] + X.Sl[lane * 4 + r];
       }
       double rmk[4];
-      mt_to_k(Rg[(size_t)m * 16 + i] + rx + X.rn[i], q, rmk);
-      double rl = Rg[(size_t)(N - 1) * 16 + i] + rlC + X.rl[i];
+      mt_to_k(Rg[(size_t)m * kMtNb + i] + rx + X.rn[i], q, rmk);
+      double rl = Rg[(size_t)(N - 1) * kMtNb + i] + rlC + X.rl[i];
       int total = X.nneg[0] + X.nneg[1];
       const int negm = mt_invert(Sm, lane);
       if (negm < 0) okm = false;
       total += negm;
       const double am = mt_gemv(Sm, rmk);
-      if (q == 0) vec[(size_t)m * 16 + i] = am;
+      if (q == 0) vec[(size_t)m * kMtNb + i] = am;
       const MtBlk Qm = mt_mul_t(Sm, Fm);
-      double* Bm = blk + (size_t)m * 3 * 256;
-      st_rm(Bm, zero); st_rm(Bm + 256, Qm);
+      double* Bm = blk + (size_t)m * kMtBlkStride;
+      st_rm(Bm, zero); st_rm(Bm + kMtBlk, Qm);
       rl -= mt_gemv(Qm, rmk);
       {
         const MtBlk U = mt_mul_t(Fm, Qm);
@@ -1597,7 +1604,7 @@ __global__ void __launch_bounds__(128) k_mt_kkt(MtProblem P, MtState st) {
   }
   if (threadIdx.x == 0) { scal[1] = delta; scal[10] += (double)fails; }   // refactorisations = failed attempts (also on the give-up path)
   if (!ok) {
-    if (threadIdx.x == 0) scal[5] = 2.0;
+    if (threadIdx.x == 0) scal[kMtStatus] = 2.0;
     return;
   }
   // ---- back substitution: x_j = a_j - Q_j' x_last - P_j' x_(neighbour towards m), from m outwards on both sides
@@ -1618,11 +1625,11 @@ __global__ void __launch_bounds__(128) k_mt_kkt(MtProblem P, MtState st) {
     for (int j0 = j_lo; j0 < j_hi; j0 += 4) {
       const int j = j0 + q;
       if (j < j_hi) {
-        const double* Qg = blk + (size_t)j * 3 * 256 + 256;
-        double acc = vec[(size_t)j * 16 + i];
+        const double* Qg = blk + (size_t)j * kMtBlkStride + kMtBlk;
+        double acc = vec[(size_t)j * kMtNb + i];
 #pragma unroll
         for (int k = 0; k < 16; ++k) acc = fma(-Qg[k * 16 + i], xl[k], acc);
-        blk[(size_t)j * 3 * 256 + 512 + i] = acc;
+        blk[(size_t)j * kMtBlkStride + 2 * kMtBlk + i] = acc;
       }
     }
   }
@@ -1631,7 +1638,7 @@ __global__ void __launch_bounds__(128) k_mt_kkt(MtProblem P, MtState st) {
   // each wave own one component each; P and a' of the node THREE steps ahead are fetched while x_j is formed (four
   // rotating register sets: a step is shorter than the latency of a load).
   if (wave == 0 && lane < 16) {
-    const double x = blk[(size_t)m * 3 * 256 + 512 + lane];
+    const double x = blk[(size_t)m * kMtBlkStride + 2 * kMtBlk + lane];
     if (lane < kMtNv) dw[(size_t)m * kMtNv + lane] = x;
     else dy[(size_t)m * kMtNe + lane - kMtNv] = x;
     X.xm[lane] = x;
@@ -1642,10 +1649,10 @@ __global__ void __launch_bounds__(128) k_mt_kkt(MtProblem P, MtState st) {
   double pb[4][17];
   auto fetch = [&](double (&dst)[17], int s_) {
     if (s_ < steps && lane < 16) {
-      const double* Bn = blk + (size_t)chain_node(s_) * 3 * 256;
+      const double* Bn = blk + (size_t)chain_node(s_) * kMtBlkStride;
 #pragma unroll
       for (int k = 0; k < 16; ++k) dst[k] = Bn[k * 16 + lane];
-      dst[16] = Bn[512 + lane];
+      dst[16] = Bn[2 * kMtBlk + lane];
     }
   };
   fetch(pb[0], 0); fetch(pb[1], 1); fetch(pb[2], 2);
@@ -1698,13 +1705,13 @@ __global__ void __launch_bounds__(256, 2) k_mt_kkt4(MtProblem P, MtState st) {
   __shared__ MtKkt4Share X;
   const int b = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, N = P.N;
   const int i = lane & 15, q = lane >> 4;
-  double* scal = st.scal + (size_t)b * 16;
-  if (scal[5] != 0.0) return;
-  const double* Dg = st.dblk + (size_t)b * N * 256;
-  const double* Eg = st.eblk + (size_t)b * N * 256;
-  const double* Rg = st.rhs + (size_t)b * N * 16;
-  double* blk = st.blk + (size_t)b * N * 3 * 256;   // per node: P [256], Q [256], a' [16]
-  double* vec = st.vec + (size_t)b * N * 16;
+  double* scal = st.scal + (size_t)b * kMtScal;
+  if (scal[kMtStatus] != 0.0) return;
+  const double* Dg = st.dblk + (size_t)b * N * kMtBlk;
+  const double* Eg = st.eblk + (size_t)b * N * kMtBlk;
+  const double* Rg = st.rhs + (size_t)b * N * kMtNb;
+  double* blk = st.blk + (size_t)b * N * kMtBlkStride;   // per node: P [256], Q [256], a' [16]
+  double* vec = st.vec + (size_t)b * N * kMtNb;
   double delta = scal[1];
   auto ld = [&](const double* G) { MtBlk Z;
 #pragma unroll
@@ -1734,42 +1741,42 @@ __global__ void __launch_bounds__(256, 2) k_mt_kkt4(MtProblem P, MtState st) {
   const int cnt = wave == 0 ? q1 : (wave == 1 ? N - 2 - q3 : (wave == 2 ? m - 1 - q1 : q3 - m - 1));   // all >= 1 for N >= 16
   const int meet = (wave == 0 || wave == 2) ? q1 : q3;
   auto node = [&](int s_) { return asc ? first + s_ : first - s_; };
-  auto ld_e = [&](int j) { return asc ? ld(Eg + (size_t)j * 256) : ld_t(Eg + (size_t)(j - 1) * 256); };   // coupling to the next node of the front
+  auto ld_e = [&](int j) { return asc ? ld(Eg + (size_t)j * kMtBlk) : ld_t(Eg + (size_t)(j - 1) * kMtBlk); };   // coupling to the next node of the front
 
   int attempt = 0, fails = 0;
   bool ok = false;
   for (; attempt < 12 && !ok; ++attempt) {
     bool bad = false;
     int n_neg = 0;
-    MtBlk S = ld_t(Dg + (size_t)first * 256); shift(S);
+    MtBlk S = ld_t(Dg + (size_t)first * kMtBlk); shift(S);
     // the block M[target][first node]: E_{N-1}' , E_{N-2} (border), E_{m-1}, E_m' (middle)
-    MtBlk F = wave == 0 ? ld_t(Eg + (size_t)(N - 1) * 256) : (wave == 1 ? ld(Eg + (size_t)(N - 2) * 256)
-            : (wave == 2 ? ld(Eg + (size_t)(m - 1) * 256) : ld_t(Eg + (size_t)m * 256)));
+    MtBlk F = wave == 0 ? ld_t(Eg + (size_t)(N - 1) * kMtBlk) : (wave == 1 ? ld(Eg + (size_t)(N - 2) * kMtBlk)
+            : (wave == 2 ? ld(Eg + (size_t)(m - 1) * kMtBlk) : ld_t(Eg + (size_t)m * kMtBlk)));
     MtBlk SlC = zero, Tx = zero, Fx = zero;
     double rlC = 0.0, rx = 0.0;
     double rk[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) rk[r] = Rg[(size_t)first * 16 + 4 * r + q];
-    MtBlk eN = ld_e(first), dN = cnt > 1 ? ld_t(Dg + (size_t)node(1) * 256) : zero;
-    double rN = cnt > 1 ? Rg[(size_t)node(1) * 16 + i] : 0.0;
+    for (int r = 0; r < 4; ++r) rk[r] = Rg[(size_t)first * kMtNb + 4 * r + q];
+    MtBlk eN = ld_e(first), dN = cnt > 1 ? ld_t(Dg + (size_t)node(1) * kMtBlk) : zero;
+    double rN = cnt > 1 ? Rg[(size_t)node(1) * kMtNb + i] : 0.0;
     for (int s_ = 0; s_ < cnt && !bad; ++s_) {
       const int j = node(s_);
       const MtBlk E = eN, dC = dN;
       const double rC = rN;
       if (s_ + 1 < cnt) {
         eN = ld_e(node(s_ + 1));
-        dN = s_ + 2 < cnt ? ld_t(Dg + (size_t)node(s_ + 2) * 256) : zero;
-        rN = s_ + 2 < cnt ? Rg[(size_t)node(s_ + 2) * 16 + i] : 0.0;
+        dN = s_ + 2 < cnt ? ld_t(Dg + (size_t)node(s_ + 2) * kMtBlk) : zero;
+        rN = s_ + 2 < cnt ? Rg[(size_t)node(s_ + 2) * kMtNb + i] : 0.0;
       }
       const int neg = mt_invert(S, lane);
       if (neg < 0) { bad = true; break; }
       n_neg += neg;
       const double aj = mt_gemv(S, rk);
-      if (q == 0) vec[(size_t)j * 16 + i] = aj;
+      if (q == 0) vec[(size_t)j * kMtNb + i] = aj;
       const MtBlk Pm = mt_mul_t(S, E);
       const MtBlk Qm = mt_mul_t(S, F);
-      double* Bj = blk + (size_t)j * 3 * 256;
-      st_rm(Bj, Pm); st_rm(Bj + 256, Qm);
+      double* Bj = blk + (size_t)j * kMtBlkStride;
+      st_rm(Bj, Pm); st_rm(Bj + kMtBlk, Qm);
       rlC -= mt_gemv(Qm, rk);
       {
         const MtBlk U = mt_mul_t(F, Qm);
@@ -1798,17 +1805,17 @@ __global__ void __launch_bounds__(256, 2) k_mt_kkt4(MtProblem P, MtState st) {
     if (fronts_ok && wave < 2) {
       const int other = wave + 2;
       const MtBlk To = lds_get(X.T[other]), CL = Fx, Cm = lds_get(X.Fn[other]);   // M[L][meet] from the own front, M[m][meet] from the other
-      MtBlk Sq = ld_t(Dg + (size_t)meet * 256); shift(Sq);
+      MtBlk Sq = ld_t(Dg + (size_t)meet * kMtBlk); shift(Sq);
 #pragma unroll
       for (int r = 0; r < 4; ++r) Sq.v[r] += Tx.v[r] + To.v[r];
       double rqk[4];
-      mt_to_k(Rg[(size_t)meet * 16 + i] + rx + X.rn[other][i], q, rqk);
+      mt_to_k(Rg[(size_t)meet * kMtNb + i] + rx + X.rn[other][i], q, rqk);
       const int negq = mt_invert(Sq, lane);
       const double aq = mt_gemv(Sq, rqk);
-      if (q == 0) vec[(size_t)meet * 16 + i] = aq;
+      if (q == 0) vec[(size_t)meet * kMtNb + i] = aq;
       const MtBlk Qm = mt_mul_t(Sq, Cm), QL = mt_mul_t(Sq, CL);
-      double* Bq = blk + (size_t)meet * 3 * 256;
-      st_rm(Bq, Qm); st_rm(Bq + 256, QL);
+      double* Bq = blk + (size_t)meet * kMtBlkStride;
+      st_rm(Bq, Qm); st_rm(Bq + kMtBlk, QL);
       MtBlk dSm = mt_mul_t(Cm, Qm), dSL = mt_mul_t(CL, QL), dCc = mt_mul_t(Cm, QL);   // Qm Cm', QL CL', QL Cm'
 #pragma unroll
       for (int r = 0; r < 4; ++r) { dSm.v[r] = -dSm.v[r]; dSL.v[r] = -dSL.v[r]; dCc.v[r] = -dCc.v[r]; }
@@ -1821,8 +1828,8 @@ __global__ void __launch_bounds__(256, 2) k_mt_kkt4(MtProblem P, MtState st) {
     if (fronts_ok && wave == 0) {
       // ---- m, then the border
       bool okm = X.bad2[0] == 0 && X.bad2[1] == 0;
-      MtBlk Sm = ld_t(Dg + (size_t)m * 256); shift(Sm);
-      MtBlk Sl = ld_t(Dg + (size_t)L_ * 256); shift(Sl);
+      MtBlk Sm = ld_t(Dg + (size_t)m * kMtBlk); shift(Sm);
+      MtBlk Sl = ld_t(Dg + (size_t)L_ * kMtBlk); shift(Sl);
       MtBlk C;
       {
         const MtBlk a2 = lds_get(X.Sl[2]), a3 = lds_get(X.Sl[3]), d0 = lds_get(X.dSm[0]), d1 = lds_get(X.dSm[1]);
@@ -1836,17 +1843,17 @@ __global__ void __launch_bounds__(256, 2) k_mt_kkt4(MtProblem P, MtState st) {
         }
       }
       double rmk[4];
-      mt_to_k(Rg[(size_t)m * 16 + i] + X.rl[2][i] + X.rl[3][i] + X.drm[0][i] + X.drm[1][i], q, rmk);
-      double rl = Rg[(size_t)L_ * 16 + i] + rlC + X.rl[1][i] + X.drL[0][i] + X.drL[1][i];
+      mt_to_k(Rg[(size_t)m * kMtNb + i] + X.rl[2][i] + X.rl[3][i] + X.drm[0][i] + X.drm[1][i], q, rmk);
+      double rl = Rg[(size_t)L_ * kMtNb + i] + rlC + X.rl[1][i] + X.drL[0][i] + X.drL[1][i];
       int total = X.nneg[0] + X.nneg[1] + X.nneg[2] + X.nneg[3] + X.nneg2[0] + X.nneg2[1];
       const int negm = mt_invert(Sm, lane);
       if (negm < 0) okm = false;
       total += negm;
       const double am = mt_gemv(Sm, rmk);
-      if (q == 0) vec[(size_t)m * 16 + i] = am;
+      if (q == 0) vec[(size_t)m * kMtNb + i] = am;
       const MtBlk QLm = mt_mul_t(Sm, C);                // M[L][m] S_m^-1
-      double* Bm = blk + (size_t)m * 3 * 256;
-      st_rm(Bm, zero); st_rm(Bm + 256, QLm);
+      double* Bm = blk + (size_t)m * kMtBlkStride;
+      st_rm(Bm, zero); st_rm(Bm + kMtBlk, QLm);
       rl -= mt_gemv(QLm, rmk);
       {
         const MtBlk U = mt_mul_t(C, QLm);
@@ -1875,7 +1882,7 @@ __global__ void __launch_bounds__(256, 2) k_mt_kkt4(MtProblem P, MtState st) {
   }
   if (threadIdx.x == 0) { scal[1] = delta; scal[10] += (double)fails; }   // refactorisations = failed attempts (also on the give-up path)
   if (!ok) {
-    if (threadIdx.x == 0) scal[5] = 2.0;
+    if (threadIdx.x == 0) scal[kMtStatus] = 2.0;
     return;
   }
   // ---- back substitution.  Wave 0: x_L, x_m = a_m - Q_m' x_L, x_q = a_q - Qm_q' x_m - QL_q' x_L for q1 and q3
@@ -1887,8 +1894,8 @@ __global__ void __launch_bounds__(256, 2) k_mt_kkt4(MtProblem P, MtState st) {
   };
   if (wave == 0 && lane < 16) {
     put_x(L_, X.xL[lane]);
-    const double* Qg = blk + (size_t)m * 3 * 256 + 256;
-    double xm = vec[(size_t)m * 16 + lane];
+    const double* Qg = blk + (size_t)m * kMtBlkStride + kMtBlk;
+    double xm = vec[(size_t)m * kMtNb + lane];
 #pragma unroll
     for (int k = 0; k < 16; ++k) xm = fma(-Qg[k * 16 + lane], X.xL[k], xm);
     X.xm[lane] = xm;
@@ -1897,10 +1904,10 @@ __global__ void __launch_bounds__(256, 2) k_mt_kkt4(MtProblem P, MtState st) {
   mt_wave_sync();
   if (wave == 0 && lane < 32) {   // lanes 0..15: q1, lanes 16..31: q3
     const int which = lane >> 4, c = lane & 15, jq = which ? q3 : q1;
-    const double* Pg = blk + (size_t)jq * 3 * 256;   // Qm (towards m), then QL
-    double x = vec[(size_t)jq * 16 + c];
+    const double* Pg = blk + (size_t)jq * kMtBlkStride;   // Qm (towards m), then QL
+    double x = vec[(size_t)jq * kMtNb + c];
 #pragma unroll
-    for (int k = 0; k < 16; ++k) x = fma(-Pg[k * 16 + c], X.xm[k], fma(-Pg[256 + k * 16 + c], X.xL[k], x));
+    for (int k = 0; k < 16; ++k) x = fma(-Pg[k * 16 + c], X.xm[k], fma(-Pg[kMtBlk + k * 16 + c], X.xL[k], x));
     X.xq[which][c] = x;
     if (c < kMtNv) dw[(size_t)jq * kMtNv + c] = x;
     else dy[(size_t)jq * kMtNe + c - kMtNv] = x;
@@ -1915,11 +1922,11 @@ __global__ void __launch_bounds__(256, 2) k_mt_kkt4(MtProblem P, MtState st) {
     for (int j0 = j_lo; j0 < j_hi; j0 += 4) {
       const int j = j0 + q;
       if (j < j_hi) {
-        const double* Qg = blk + (size_t)j * 3 * 256 + 256;
-        double acc = vec[(size_t)j * 16 + i];
+        const double* Qg = blk + (size_t)j * kMtBlkStride + kMtBlk;
+        double acc = vec[(size_t)j * kMtNb + i];
 #pragma unroll
         for (int k = 0; k < 16; ++k) acc = fma(-Qg[k * 16 + i], xt[k], acc);
-        blk[(size_t)j * 3 * 256 + 512 + i] = acc;
+        blk[(size_t)j * kMtBlkStride + 2 * kMtBlk + i] = acc;
       }
     }
   }
@@ -1931,10 +1938,10 @@ __global__ void __launch_bounds__(256, 2) k_mt_kkt4(MtProblem P, MtState st) {
   double pb[4][17];
   auto fetch = [&](double (&dst)[17], int s_) {
     if (s_ < steps && lane < 16) {
-      const double* Bn = blk + (size_t)chain_node(s_) * 3 * 256;
+      const double* Bn = blk + (size_t)chain_node(s_) * kMtBlkStride;
 #pragma unroll
       for (int k = 0; k < 16; ++k) dst[k] = Bn[k * 16 + lane];
-      dst[16] = Bn[512 + lane];
+      dst[16] = Bn[2 * kMtBlk + lane];
     }
   };
   fetch(pb[0], 0); fetch(pb[1], 1); fetch(pb[2], 2);
@@ -1964,8 +1971,8 @@ __global__ void __launch_bounds__(256, 2) k_mt_kkt4(MtProblem P, MtState st) {
 // residuals only (final report of the instances that ran into the iteration limit)
 __global__ void __launch_bounds__(64) k_mt_residuals(MtProblem P, MtState st) {
   const int b = blockIdx.x, lane = threadIdx.x, N = P.N;
-  double* scal = st.scal + (size_t)b * 16;
-  if (scal[5] == 1.0) return;
+  double* scal = st.scal + (size_t)b * kMtScal;
+  if (scal[kMtStatus] == 1.0) return;
   mt_instance(P, b);
   double kkt, viol, compl_, errmu, lap;
   mt_residuals(P, st.w + (size_t)b * N * kMtNv, st.s + (size_t)b * N * kMtNi, st.y + (size_t)b * N * kMtNe,
@@ -1993,9 +2000,9 @@ __device__ __forceinline__ MtStepPtrs mt_step_ptrs(const MtState& st, int b, int
   MtStepPtrs q;
   q.w = st.w + (size_t)b * N * kMtNv; q.sv = st.s + (size_t)b * N * kMtNi; q.yv = st.y + (size_t)b * N * kMtNe;
   q.zv = st.z + (size_t)b * N * kMtNi; q.dw = st.dw + (size_t)b * N * kMtNv; q.dy = st.dy + (size_t)b * N * kMtNe;
-  q.ds = st.blk + (size_t)b * N * 3 * 256;   // [N,17] ds, then [N,17] dz (the factor blocks are dead now)
+  q.ds = st.blk + (size_t)b * N * kMtBlkStride;   // [N,17] ds, then [N,17] dz (the factor blocks are dead now)
   q.dz = q.ds + (size_t)N * kMtNi;
-  q.scal = st.scal + (size_t)b * 16; q.filt = st.filt + (size_t)b * 2 * kMtFilter;
+  q.scal = st.scal + (size_t)b * kMtScal; q.filt = st.filt + (size_t)b * 2 * kMtFilter;
   return q;
 }
 
@@ -2054,10 +2061,14 @@ __device__ __forceinline__ void mt_take_step(const MtState& st, const MtStepPtrs
 // grid (blocks of 64 rows, B): one inequality row per thread: ds = -r_g - G dw, dz = -(s z - mu + z ds) / s, and the wave's
 // share of (ap, ad, theta0, phi0) -> part[b][block][4]  (part = the start of the instance's derivative work array hw, dead after k_mt_node)
 constexpr int kMtDirBlocks(int N) { return (N * kMtNi + 63) / 64; }
+constexpr int mt_row_blocks(int N) { return (N + 63) / 64; }                          // blocks along x of the other grids: one thread per node
+constexpr int mt_jac_blocks(int N) { return (N + kMtJacNodes - 1) / kMtJacNodes; }    // k_mt_jac_dirs
+constexpr int mt_node_blocks(int N) { return ((N + kMtRun - 1) / kMtRun + kMtNodeGroups - 1) / kMtNodeGroups; }   // k_mt_node
+constexpr int mt_init_blocks(int N) { return (N * kMtNi + 255) / 256; }               // k_mt_init
 __global__ void __launch_bounds__(64) k_mt_dir(MtProblem P, MtState st) {
   const int b = blockIdx.y, N = P.N, idx = blockIdx.x * 64 + threadIdx.x;
   const MtStepPtrs q = mt_step_ptrs(st, b, N);
-  if (q.scal[5] != 0.0) return;
+  if (q.scal[kMtStatus] != 0.0) return;
   double ap = 1.0, ad = 1.0, th = 0.0, ph = 0.0;
   if (idx < N * kMtNi) {
     const double* fun = st.fun + (size_t)b * N * kMtNf;
@@ -2131,7 +2142,7 @@ constexpr int kMtTrials = RL_MT_TRIALS;
 __global__ void __launch_bounds__(64) k_mt_trial(MtProblem P, MtState st) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y, N = P.N;
   const MtStepPtrs q = mt_step_ptrs(st, b, N);
-  if (q.scal[5] != 0.0) return;
+  if (q.scal[kMtStatus] != 0.0) return;
   // the primal step length: every workgroup takes the minimum over the shares of k_mt_dir itself (220 values; a minimum does not depend on the order)
   double ap = 1.0;
   {
@@ -2141,7 +2152,7 @@ __global__ void __launch_bounds__(64) k_mt_trial(MtProblem P, MtState st) {
   }
   if (j >= N) return;
   mt_instance(P, b);
-  double* o = st.vec + ((size_t)b * N + j) * 16;
+  double* o = st.vec + ((size_t)b * N + j) * kMtNb;
   double a = ap;
   const double mu = q.scal[0];
   for (int k = 0; k < kMtTrials; ++k) {
@@ -2167,7 +2178,7 @@ __global__ void __launch_bounds__(256, 2) k_mt_step(MtProblem P, MtState st) {
   __shared__ double red[(4 + 2 * kMtTrials) * 4];
   const int b = blockIdx.x, tid = threadIdx.x, N = P.N;
   const MtStepPtrs q = mt_step_ptrs(st, b, N);
-  if (q.scal[5] != 0.0) return;
+  if (q.scal[kMtStatus] != 0.0) return;
   mt_instance(P, b);
   // ---- the step lengths and (theta0, phi0) of the current point from the shares of k_mt_dir
   double ap = 1.0, ad = 1.0, theta0 = 0.0, phi0 = 0.0;
@@ -2190,9 +2201,9 @@ __global__ void __launch_bounds__(256, 2) k_mt_step(MtProblem P, MtState st) {
     }
   }
   // ---- the trial point of k_mt_trial
-  double* tp = st.vec + (size_t)b * N * 16;
+  double* tp = st.vec + (size_t)b * N * kMtNb;
   double th0 = 0.0, ph0 = 0.0;
-  for (int j = tid; j < N; j += 256) { th0 += tp[(size_t)j * 16]; ph0 += tp[(size_t)j * 16 + 1]; }
+  for (int j = tid; j < N; j += 256) { th0 += tp[(size_t)j * kMtNb]; ph0 += tp[(size_t)j * kMtNb + 1]; }
   {
     double v[6] = {ap, ad, theta0, phi0, th0, ph0};
     const int op[6] = {1, 1, 0, 0, 0, 0};
@@ -2214,12 +2225,12 @@ __global__ void __launch_bounds__(256, 2) k_mt_step(MtProblem P, MtState st) {
 __global__ void __launch_bounds__(64) k_mt_trial_b(MtProblem P, MtState st) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y, N = P.N;
   const MtStepPtrs q = mt_step_ptrs(st, b, N);
-  if (q.scal[5] != 0.0 || q.scal[15] == 0.0) return;
+  if (q.scal[kMtStatus] != 0.0 || q.scal[15] == 0.0) return;
   if (j >= N) return;
   mt_instance(P, b);
-  const double ap = st.vec[(size_t)b * N * 16 + kMtStash];
+  const double ap = st.vec[(size_t)b * N * kMtNb + kMtStash];
   const double mu = q.scal[0];
-  double* o = st.vec + ((size_t)b * N + j) * 16;
+  double* o = st.vec + ((size_t)b * N + j) * kMtNb;
   double a = 0.5 * ap;
   for (int k = 1; k <= 2; ++k) {
     double theta = 0.0, phi = 0.0;
@@ -2233,15 +2244,15 @@ __global__ void __launch_bounds__(256, 2) k_mt_step_b(MtProblem P, MtState st) {
   __shared__ double red[4 * 4];
   const int b = blockIdx.x, tid = threadIdx.x, N = P.N;
   const MtStepPtrs q = mt_step_ptrs(st, b, N);
-  if (q.scal[5] != 0.0 || q.scal[15] == 0.0) return;
+  if (q.scal[kMtStatus] != 0.0 || q.scal[15] == 0.0) return;
   mt_instance(P, b);
   const double mu = q.scal[0];
-  const double* tp = st.vec + (size_t)b * N * 16;
+  const double* tp = st.vec + (size_t)b * N * kMtNb;
   const double ap = tp[kMtStash], ad = tp[kMtStash + 1], theta0 = tp[kMtStash + 2], phi0 = tp[kMtStash + 3];
   double th[2] = {0.0, 0.0}, ph[2] = {0.0, 0.0};
   for (int j = tid; j < N; j += 256) {
 #pragma unroll
-    for (int k = 0; k < 2; ++k) { th[k] += tp[(size_t)j * 16 + 2 + 2 * k]; ph[k] += tp[(size_t)j * 16 + 3 + 2 * k]; }
+    for (int k = 0; k < 2; ++k) { th[k] += tp[(size_t)j * kMtNb + 2 + 2 * k]; ph[k] += tp[(size_t)j * kMtNb + 3 + 2 * k]; }
   }
   {
     double v[4] = {th[0], ph[0], th[1], ph[1]};
@@ -2282,7 +2293,7 @@ __global__ void __launch_bounds__(256, 2) k_mt_step_b(MtProblem P, MtState st) {
     // no acceptable step: more damping, same point (the next iteration re-solves with the larger delta)
     const double delta = fmax(10.0 * q.scal[1], 1e-4);
     __syncthreads();
-    if (tid == 0) { q.scal[1] = delta; q.scal[7] = 0.0; q.scal[6] += 1.0; if (delta > 1e6) q.scal[5] = 2.0; }
+    if (tid == 0) { q.scal[1] = delta; q.scal[7] = 0.0; q.scal[6] += 1.0; if (delta > 1e6) q.scal[kMtStatus] = 2.0; }
     RL_MT_COUNT(12);
     return;
   }
@@ -2315,9 +2326,9 @@ __global__ void k_mt_unpack(MtProblem P, MtState st, double* X, double* U, doubl
 __global__ void k_mt_stats(MtState st, double* stats) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= st.B) return;
-  const double* q = st.scal + (size_t)b * 16;
-  double* o = stats + (size_t)b * 12;
-  o[0] = q[6]; o[1] = q[2]; o[2] = q[3]; o[3] = q[4]; o[4] = q[11]; o[5] = q[5]; o[6] = q[0]; o[7] = q[1];
+  const double* q = st.scal + (size_t)b * kMtScal;
+  double* o = stats + (size_t)b * kMtStats;
+  o[0] = q[6]; o[1] = q[2]; o[2] = q[3]; o[3] = q[4]; o[4] = q[11]; o[5] = q[kMtStatus]; o[6] = q[0]; o[7] = q[1];
   o[8] = q[7]; o[9] = q[10]; o[10] = q[12]; o[11] = q[13];
 }
 
@@ -2332,7 +2343,7 @@ __global__ void k_mt_init(MtProblem P, MtState st, double mu0, double delta0) {
     st.z[(size_t)b * N * kMtNi + idx] = mu0 / s;
   }
   if (idx < N * kMtNe) st.y[(size_t)b * N * kMtNe + idx] = 0.0;
-  if (idx < 16) st.scal[(size_t)b * 16 + idx] = idx == 0 ? mu0 : (idx == 1 ? delta0 : 0.0);
+  if (idx < kMtScal) st.scal[(size_t)b * kMtScal + idx] = idx == 0 ? mu0 : (idx == 1 ? delta0 : 0.0);
 }
 
 }  // namespace rl

@@ -14,6 +14,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MGKT = os.path.join(ROOT, "spline_trajectory_optimization_amd", "examples", "race_track", "mgkt")
 
 
+def width_scales(B):
+    """Per-instance track-width factors of a test batch: a fixed seed, within +-8 %."""
+    return 1.0 + np.random.default_rng(2024).uniform(-0.08, 0.08, size=B)
+
+
 def _load(name):
     return np.loadtxt(os.path.join(MGKT, name), delimiter=",", skiprows=1, usecols=(0, 1))
 

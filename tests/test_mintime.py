@@ -7,7 +7,7 @@ track widths, and its argument checks."""
 import numpy as np
 import pytest
 
-from mintime_problem import mgkt_problem
+from mintime_problem import mgkt_problem, width_scales
 from oracle import dt_checker as dc
 from oracle import sqp_twin as tw
 from spline_trajectory_optimization_amd.min_time_optm import defaults
@@ -252,6 +252,55 @@ def test_mintime_batch_with_per_instance_widths(coarse):
 
 
 @pytest.mark.gpu
+def test_sub_batch_streams_do_not_change_the_result(tmp_path):
+    """The solve splits a batch into sub-batches on as many streams (RL_MT_GROUPS, default 3, when B >= 4 x groups); instances
+    are independent, so the split changes no result.  B = 13 is the smallest uneven batch that forks three groups (slices of
+    4, 4 and 5 instances): after 12 iterations everything the call returns equals, bit for bit, what one stream gives.
+    (Each library instance reads the switch when its context is created: two processes.)"""
+    import os
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    out = {}
+    for groups in ("1", "3"):
+        f = str(tmp_path / f"grp_{groups}.npz")
+        env = dict(os.environ, RL_MT_GROUPS=groups)
+        subprocess.run([sys.executable, os.path.join(here, "mintime_run.py"), f, "12", "8.0", "1e-12", "13"], check=True, env=env, timeout=300)
+        out[groups] = np.load(f)
+    a, b = out["1"], out["3"]
+    assert a["X"].shape[0] == 13 and (a["st"][:, 0] == 12.0).all()
+    for key in ("X", "U", "T", "st"):
+        np.testing.assert_array_equal(a[key], b[key], err_msg=key)
+
+
+@pytest.mark.gpu
+def test_host_entry_point_equals_the_device_one_on_a_forked_batch(coarse):
+    """rl_mintime_solve_batch polls the status words every 8 iterations and stops enqueueing once every instance has
+    finished; rl_mintime_solve_batch_dev enqueues all max_iter iterations without waiting.  A finished instance's kernels
+    return at their first line, so on a batch that forks three sub-batches (B = 13) both return identical bits and identical
+    iteration counts, and every instance converges."""
+    import torch
+    from spline_trajectory_optimization_amd import ops
+    d, P, w0 = coarse
+    X0, U0, T0 = P.unpack(w0)
+    B = 13
+    left = P.left[None] * width_scales(B)[:, None]; right = P.right[None] * width_scales(B)[:, None]
+    rep = lambda a: np.repeat(a[None], B, axis=0)  # noqa: E731
+    Xh, Uh, Th, sth = ops.mintime_solve_batch(P.m, P.s, P.kappa, left, right, P.margin, P.L, rep(X0), rep(U0), rep(T0),
+                                              max_iter=200, tol=1e-6)
+    dev = torch.device("cuda", 0)
+    g = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    X, U, T = g(rep(X0)), g(rep(U0)), g(rep(T0))
+    st = ops.mintime_solve_torch(P.m, g(P.s), g(P.kappa), g(left), g(right), P.margin, P.L, X, U, T, max_iter=200, tol=1e-6)
+    torch.cuda.synchronize()
+    print("host / device entry point: iterations", sth[:, 0], st.cpu().numpy()[:, 0])
+    assert (sth[:, 5] == 1.0).all() and sth[:, 0].max() < 200
+    np.testing.assert_array_equal(st.cpu().numpy(), sth)      # all 12 columns of the report
+    np.testing.assert_array_equal(X.cpu().numpy(), Xh); np.testing.assert_array_equal(U.cpu().numpy(), Uh)
+    np.testing.assert_array_equal(T.cpu().numpy(), Th)
+
+
+@pytest.mark.gpu
 def test_reference_pipeline_on_the_example_track():
     """The reference CLI's pipeline (entrypoints/traj_opt_double_track.py:24-86) through the mirror classes at the
     example's own resolution (MGKT, interval 1 m, yaml defaults): RaceTrack + interpolants -> QSS warm start on
@@ -493,7 +542,7 @@ def test_cli_lines_against_the_facade(tmp_path):
 def test_dev_calls_on_two_torch_streams_do_not_share_scratch(coarse):
     """The *_dev entry points carve their work arrays out of ONE arena per context, from offset 0.  Two solves enqueued on
     DIFFERENT torch streams without a host synchronisation in between must still run one after the other on that scratch
-    (rl_mincurv.hip: Arena::begin orders a call behind the arena's previous user with an event when the stream has
+    (rl_host.hpp: Arena::carve orders a call behind the arena's previous user with an event when the stream has
     changed): both give, bit for bit, what they give when run alone."""
     import torch
     from spline_trajectory_optimization_amd import ops

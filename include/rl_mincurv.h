@@ -123,8 +123,9 @@ int rl_ctx_set_numpy_raise(rl_ctx* ctx, int on);
  *   "qss_df_waves"    1 | 2 | 4 waves per instance of the dataflow kernel (default 4)
  *   "qss_df_bail_at"  g > 0: the dataflow kernel hands every instance back to the list-order kernel at iteration g (the path
  *                     taken when its tables overflow); 0 = never
- *   "tables_search"   RL_SEARCH_BRUTE | _CULLED | _WINDOWED (default): ring search of rl_tables_batch_*
- *   "tables_rings"    0 = rl_tables_batch_* keeps an instance's ring vertices in LDS where they fit (default), 1 = in the arena
+ *   "tables_search"   RL_SEARCH_BRUTE | _CULLED | _WINDOWED (default): ring search of rl_tables_batch_* and rl_pose_tables_batch_*
+ *   "tables_rings"    0 = rl_tables_batch_* and rl_pose_tables_batch_* keep an instance's ring vertices in LDS where they fit
+ *                     (default), 1 = in the arena
  * Defaults come from RL_QSS_DF / RL_QSS_V1 / RL_QSS_DF_WAVES / RL_QSS_DF_BAIL_AT, read ONCE in rl_ctx_create. */
 int rl_ctx_set_option(rl_ctx* ctx, const char* name, int value);
 /* test aid: out[n,5] = yaw, cos / sin(yaw + pi/2), cos / sin(yaw - pi/2) of the tangents (dx, dy), as the
@@ -407,7 +408,8 @@ int rl_qss_sim(rl_ctx* ctx, double* points, int B, int N, const double* acc_x, c
                int* iters);
 /* Same with DEVICE pointers for points and iters (the lookup tables and params stay small host arrays):
  * enqueued on the context's stream, no synchronisation, scratch from the context's grow-only arena -- so that
- * QSS warm start -> initial guess -> rl_mintime_solve_batch_dev chain on the GPU without a host round trip. */
+ * QSS warm start -> initial guess -> rl_mintime_solve_batch_dev -> rl_pose_tables_batch_dev -> rl_table_summary_dev chain
+ * on the GPU without a host round trip: from the centre-line table to the solved batch's tables and lap times. */
 int rl_qss_sim_dev(rl_ctx* ctx, double* points, int B, int N, const double* acc_x, const double* acc_c,
                    int acc_m, const double* dcc_x, const double* dcc_c, int dcc_m, const double* params,
                    int* iters);
@@ -434,6 +436,38 @@ int rl_tables_batch_dev(rl_ctx* ctx, const rl_track* trk, const double* ctrl, in
                         double length, const double* bank, int bank_per_instance, double* points);
 int rl_tables_batch_host(rl_ctx* ctx, const rl_track* trk, const double* ctrl, int B, int bounds_form, const double* bounds,
                          double length, const double* bank, int bank_per_instance, double* points);
+
+/* ---- tables of a batch of poses (csrc/rl_pose_tables.hpp): the tail of the reference's min-time pipeline
+ * (entrypoints/traj_opt_double_track.py:75-82) for the B solutions of rl_mintime_solve_batch_* or rl_bicycle_solve_batch_*,
+ * one launch for the batch.  Per instance: the pose (x, y, phi) of every node, X / Y / YAW / SPEED into a copy of `base`,
+ * Trajectory.fill_bounds along the table's own YAW against the instance's rings (max_dist 100), Trajectory.fill_distance
+ * (chords between consecutive nodes, the last back to node 0, added up in index order).
+ *   form        RL_POSE_FRENET: X [B,N,6] = (s, n, xi, ., ., v), RaceTrack.frenet_to_global on the centre line's periodic
+ *               piecewise cubics x(s), y(s), given as scipy CubicSpline pieces like rl_qss_sim's tables: breakpoints
+ *               ss[M+1] (ss[M] = track length), coefficients cxs[4][M], cys[4][M], c[0] = cubic term; s is wrapped into [0, L).
+ *               RL_POSE_GLOBAL: X [B,N,5] = (x, y, theta, ., v) taken as they are (YAW = theta unchanged, unwrapped or not);
+ *               ss / cxs / cys may be NULL.
+ *   N           nodes per instance, independent of the ring sizes
+ *   bounds_form / bounds  the instance's rings as for rl_tables_batch_dev; the WIDTHS [B,trk->N,2] and POINTS [B,trk->N,4]
+ *               forms make rings of trk->N vertices
+ *   base        NULL, [N,19] or (base_per_instance != 0) [B,N,19]: every column this call does not compute; NULL: IDX = i,
+ *               ITERATION_FLAG = -1, the others 0
+ *   T           NULL or [B,N], the duration of the step that STARTS at node i: TIME[(i+1) % N] = T[b,i] (Trajectory.fill_time's
+ *               convention, so that rl_table_summary_* returns the NLP's lap time); NULL: TIME as in `base`
+ *   points      [B,N,19] out
+ * RL_ERR_ARG for nulls, B <= 0, N < 2, FRENET without pieces, WIDTHS / POINTS without `bounds`, SHARED_RINGS without rings.
+ * An instance's poses and chords are LDS resident (32 B per node next to 44 KiB of row staging and the chunk tables of the
+ * rings): N up to about 3400 nodes with the rings in the arena, RL_ERR_UNSUPPORTED beyond.
+ * *_dev: device pointers throughout (the pieces too), enqueued on the context's stream, no synchronisation; rings that do not
+ * fit LDS live in the context's grow-only arena.  *_host: host pointers, synchronises.  The test hooks "tables_search" and
+ * "tables_rings" apply (bit-identical results). */
+enum { RL_POSE_FRENET = 0, RL_POSE_GLOBAL = 1 };
+int rl_pose_tables_batch_dev(rl_ctx* ctx, const rl_track* trk, int form, const double* X, int B, int N, const double* ss,
+                             const double* cxs, const double* cys, int M, int bounds_form, const double* bounds,
+                             const double* base, int base_per_instance, const double* T, double* points);
+int rl_pose_tables_batch_host(rl_ctx* ctx, const rl_track* trk, int form, const double* X, int B, int N, const double* ss,
+                              const double* cxs, const double* cys, int M, int bounds_form, const double* bounds,
+                              const double* base, int base_per_instance, const double* T, double* points);
 
 /* Per-instance summary of simulated tables points [B,N,19]: out [B,8] = lap time (sum of TIME, added in index order), the
  * reference's total_time (TIME[0], simulator.py:378), its average_speed (DIST_TO_SF_FWD[0] / TIME[0], :379-380), max / min

@@ -16,6 +16,7 @@ NCOL = 19
 MAX_ITER = 32
 BOUNDS_SHARED_RINGS, BOUNDS_WIDTHS, BOUNDS_POINTS = 0, 1, 2
 SEARCH_BRUTE, SEARCH_CULLED, SEARCH_WINDOWED = 0, 1, 2
+POSE_FRENET, POSE_GLOBAL = 0, 1   # include/rl_mincurv.h: RL_POSE_*
 ARITH_DEFAULT, ARITH_FAST, ARITH_REFERENCE, ARITH_BRANCH = -1, 0, 1, 2   # include/rl_mincurv.h: RL_ARITH_*
 
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -105,6 +106,10 @@ _SIGNATURES = {
                                            ctypes.c_int, _vp]),
     "rl_tables_batch_host": (ctypes.c_int, [_vp, _vp, _dp, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_double, _dp,
                                             ctypes.c_int, _dp]),
+    "rl_pose_tables_batch_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp,
+                                                ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp]),
+    "rl_pose_tables_batch_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp,
+                                                 ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_int, _dp, _dp]),
     "rl_table_summary_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp]),
     "rl_table_summary_host": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _ip, _dp]),
 }

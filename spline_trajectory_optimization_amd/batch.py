@@ -162,6 +162,24 @@ def lap_times_host(track, ctrl, bounds_form, bounds, length, vehicle, bank=None)
     return {k_: v.cpu().numpy() for k_, v in out.items()}
 
 
+def min_time_tables_torch(race_track, track, X, T, bounds_form, bounds, base=None, pieces=None):
+    """Tables of a batch the min-time solve returned (ops.mintime_solve_torch): X [B,N,6] in race_track's curvilinear frame, T
+    [B,N] -> points [B,N,19] with X, Y, YAW, SPEED, the bounds, the distances and TIME filled (ops.pose_tables_torch, form
+    POSE_FRENET), every other column from `base` ([N,19] or [B,N,19], e.g. the QSS table the solve started from).
+    bounds_form / bounds as for ops.pose_tables_torch (rings of track.N vertices in the widths / points forms).  pieces:
+    race_track.centerline_pieces() as cuda tensors on X's device; None uploads them with this call (three small copies), so a
+    caller that makes many calls passes its own.  Enqueues on torch's current stream, no sync.  Returns the cuda tensor."""
+    import torch
+    if pieces is None:
+        pieces = tuple(torch.from_numpy(a).to(X.device) for a in race_track.centerline_pieces())
+    return ops.pose_tables_torch(track, _lib.POSE_FRENET, X, pieces, bounds_form, bounds, base=base, T=T)
+
+
+def min_time_tables_host(race_track, track, X, T, bounds_form, bounds, base=None):
+    """min_time_tables_torch for numpy input (float64, C-contiguous): rl_pose_tables_batch_host.  Returns points [B,N,19]."""
+    return ops.pose_tables_host(track, _lib.POSE_FRENET, X, race_track.centerline_pieces(), bounds_form, bounds, base=base, T=T)
+
+
 # ---------------------------------------------------------------- min-time NLP plumbing (config 5)
 def min_time_initial_guess(points):
     """The initial guess the reference hands to its min-time NLP when no previous solution is given

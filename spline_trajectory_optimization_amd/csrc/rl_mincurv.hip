@@ -23,6 +23,7 @@
 #include "rl_bicycle.hpp"
 #include "rl_region.hpp"
 #include "rl_tables.hpp"
+#include "rl_pose_tables.hpp"
 
 namespace {
 double* g_dbg_buf = nullptr;   // rl_debug_dump_enable: step / window dump of the sweep kernels (tests)
@@ -1193,6 +1194,83 @@ int rl_tables_batch_host(rl_ctx* ctx, const rl_track* trk, const double* ctrl, i
   const double* din = cols ? sg.in(bounds, (size_t)B * N * cols) : nullptr;
   const double* dbank = sg.in(bank, (size_t)(bank_per_instance ? B : 1) * N);
   sg.run([&] { return rl_tables_batch_dev(ctx, trk, dctrl, B, bounds_form, din, length, dbank, bank_per_instance, dpts); });
+  return sg.finish();
+}
+
+// tables of a batch of poses: the tail of the reference's min-time pipeline (csrc/rl_pose_tables.hpp)
+static int pose_tables_check(const rl_ctx* ctx, const rl_track* trk, int form, const double* X, int B, int N, const double* ss,
+                             const double* cxs, const double* cys, int M, int bounds_form, const double* bounds,
+                             const double* points) {
+  if (!ctx || !trk || !X || !points) return fail(RL_ERR_ARG, "null argument");
+  if (B <= 0 || N < 2) return fail(RL_ERR_ARG, "bad sizes");
+  if (form != RL_POSE_FRENET && form != RL_POSE_GLOBAL) return fail(RL_ERR_ARG, "bad pose form");
+  if (form == RL_POSE_FRENET && (!ss || !cxs || !cys || M < 1)) return fail(RL_ERR_ARG, "RL_POSE_FRENET needs the centre line's pieces");
+  if (bounds_form != RL_BOUNDS_SHARED_RINGS && bounds_form != RL_BOUNDS_WIDTHS && bounds_form != RL_BOUNDS_POINTS)
+    return fail(RL_ERR_ARG, "bad bounds_form");
+  if (bounds_cols(bounds_form) && !bounds) return fail(RL_ERR_ARG, "bounds input is null");
+  return RL_OK;
+}
+
+int rl_pose_tables_batch_dev(rl_ctx* ctx, const rl_track* trk, int form, const double* X, int B, int N, const double* ss,
+                             const double* cxs, const double* cys, int M, int bounds_form, const double* bounds,
+                             const double* base, int base_per_instance, const double* T, double* points) {
+  RL_TRY(pose_tables_check(ctx, trk, form, X, B, N, ss, cxs, cys, M, bounds_form, bounds, points));
+  rl::PoseTablesArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.form = form; a.X = X; a.B = B; a.N = N;
+  a.ss = ss; a.cxs = cxs; a.cys = cys; a.M = M;
+  a.bounds_form = bounds_form; a.in = bounds;
+  Bounds bd;
+  if (int rc = resolve_bounds(trk, bounds_form, bounds, bd)) return rc;
+  a.ringL = bd.ringL; a.ringR = bd.ringR; a.nL = bd.nL; a.nR = bd.nR;
+  RL_HIP(hipSetDevice(ctx->device));
+  if (bounds_form == RL_BOUNDS_WIDTHS) {   // the rings rl_tables_batch_dev builds from the same widths
+    if (!degree_supported(trk->k)) return fail(RL_ERR_UNSUPPORTED, "spline degree must be 3 or 5");
+    if (trk->k == 5 && ctx->arith != RL_ARITH_FAST) {
+      if (int rc = ensure_strict_tables(ctx, trk)) return rc;
+      a.strict_rings = 1;
+    }
+  }
+  a.tr = trk->dev();
+  a.search = ctx->tables_search;
+  a.max_dist = 100.0;   // race_track.py: fill_trajectory_boundaries
+  a.base = base; a.base_per_instance = base_per_instance;
+  a.T = T;
+  a.points = points;
+  bool rings_lds = !ctx->tables_rings_global;
+  size_t lds = rl::pose_lds_layout(N, a.nL, a.nR, true).total * sizeof(double);
+  if (lds > (size_t)ctx->max_lds) rings_lds = false;
+  if (!rings_lds) lds = rl::pose_lds_layout(N, a.nL, a.nR, false).total * sizeof(double);
+  if (lds > (size_t)ctx->max_lds) return fail(RL_ERR_UNSUPPORTED, "pose tables: the instance's poses do not fit LDS");
+  Arena ar(ctx);
+  if (!rings_lds) {
+    a.gscratch_stride = rl::tables_ring_scratch_doubles(a.nL, a.nR);
+    RL_HIP(ar.carve([&](Arena& x) { a.gscratch = x.take<double>(a.gscratch_stride * (size_t)B); }));
+  }
+  const dim3 grid(B), block(rl::kTablesThreads);
+  RL_TRY(rings_lds ? launch(ctx, rl::k_pose_tables<true>, grid, block, lds, a) : launch(ctx, rl::k_pose_tables<false>, grid, block, lds, a));
+  if (!rings_lds) RL_HIP(ar.end());
+  return RL_OK;
+}
+
+int rl_pose_tables_batch_host(rl_ctx* ctx, const rl_track* trk, int form, const double* X, int B, int N, const double* ss,
+                              const double* cxs, const double* cys, int M, int bounds_form, const double* bounds,
+                              const double* base, int base_per_instance, const double* T, double* points) {
+  RL_TRY(pose_tables_check(ctx, trk, form, X, B, N, ss, cxs, cys, M, bounds_form, bounds, points));
+  const int cols = bounds_cols(bounds_form);
+  const bool frenet = form == RL_POSE_FRENET;
+  Staging sg(ctx);
+  const double* dX = sg.in(X, (size_t)B * N * (frenet ? 6 : 5));
+  const double* dss = frenet ? sg.in(ss, (size_t)M + 1) : nullptr;
+  const double* dcx = frenet ? sg.in(cxs, (size_t)4 * M) : nullptr;
+  const double* dcy = frenet ? sg.in(cys, (size_t)4 * M) : nullptr;
+  const double* din = cols ? sg.in(bounds, (size_t)B * trk->N * cols) : nullptr;
+  const double* dbase = sg.in(base, (size_t)(base_per_instance ? B : 1) * N * RL_NCOL);
+  const double* dT = sg.in(T, (size_t)B * N);
+  double* dpts = sg.out(points, (size_t)B * N * RL_NCOL);
+  sg.run([&] {
+    return rl_pose_tables_batch_dev(ctx, trk, form, dX, B, N, dss, dcx, dcy, M, bounds_form, din, dbase, base_per_instance, dT, dpts);
+  });
   return sg.finish();
 }
 

@@ -99,6 +99,142 @@ __device__ __forceinline__ void wave_lds_sync() {   // the LDS writes of this wa
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// ---- what k_tables and k_pose_tables (rl_pose_tables.hpp) share: the prologue that makes an instance's rings searchable,
+// the hint of the windowed search along a run of samples, and the way a tile of rows leaves for global memory.
+
+// The instance's ring vertices into rL / rR (LDS or the arena), as k_sweep's prologue builds them, with the first kRingPad
+// vertices repeated behind the last.  form = RL_BOUNDS_*: the widths / points forms make tr.N vertices per side from
+// in[b] (strict_rings: from the reference-order tables), the shared form copies ringL / ringR.  Every thread of the
+// block calls it; the rings are complete (block wide) on return.
+template <int BLOCK>
+__device__ __forceinline__ void tables_build_rings(const TrackDev& tr, int form, int strict_rings, const double* in, int b,
+                                                   const double2* ringL, const double2* ringR, int nL, int nR, double2* rL,
+                                                   double2* rR, int tid) {
+  const int N = tr.N;
+  if (form == 1) {   // widths: vertex i = p0_i + w_l n0_i  /  p0_i - w_r n0_i
+    const double2* w = reinterpret_cast<const double2*>(in) + (size_t)b * N;
+    for (int i = tid; i < N; i += BLOCK) {
+      const double2 wi = w[i];
+      if (strict_rings) {   // oracle: orc_width_rings -- p0 + w cos / sin(yaw0 +- pi/2), each normal on its own
+        const double* bs = tr.base_s;
+        const double px = bs[i], py = bs[(size_t)N + i];
+        rL[i] = make_double2(uf_madd(px, wi.x, bs[(size_t)2 * N + i]), uf_madd(py, wi.x, bs[(size_t)3 * N + i]));
+        rR[i] = make_double2(uf_madd(px, wi.y, bs[(size_t)4 * N + i]), uf_madd(py, wi.y, bs[(size_t)5 * N + i]));
+      } else {
+        const double px = tr.base[i], py = tr.base[(size_t)N + i];
+        const double nx = tr.base[(size_t)2 * N + i], ny = tr.base[(size_t)3 * N + i];
+        rL[i] = make_double2(px + wi.x * nx, py + wi.x * ny);
+        rR[i] = make_double2(px - wi.y * nx, py - wi.y * ny);
+      }
+    }
+  } else if (form == 2) {   // bound points
+    const double4* w = reinterpret_cast<const double4*>(in) + (size_t)b * N;
+    for (int i = tid; i < N; i += BLOCK) {
+      const double4 wi = w[i];
+      rL[i] = make_double2(wi.x, wi.y);
+      rR[i] = make_double2(wi.z, wi.w);
+    }
+  } else {
+    for (int i = tid; i < nL; i += BLOCK) rL[i] = ringL[i];
+    for (int i = tid; i < nR; i += BLOCK) rR[i] = ringR[i];
+  }
+  __syncthreads();
+  for (int q = tid; q < 2 * kRingPad; q += BLOCK) {   // repeat the first vertices behind the last
+    if (q < kRingPad) rL[nL + q] = rL[q % nL]; else rR[nR + q - kRingPad] = rR[(q - kRingPad) % nR];
+  }
+  __syncthreads();
+}
+
+// Chunk circles (culled and windowed search), chunk separations and the coordinate bound (windowed search) of the two
+// rings.  Returns the search mode in effect: the windowed mode needs rings longer than its window (as k_sweep decides it).
+// Every thread of the block calls it; the CALLER's next __syncthreads() completes the tables.
+template <int BLOCK>
+__device__ __forceinline__ int tables_chunk_tables(int search, const double2* rL, const double2* rR, int nL, int nR, int ncL,
+                                                   int ncR, double* circL, double* circR, double* sepL, double* sepR,
+                                                   double* cmax, int tid) {
+  const int lane = tid & (kWave - 1), wave = tid / kWave;
+  const int mode = (search == 2 && nL > 2 * kWinEdges && nR > 2 * kWinEdges) ? 2 : (search >= 1 ? 1 : 0);
+  if (mode >= 1) {
+    for (int c = tid; c < ncL + ncR; c += BLOCK) {
+      const bool left = c < ncL;
+      const int cc = left ? c : c - ncL;
+      const double2* ring = left ? rL : rR;
+      const int nr = left ? nL : nR;
+      const int j0 = cc * kChunk, j1 = min(j0 + kChunk, nr);
+      double xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY;
+      for (int j = j0; j <= j1; ++j) {
+        const double2 v = ring[j >= nr ? j - nr : j];
+        xmin = fmin(xmin, v.x); xmax = fmax(xmax, v.x);
+        ymin = fmin(ymin, v.y); ymax = fmax(ymax, v.y);
+      }
+      const double mx = 0.5 * (xmin + xmax), my = 0.5 * (ymin + ymax);
+      double r2 = 0.0;
+      for (int j = j0; j <= j1; ++j) {
+        const double2 v = ring[j >= nr ? j - nr : j];
+        const double ex = v.x - mx, ey = v.y - my;
+        r2 = fmax(r2, ex * ex + ey * ey);
+      }
+      double* o = (left ? circL : circR) + 3 * cc;
+      o[0] = mx; o[1] = my; o[2] = sqrt(r2) * (1.0 + 1e-12);
+    }
+    __syncthreads();
+    if (mode == 2) {
+      for (int c = tid; c < ncL + ncR; c += BLOCK) {
+        const bool left = c < ncL;
+        const int cc = left ? c : c - ncL;
+        const double* circ = left ? circL : circR;
+        const int nc = left ? ncL : ncR;
+        const double mx = circ[3 * cc], my = circ[3 * cc + 1], r = circ[3 * cc + 2];
+        double gap = INFINITY;
+        for (int q = 0; q < nc; ++q) {
+          int dq = q - cc;
+          if (dq < 0) dq = -dq;
+          if (nc - dq < dq) dq = nc - dq;   // cyclic distance in ring order
+          if (dq <= kNear) continue;
+          const double ex = circ[3 * q] - mx, ey = circ[3 * q + 1] - my;
+          gap = fmin(gap, sqrt(ex * ex + ey * ey) - r - circ[3 * q + 2]);
+        }
+        (left ? sepL : sepR)[cc] = gap * (1.0 - 1e-9) - 1e-9;
+      }
+      if (wave == 0) {   // a bound on every ring coordinate, for the quick sign pass of the window scan (+inf: no quick pass)
+        double m = 0.0;
+        for (int c = lane; c < ncL + ncR; c += kWave) {
+          const double* o = c < ncL ? circL + 3 * c : circR + 3 * (c - ncL);
+          const double v = fmax(fabs(o[0]), fabs(o[1])) + o[2];
+          m = v <= 0x1p+1000 ? fmax(m, v) : INFINITY;
+        }
+        m = wave_max_bfly(m);
+        if (lane == 0) cmax[0] = m;
+      }
+    }
+  }
+  return mode;
+}
+
+// Hint of the windowed search for sample i of N along a ring of nr edges: continue the run of the wave's previous 64 samples
+// (e0, e1: the edges its first and last lane found, < 0: none) along the ring; a wave's first tile guesses proportionally.
+// A wrong hint costs the slow path of the search, never the result.
+__device__ __forceinline__ int ring_hint(int e0, int e1, int nr, int i, int N, int lane) {
+  if (e0 < 0 || e1 < 0) return (int)(((long long)i * nr) / N);
+  int d = e1 - e0;
+  if (d > nr / 2) d -= nr;
+  if (d < -(nr / 2)) d += nr;
+  int h = (e1 + (d * (lane + 1)) / (kWave - 1)) % nr;
+  return h < 0 ? h + nr : h;
+}
+
+// A wave's tile of `rows` (<= 64) table rows to global memory, consecutive lanes on consecutive addresses: column c comes
+// from the staged column src[c] (COLS staged doubles per row), or from other(row, c) where src[c] < 0.
+template <int COLS, typename Other>
+__device__ __forceinline__ void tile_rows_out(double* o, const double* stg, const signed char* src, int rows, int lane,
+                                              Other&& other) {
+  for (int e = lane; e < rows * 19; e += kWave) {
+    const int r = e / 19, c = e - r * 19;
+    const int s = src[c];
+    o[e] = s >= 0 ? stg[r * COLS + s] : other(r, c);
+  }
+}
+
 template <int K, bool RINGS_LDS>
 __global__ __launch_bounds__(kTablesThreads) void k_tables(TablesArgs a) {
   extern __shared__ double tab_lds[];
@@ -132,94 +268,8 @@ __global__ __launch_bounds__(kTablesThreads) void k_tables(TablesArgs a) {
     const double2* cb = reinterpret_cast<const double2*>(a.ctrl) + (size_t)b * n;
     for (int j = tid; j < n; j += BLOCK) { const double2 c = cb[j]; cx[j] = c.x; cy[j] = c.y; }
   }
-  if (a.form == 1) {   // widths: vertex i = p0_i + w_l n0_i  /  p0_i - w_r n0_i
-    const double2* w = reinterpret_cast<const double2*>(a.in) + (size_t)b * N;
-    for (int i = tid; i < N; i += BLOCK) {
-      const double2 wi = w[i];
-      if (a.strict_rings) {   // oracle: orc_width_rings -- p0 + w cos / sin(yaw0 +- pi/2), each normal on its own
-        const double* bs = tr.base_s;
-        const double px = bs[i], py = bs[(size_t)N + i];
-        rL[i] = make_double2(uf_madd(px, wi.x, bs[(size_t)2 * N + i]), uf_madd(py, wi.x, bs[(size_t)3 * N + i]));
-        rR[i] = make_double2(uf_madd(px, wi.y, bs[(size_t)4 * N + i]), uf_madd(py, wi.y, bs[(size_t)5 * N + i]));
-      } else {
-        const double px = tr.base[i], py = tr.base[(size_t)N + i];
-        const double nx = tr.base[(size_t)2 * N + i], ny = tr.base[(size_t)3 * N + i];
-        rL[i] = make_double2(px + wi.x * nx, py + wi.x * ny);
-        rR[i] = make_double2(px - wi.y * nx, py - wi.y * ny);
-      }
-    }
-  } else if (a.form == 2) {   // bound points
-    const double4* w = reinterpret_cast<const double4*>(a.in) + (size_t)b * N;
-    for (int i = tid; i < N; i += BLOCK) {
-      const double4 wi = w[i];
-      rL[i] = make_double2(wi.x, wi.y);
-      rR[i] = make_double2(wi.z, wi.w);
-    }
-  } else {
-    for (int i = tid; i < nL; i += BLOCK) rL[i] = a.ringL[i];
-    for (int i = tid; i < nR; i += BLOCK) rR[i] = a.ringR[i];
-  }
-  __syncthreads();
-  for (int q = tid; q < 2 * kRingPad; q += BLOCK) {   // repeat the first vertices behind the last
-    if (q < kRingPad) rL[nL + q] = rL[q % nL]; else rR[nR + q - kRingPad] = rR[(q - kRingPad) % nR];
-  }
-  __syncthreads();
-  // the windowed mode needs rings longer than its window (as k_sweep decides it)
-  const int mode = (a.search == 2 && nL > 2 * kWinEdges && nR > 2 * kWinEdges) ? 2 : (a.search >= 1 ? 1 : 0);
-  if (mode >= 1) {
-    for (int c = tid; c < L.ncL + L.ncR; c += BLOCK) {
-      const bool left = c < L.ncL;
-      const int cc = left ? c : c - L.ncL;
-      const double2* ring = left ? rL : rR;
-      const int nr = left ? nL : nR;
-      const int j0 = cc * kChunk, j1 = min(j0 + kChunk, nr);
-      double xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY;
-      for (int j = j0; j <= j1; ++j) {
-        const double2 v = ring[j >= nr ? j - nr : j];
-        xmin = fmin(xmin, v.x); xmax = fmax(xmax, v.x);
-        ymin = fmin(ymin, v.y); ymax = fmax(ymax, v.y);
-      }
-      const double mx = 0.5 * (xmin + xmax), my = 0.5 * (ymin + ymax);
-      double r2 = 0.0;
-      for (int j = j0; j <= j1; ++j) {
-        const double2 v = ring[j >= nr ? j - nr : j];
-        const double ex = v.x - mx, ey = v.y - my;
-        r2 = fmax(r2, ex * ex + ey * ey);
-      }
-      double* o = (left ? circL : circR) + 3 * cc;
-      o[0] = mx; o[1] = my; o[2] = sqrt(r2) * (1.0 + 1e-12);
-    }
-    __syncthreads();
-    if (mode == 2) {
-      for (int c = tid; c < L.ncL + L.ncR; c += BLOCK) {
-        const bool left = c < L.ncL;
-        const int cc = left ? c : c - L.ncL;
-        const double* circ = left ? circL : circR;
-        const int nc = left ? L.ncL : L.ncR;
-        const double mx = circ[3 * cc], my = circ[3 * cc + 1], r = circ[3 * cc + 2];
-        double gap = INFINITY;
-        for (int q = 0; q < nc; ++q) {
-          int dq = q - cc;
-          if (dq < 0) dq = -dq;
-          if (nc - dq < dq) dq = nc - dq;   // cyclic distance in ring order
-          if (dq <= kNear) continue;
-          const double ex = circ[3 * q] - mx, ey = circ[3 * q + 1] - my;
-          gap = fmin(gap, sqrt(ex * ex + ey * ey) - r - circ[3 * q + 2]);
-        }
-        (left ? sepL : sepR)[cc] = gap * (1.0 - 1e-9) - 1e-9;
-      }
-      if (wave == 0) {   // a bound on every ring coordinate, for the quick sign pass of the window scan (+inf: no quick pass)
-        double m = 0.0;
-        for (int c = lane; c < L.ncL + L.ncR; c += kWave) {
-          const double* o = c < L.ncL ? circL + 3 * c : circR + 3 * (c - L.ncL);
-          const double v = fmax(fabs(o[0]), fabs(o[1])) + o[2];
-          m = v <= 0x1p+1000 ? fmax(m, v) : INFINITY;
-        }
-        m = wave_max_bfly(m);
-        if (lane == 0) cmax[0] = m;
-      }
-    }
-  }
+  tables_build_rings<BLOCK>(tr, a.form, a.strict_rings, a.in, b, a.ringL, a.ringR, nL, nR, rL, rR, tid);
+  const int mode = tables_chunk_tables<BLOCK>(a.search, rL, rR, nL, nR, L.ncL, L.ncR, circL, circR, sepL, sepR, cmax, tid);
 
   // ---- phase 1: segment lengths (trajectory.py:283-289: quad over [u_{i-1}, u_i] = one GK21 panel)
   const double step = 1.0 / (double)N;   // np.linspace(0, 1, N, endpoint=False)
@@ -282,14 +332,7 @@ __global__ __launch_bounds__(kTablesThreads) void k_tables(TablesArgs a) {
       if (a.form == 0) {
         // shared rings: continue the run of the wave's previous 64 samples along the ring; the first tile of a wave guesses
         // proportionally (a wrong hint costs the slow path of the search, never the result)
-        auto guess = [&](int e0, int e1, int nr) {
-          if (e0 < 0 || e1 < 0) return (int)(((long long)i * nr) / N);
-          int d = e1 - e0;
-          if (d > nr / 2) d -= nr;
-          if (d < -(nr / 2)) d += nr;
-          int h = (e1 + (d * (lane + 1)) / (kWave - 1)) % nr;
-          return h < 0 ? h + nr : h;
-        };
+        auto guess = [&](int e0, int e1, int nr) { return ring_hint(e0, e1, nr, i, N, lane); };
         hintL = guess(pL0, pL1, nL);
         hintR = guess(pR0, pR1, nR);
       }
@@ -327,11 +370,8 @@ __global__ __launch_bounds__(kTablesThreads) void k_tables(TablesArgs a) {
     // the tile's rows, consecutive lanes on consecutive addresses
     const int row0 = tl * kWave, rows = min(kWave, N - row0);
     double* o = out + (size_t)row0 * 19;
-    for (int e = lane; e < rows * 19; e += kWave) {
-      const int r = e / 19, c = e - r * 19;
-      const int src = c_tab_src[c];
-      o[e] = src >= 0 ? stg[r * kTabCols + src] : (c == 17 ? (double)(row0 + r) : (c == 18 ? -1.0 : 0.0));
-    }
+    tile_rows_out<kTabCols>(o, stg, c_tab_src, rows, lane,
+                            [&](int r, int c) { return c == 17 ? (double)(row0 + r) : (c == 18 ? -1.0 : 0.0); });
     wave_lds_sync();   // the tile is free again
   }
 }

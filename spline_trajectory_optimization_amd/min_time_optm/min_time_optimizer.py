@@ -311,6 +311,12 @@ def optimise_track(race_track, vehicle, model, average_track_width=7.0, speed_ca
     prob = DoubleTrackProblem({"N": len(traj_d), "model": model, "race_track": race_track, "traj_d": traj_d,
                                "average_track_width": average_track_width, "speed_cap": speed_cap, "max_iter": max_iter})
     X, U, T, st = prob.solve(tol=tol)
+    return pose_table(race_track, traj_d, X), X, U, T, st
+
+
+def pose_table(race_track, traj_d, X):
+    """The CLI's last step (entrypoints/traj_opt_double_track.py:75-82) for one solution X [N,6] on the host: a copy of
+    `traj_d` with the global poses, the speed, the bounds and the distances of the optimised line."""
     out = traj_d.copy()
     pose = race_track.frenet_to_global(X[:, 0], X[:, 1], X[:, 2])                           # :76
     out[:, 0:2] = pose[:, 0:2]
@@ -318,4 +324,72 @@ def optimise_track(race_track, vehicle, model, average_track_width=7.0, speed_ca
     out[:, Trajectory.SPEED] = X[:, 5]
     race_track.fill_trajectory_boundaries(out)
     out.fill_distance()                                                                     # :81
-    return out, X, U, T, st
+    return out
+
+
+def optimise_track_batch(race_track, vehicle, model, left=None, right=None, average_track_width=7.0, speed_cap=30.0,
+                         max_iter=200, tol=1e-6, device=None, track=None):
+    """optimise_track for B instances of one track that differ in their boundary distances, as ONE chain on torch's current
+    stream with device tensors throughout: QSS warm start (k_qss_sim) -> initial guess -> NLP solve (k_mt_*) -> tables of
+    the batch (k_pose_tables) -> their summary (k_table_summary).  No result travels to the host in between; the host set-up is
+    the interpolants' values at the nodes (scipy, as in DoubleTrackProblem) and the rl_track of the centre line.
+    left / right [B,N] (numpy or cuda tensors): the distances from the centre line to the left (> 0) and right (< 0) edge at
+    the nodes, as DoubleTrackProblem.solve_batch takes them; an instance's rings are then the polygons through those edge
+    points on the centre line's normals (BOUNDS_POINTS).  None: one instance with the track's own distances, bounded by
+    race_track's own rings -- optimise_track's result.
+    track: the _lib.Track of race_track.center_s with len(race_track.center_d) samples (batch.make_track) that the tables
+    step runs on; None builds one (device allocations and table kernels: set-up, not part of the chain).  A track that is
+    destroyed frees device memory, which waits for the device: the one used is therefore returned under "track", and the
+    chain stays asynchronous for as long as the caller holds the result; pass it back in for the next call.
+    Returns dict(points [B,N,19], X [B,N,6], U [B,N,4], T [B,N], stats [B,12], summary [B,8]) of cuda tensors plus "track":
+    stats as include/rl_mincurv.h: rl_mintime_solve_batch, summary in the order of ops.SUMMARY_COLUMNS (summary[:, 0] is the
+    lap time)."""
+    import torch
+    from .. import _lib, batch
+    from ..models.trajectory import _ring_coords
+    dev = torch.device("cuda", _lib.Context.get(device).device)
+    up = lambda a: a.to(dev).contiguous() if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)  # noqa: E731
+    if (left is None) != (right is None):
+        raise ValueError("left and right: both or neither")
+    traj_d = race_track.center_d.copy()
+    race_track.fill_trajectory_boundaries(traj_d)
+    N = len(traj_d)
+    s = np.ascontiguousarray(race_track.abscissa, dtype=np.float64)
+    margin = model["vehicle_width"] / 2.0 + model["safety_margin"]
+    if left is None:
+        left_d, right_d = up(np.asarray(race_track.left_intp(s))[None]), up(np.asarray(race_track.right_intp(s))[None])
+    else:
+        left_d, right_d = up(left), up(right)
+    B = int(left_d.shape[0])
+    if tuple(left_d.shape) != (B, N) or tuple(right_d.shape) != (B, N):
+        raise ValueError(f"left / right: expected [B,{N}]")
+    # QSS warm start: the simulated centre-line table is the same for every instance
+    base = up(traj_d.points)[None].contiguous()
+    ops.qss_sim_torch(base, *batch.vehicle_tables(vehicle))
+    base = base[0]
+    # initial guess (min_time_optimizer.py:146-151 as written; DoubleTrackProblem's "reference" mode)
+    s_d = up(s)
+    X = torch.zeros((B, N, 6), dtype=torch.float64, device=dev)
+    X[:, :, 0] = s_d
+    X[:, :, 5] = base[:, Trajectory.SPEED]
+    U = torch.tensor([1.0, -1.0, 0.001, 0.0], dtype=torch.float64, device=dev).repeat(B, N, 1).contiguous()
+    T = base[:, Trajectory.TIME].repeat(B, 1).contiguous()
+    stats = ops.mintime_solve_torch(dict(model), s_d, up(race_track.curvature_intp(s)), left_d, right_d, margin,
+                                    float(race_track.center_s.get_length()), X, U, T, float(average_track_width),
+                                    float(speed_cap), max_iter=int(max_iter), tol=float(tol))
+    if track is None:
+        track = batch.make_track(race_track.center_s, N, device=dev.index)
+    elif track.N != N:
+        raise ValueError(f"track: {track.N} samples, the race track has {N} nodes")
+    if left is None:
+        track.set_rings(_ring_coords(race_track.left_r), _ring_coords(race_track.right_r))
+        form, bounds = _lib.BOUNDS_SHARED_RINGS, None
+    else:
+        yaw0 = up(race_track.yaw_intp(s))
+        cx, cy, nx, ny = up(race_track.x_intp(s)), up(race_track.y_intp(s)), -torch.sin(yaw0), torch.cos(yaw0)
+        bounds = torch.stack([cx + nx * left_d, cy + ny * left_d, cx + nx * right_d, cy + ny * right_d], dim=2).contiguous()
+        form = _lib.BOUNDS_POINTS
+    points = batch.min_time_tables_torch(race_track, track, X, T, form, bounds, base=base,
+                                         pieces=tuple(up(a) for a in race_track.centerline_pieces()))
+    summary = ops.table_summary_torch(points)
+    return {"points": points, "X": X, "U": U, "T": T, "stats": stats, "summary": summary, "track": track}

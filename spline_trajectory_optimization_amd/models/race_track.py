@@ -95,6 +95,13 @@ class RaceTrack:
         self.curvature_intp = curvature
         self.fast_curvature_intp = lambda s_: np.interp(wrap(s_), ss, np.r_[curvature(self.abscissa), curvature(self.abscissa[:1])])
 
+    def centerline_pieces(self):
+        """(ss [M+1], cxs [4,M], cys [4,M]) of the centre line's periodic cubic splines x(s), y(s) behind x_intp / y_intp /
+        yaw_intp: scipy CubicSpline pieces (breakpoints, coefficients with c[0] the cubic term; ss[M] = track length), as
+        ops.pose_tables_* takes them for POSE_FRENET."""
+        as_c = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
+        return as_c(self._sx.x), as_c(self._sx.c), as_c(self._sy.c)
+
     def frenet_to_global(self, s, t, xi):
         """(abscissa, lateral offset, relative heading) -> (x, y, heading)  (race_track.py:87-96)."""
         yaw0 = self.yaw_intp(s)

@@ -415,6 +415,92 @@ def tables_torch(track, ctrl, bounds_form, bounds, length, bank=None, out=None):
     return out
 
 
+def _pose_tables_shapes(track, form, X, pieces, bounds_form, bounds, base):
+    """(B, N, M, bounds shape | None, base shape | None, base_per_instance) of a pose-tables call; ValueError for a bad form,
+    rank or a missing argument -- before any library call."""
+    if form not in (_lib.POSE_FRENET, _lib.POSE_GLOBAL):
+        raise ValueError(f"form: POSE_FRENET or POSE_GLOBAL, got {form!r}")
+    if bounds_form not in _BOUNDS_COLS:
+        raise ValueError(f"bounds_form: one of BOUNDS_SHARED_RINGS / _WIDTHS / _POINTS, got {bounds_form!r}")
+    width = 6 if form == _lib.POSE_FRENET else 5
+    if getattr(X, "ndim", None) != 3 or X.shape[2] != width:
+        raise ValueError(f"X: expected [B,N,{width}]")
+    B, N = int(X.shape[0]), int(X.shape[1])
+    if B <= 0 or N < 2:
+        raise ValueError("X: needs at least one instance of two nodes")
+    M = 0
+    if form == _lib.POSE_FRENET:
+        if pieces is None or len(pieces) != 3:
+            raise ValueError("pieces: POSE_FRENET needs (ss [M+1], cxs [4,M], cys [4,M]) of the centre line (RaceTrack.centerline_pieces)")
+        M = int(pieces[0].shape[0]) - 1
+        if M < 1:
+            raise ValueError("pieces: at least one piece")
+    cols = _BOUNDS_COLS[bounds_form]
+    if (bounds is None) != (cols == 0):
+        raise ValueError("bounds: None for BOUNDS_SHARED_RINGS, [B,track.N,2] widths / [B,track.N,4] points otherwise")
+    per = base is not None and getattr(base, "ndim", 2) == 3
+    return (B, N, M, ((B, track.N, cols) if cols else None),
+            (None if base is None else ((B, N, _lib.NCOL) if per else (N, _lib.NCOL))), per)
+
+
+def pose_tables_host(track, form, X, pieces, bounds_form, bounds, base=None, T=None):
+    """Tables of a batch of poses (rl_pose_tables_batch_host): the tail of the reference's min-time pipeline
+    (entrypoints/traj_opt_double_track.py:75-82) per instance -- RaceTrack.frenet_to_global, X / Y / YAW / SPEED into a copy
+    of `base`, Trajectory.fill_bounds, Trajectory.fill_distance.  form POSE_FRENET: X [B,N,6] of mintime_solve_batch and
+    pieces = RaceTrack.centerline_pieces(); POSE_GLOBAL: X [B,N,5] of bicycle_solve_batch, pieces None.  bounds None /
+    widths [B,track.N,2] / points [B,track.N,4]; base None, [N,19] or [B,N,19]; T None or [B,N] (TIME[(i+1) % N] = T[b,i]).
+    numpy float64, C-contiguous.  Returns points [B,N,19]."""
+    B, N, M, bshape, kshape, per = _pose_tables_shapes(track, form, X, pieces, bounds_form, bounds, base)
+    _check_np(X, "X", (B, N, X.shape[2]))
+    if M:
+        _check_np(pieces[0], "pieces[0]", (M + 1,)); _check_np(pieces[1], "pieces[1]", (4, M)); _check_np(pieces[2], "pieces[2]", (4, M))
+    if bshape:
+        _check_np(bounds, "bounds", bshape)
+    if kshape:
+        _check_np(base, "base", kshape)
+    if T is not None:
+        _check_np(T, "T", (B, N))
+    ctx = track.ctx
+    pts = np.empty((B, N, _lib.NCOL))
+    p = lambda a: None if a is None else a.ctypes.data_as(_dp)  # noqa: E731
+    check(ctx.lib.rl_pose_tables_batch_host(ctx.h, track.h, int(form), p(X), B, N, p(pieces[0]) if M else None,
+                                            p(pieces[1]) if M else None, p(pieces[2]) if M else None, M, int(bounds_form),
+                                            p(bounds), p(base), int(per), p(T), p(pts)))
+    return pts
+
+
+def pose_tables_torch(track, form, X, pieces, bounds_form, bounds, base=None, T=None, out=None):
+    """pose_tables_host on DEVICE tensors (float64 cuda, contiguous, all on the device of the track's context; the pieces
+    too): enqueues on torch's current stream, no sync (rl_pose_tables_batch_dev).  Returns the cuda tensor points [B,N,19] (`out` if given)."""
+    import torch
+    B, N, M, bshape, kshape, per = _pose_tables_shapes(track, form, X, pieces, bounds_form, bounds, base)
+    _check_torch(X, "X", (B, N, X.shape[2]))
+    if M:
+        _check_torch(pieces[0], "pieces[0]", (M + 1,)); _check_torch(pieces[1], "pieces[1]", (4, M)); _check_torch(pieces[2], "pieces[2]", (4, M))
+    if bshape:
+        _check_torch(bounds, "bounds", bshape)
+    if kshape:
+        _check_torch(base, "base", kshape)
+    if T is not None:
+        _check_torch(T, "T", (B, N))
+    dev = X.device
+    if out is None:
+        out = torch.empty((B, N, _lib.NCOL), dtype=torch.float64, device=dev)
+    _check_torch(out, "out", (B, N, _lib.NCOL))
+    ctx = track.ctx
+    if dev.index != ctx.device:
+        raise ValueError(f"X: on {dev}, the track's context is on device {ctx.device}")
+    for name, t_ in (("bounds", bounds), ("base", base), ("T", T), ("out", out)) + tuple((f"pieces[{j}]", q) for j, q in enumerate(pieces or ())):
+        if t_ is not None and t_.device != dev:
+            raise ValueError(f"{name}: on {t_.device}, X is on {dev}")
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    p = lambda t_: None if t_ is None else ctypes.c_void_p(t_.data_ptr())  # noqa: E731
+    check(ctx.lib.rl_pose_tables_batch_dev(ctx.h, track.h, int(form), p(X), B, N, p(pieces[0]) if M else None,
+                                           p(pieces[1]) if M else None, p(pieces[2]) if M else None, M, int(bounds_form),
+                                           p(bounds), p(base), int(per), p(T), p(out)))
+    return out
+
+
 def table_summary(points, iters=None, device=None):
     """Per-instance summary of simulated tables [B,N,19] (numpy): [B,8] in the order of SUMMARY_COLUMNS -- lap time (TIME
     added up in index order) and the scalars of the reference's SimulationResult (simulator.py:375-386).  iters [B] int32

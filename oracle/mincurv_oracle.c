@@ -306,8 +306,11 @@ void orc_heading(const double* dx, const double* dy, int n, double* out) {
  * with the closed polyline `ring`.  trajectory.py:84-129: LineString((min_norm,max_norm)) ∩ ring,
  * keep the Point closest to the waypoint; no intersection -> the waypoint itself (:127).
  * The hit is expressed as  p + s*d  with  s = cross(P-p, Q-P) / cross(d, Q-P)  for the ring edge
- * (P,Q) the line crosses (cross(P-p,d) and cross(Q-p,d) of opposite sign); distance = |s|*max_dist.
- * Ties keep the lowest edge index. */
+ * (P,Q) the line meets: every edge whose end points are NOT strictly on one side of the line (cross(P-p,d) and
+ * cross(Q-p,d) of opposite sign, or one of them zero: a vertex on the line counts for both of its edges), except an edge
+ * parallel to or lying on the line (den == 0: its neighbours meet the line at its end vertices); |s| > 1 is out of
+ * range; distance = |s|*max_dist.  Ties in |s| keep the lowest edge index.  Pinned exactly, case by case, by
+ * tests/test_ring_crossings_cpu.py. */
 static void closest_hit(double px, double py, double yaw_norm, double max_dist,
                         const double* ring, int nr, double* bx, double* by) {
   double dx = max_dist * o_cos(yaw_norm), dy = max_dist * o_sin(yaw_norm);

@@ -234,6 +234,66 @@ int rl_mincurv_solve_batch_host(rl_ctx* ctx, const rl_track* trk, int bounds_for
                                 double* out_ctrl, double* out_xy, int* n_success, int* status,
                                 rl_stats* stats);
 
+/* ---- the same batched solve with, per instance, its own start line and its own start indices.
+ *   ctrl0   NULL (trk's initial control points, as rl_mincurv_solve_batch_*) or [B,n,2]: instance b starts from ctrl0[b] as
+ *           rl_mincurv_sweep starts from its cx, cy (used as given; the caller keeps scipy's periodic layout, coefficient
+ *           j + (n-k) = coefficient j for j < k)
+ *   i_start, i_start_per_instance   0: HOST [max_iter] as rl_mincurv_solve_batch_*; != 0: [B,max_iter], row b for instance b --
+ *           HOST for *_host (validated, RL_ERR_ARG), DEVICE for *_dev, where the kernel validates: an instance with an index
+ *           outside [k//2, n-(k-k//2)) runs no step: status[b] = -1, out_ctrl[b] = its start line, out_xy[b] = that line's
+ *           samples, n_success[b] = 0
+ *   everything else as rl_mincurv_solve_batch_dev / _host.  With ctrl0 == NULL and i_start_per_instance == 0 the call IS
+ *   rl_mincurv_solve_batch_* (the same kernels, the same bits).  Every arithmetic of the sweep (rl_ctx_set_arith) and both
+ *   residencies; RL_FORCE_RESIDENCY=2 runs all-global here; the step dump (rl_debug_dump_enable) does not record these calls.
+ * RL_BOUNDS_WIDTHS rings are still built about TRK's initial control points (the track's centre line), not about ctrl0.
+ *
+ * Continuation.  A run of a + b outer iterations equals a run of a iterations followed by rl_ctx_set_numpy_raise(ctx, 1) and a
+ * run of b iterations from ctrl0 = the first run's out_ctrl with the remaining start indices -- bit for bit in every arithmetic:
+ * control points, samples and the success counts of the last b iterations -- WHENEVER NO STEP RAISED (reference-order
+ * arithmetic: the oracle's last_raised() == 0; the fast arithmetic never raises).  The kernel derives its whole table from the
+ * control points it starts from, and numpy's raise mode, which begins at the end of outer iteration 0, is what
+ * rl_ctx_set_numpy_raise(ctx, 1) puts the second run in.  A step that raised leaves a STALE table behind (the control point
+ * written, the samples not refreshed, see rl_ctx_set_numpy_raise): control points alone cannot carry that state, the second
+ * run would start from a fresh table and may differ from the uninterrupted run from there on. */
+int rl_mincurv_solve_batch_from_dev(rl_ctx* ctx, const rl_track* trk, int bounds_form, const double* in, int B,
+                                    const double* ctrl0, const int* i_start, int i_start_per_instance, int max_iter,
+                                    int search, double* out_ctrl, double* out_xy, int* n_success, int* status,
+                                    rl_stats* stats);
+int rl_mincurv_solve_batch_from_host(rl_ctx* ctx, const rl_track* trk, int bounds_form, const double* in, int B,
+                                     const double* ctrl0, const int* i_start, int i_start_per_instance, int max_iter,
+                                     int search, double* out_ctrl, double* out_xy, int* n_success, int* status,
+                                     rl_stats* stats);
+
+/* ---- least-squares periodic B-spline through P points per instance ON trk's KNOTS (degree trk->k; csrc/rl_spline_fit.hpp):
+ * what scipy.interpolate.splprep([x,y], u=u, t=trk's knots, task=-1, per=True, k=k) returns for the closed loop (FITPACK
+ * clocur; the reference's own fit, models/trajectory.py:219-222, is task 0 of the same routine).  This is how a line that is
+ * not the track's -- poses of a min-time solution, a driven line, a line on another knot layout -- becomes a start line
+ * (ctrl0 above).  One workgroup per instance, normal equations, cyclic banded Cholesky in LDS.
+ *   xy      point (b,p) at xy[(b*P+p)*stride], [+1]  (stride 2: xy arrays; 19: Trajectory tables) -- as rl_region_index_dev
+ *   u       NULL: chord-length parameters of the closed polygon, u_0 = 0, u_p = sum_{q<p}|p_{q+1}-p_q| / perimeter
+ *           (perimeter includes the closing chord; what splprep computes for the loop with the first point repeated);
+ *           else [P] (u_per_instance == 0) or [B,P], values in [0,1], 1 is taken as 0; any order.  u is mapped linearly onto
+ *           the knots' base interval [t[k], t[n]] ([0,1] for every spline of this package)
+ *   out_ctrl  [B,n,2], coefficient j+(n-k) = coefficient j for j < k (scipy's periodic layout)
+ *   out_stats [B,4]: status, rms residual [m] (sqrt of the mean squared point-to-fit distance at the points' parameters), max
+ *           residual [m], smallest pivot / largest diagonal of the normal matrix G = A^T A
+ *           status 0 = fitted; 1 = rank deficient (smallest pivot <= 1e-12 * largest diagonal, or not positive);
+ *           2 = a non-finite point / parameter / result or a parameter outside [0,1].  For status != 0 out_ctrl[b] := trk's
+ *           initial control points (a finite, valid start line: nothing downstream ever receives NaN control points) and both
+ *           residuals are NaN (status 2 from the input: the pivot ratio too)
+ *   The rank threshold is derived, not tuned: a Cholesky pivot is >= lambda_min(G) and the largest diagonal <= lambda_max(G),
+ *   so pivot / largest diagonal >= 1 / cond2(G): 1e-12 never flags a problem with cond2(G) < 1e12, beyond which the error
+ *   bound of the normal equations (eps cond2(G) max|c|) exceeds 2e-4 max|c| anyway; an exactly deficient problem (an empty
+ *   run of knot spans) computes a pivot of order (n-k) eps diag or a negative one.
+ *   Reproducible: every sum has one order fixed by the input (no floating-point atomics): the same points give the same bits
+ *   in every run and at every batch position.
+ * Limits: 2k+1 <= n-k <= 192, 1 <= P <= 4096, else RL_ERR_UNSUPPORTED.  *_dev: device pointers, context's stream, no sync;
+ * *_host: host pointers, synchronises. */
+int rl_spline_fit_batch_dev(rl_ctx* ctx, const rl_track* trk, const double* xy, int B, int P, int stride, const double* u,
+                            int u_per_instance, double* out_ctrl, double* out_stats);
+int rl_spline_fit_batch_host(rl_ctx* ctx, const rl_track* trk, const double* xy, int B, int P, int stride, const double* u,
+                             int u_per_instance, double* out_ctrl, double* out_stats);
+
 /* ---- a15: GLOBAL min-curvature QP, B instances, one workgroup each (replaces the
  * reference's non-converging Julia prototype julia/spline_traj_opt.ipynb cells 6/8/9 -- see SURVEY.md
  * App. A.6 -- with a well-posed formulation of the same problem; BASELINE.json north_star: "lateral

@@ -75,6 +75,14 @@ _SIGNATURES = {
     "rl_mincurv_solve_batch_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, ctypes.c_int, _ip,
                                                    ctypes.c_int, ctypes.c_int, _dp, _dp, _ip, _ip,
                                                    ctypes.POINTER(Stats)]),
+    "rl_mincurv_solve_batch_from_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int,
+                                                       ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.POINTER(Stats)]),
+    "rl_mincurv_solve_batch_from_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, ctypes.c_int, _dp, _ip, ctypes.c_int,
+                                                        ctypes.c_int, ctypes.c_int, _dp, _dp, _ip, _ip, ctypes.POINTER(Stats)]),
+    "rl_spline_fit_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
+                                               _vp, _vp]),
+    "rl_spline_fit_batch_host": (ctypes.c_int, [_vp, _vp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_int,
+                                                _dp, _dp]),
     "rl_dt_eval_nodes": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_double,
                                         ctypes.c_double, _dp, _dp, _dp, _dp, _dp, _dp]),
     "rl_dt_eval_jac": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_double,

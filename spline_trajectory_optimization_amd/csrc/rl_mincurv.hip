@@ -24,6 +24,7 @@
 #include "rl_region.hpp"
 #include "rl_tables.hpp"
 #include "rl_pose_tables.hpp"
+#include "rl_spline_fit.hpp"
 
 namespace {
 double* g_dbg_buf = nullptr;   // rl_debug_dump_enable: step / window dump of the sweep kernels (tests)
@@ -186,6 +187,30 @@ int launch_sweep(const rl_ctx* ctx, int k, const SweepPlan& p, const rl::SweepAr
     return launch_sweep_in<5, Driver::Sweep, Arith::Fast>(ctx, p, a);
   }
   if (k == 3) return launch_sweep_in<3, Driver::Sweep, Arith::Fast>(ctx, p, a);
+  return fail(RL_ERR_UNSUPPORTED, "spline degree must be 3 or 5");
+}
+
+// The sweep from per-instance start lines / start indices (rl_mincurv_solve_batch_from_*): the SweepConfigFrom instantiations,
+// in the residency the plan chose, for every arithmetic of the sweep driver.
+template <int K, rl::Arith ARITH>
+int launch_sweep_from_in(const rl_ctx* ctx, const SweepPlan& p, const rl::SweepArgs& a) {
+  using rl::Residency; using rl::SweepConfigFrom;
+  const dim3 grid(a.B), block(rl::kSweepThreads);
+  return p.residency == Residency::Lds
+             ? launch(ctx, rl::k_sweep<SweepConfigFrom<K, Residency::Lds, ARITH>>, grid, block, p.lds_bytes, a)
+             : launch(ctx, rl::k_sweep<SweepConfigFrom<K, Residency::Global, ARITH>>, grid, block, p.lds_bytes, a);
+}
+int launch_sweep_from(const rl_ctx* ctx, int k, const SweepPlan& p, const rl::SweepArgs& a, bool strict, bool lite) {
+  using rl::Arith;
+  if (strict) {
+    if (k != 5) return fail(RL_ERR_UNSUPPORTED, "reference-order / branch arithmetic: degree-5 splines");
+    if (lite) return launch_sweep_from_in<5, Arith::Branch>(ctx, p, a);
+    // as launch_sweep: the plain kernel flags, the ReferenceRaise instantiation redoes the flagged instances -- from the same start
+    if (int rc = launch_sweep_from_in<5, Arith::Reference>(ctx, p, a)) return rc;
+    return launch_sweep_from_in<5, Arith::ReferenceRaise>(ctx, p, a);
+  }
+  if (k == 5) return launch_sweep_from_in<5, Arith::Fast>(ctx, p, a);
+  if (k == 3) return launch_sweep_from_in<3, Arith::Fast>(ctx, p, a);
   return fail(RL_ERR_UNSUPPORTED, "spline degree must be 3 or 5");
 }
 
@@ -557,8 +582,13 @@ int rl_track_constraint(rl_ctx* ctx, const rl_track* trk, const double* points, 
 static int solve_batch_common(rl_ctx* ctx, const rl_track* trk, int form, const double* in_dev,
                               int B, const int* i_start, int max_iter, int search,
                               double* out_ctrl, double* out_xy, double* out_points, int* n_success,
-                              int* status, rl_stats* stats, SweepPlan* plan_out, bool joint = false) {
-  if (!ctx || !trk || !i_start || !out_ctrl) return fail(RL_ERR_ARG, "null argument");
+                              int* status, rl_stats* stats, SweepPlan* plan_out, bool joint = false,
+                              const double* ctrl0 = nullptr, const int* i_start_rows = nullptr) {
+  // ctrl0 / i_start_rows (DEVICE, rl_mincurv_solve_batch_from_*): per-instance start lines / start indices; `i_start` is then
+  // unused when rows are given
+  const bool from = ctrl0 || i_start_rows;
+  if (!ctx || !trk || (!i_start && !i_start_rows) || !out_ctrl) return fail(RL_ERR_ARG, "null argument");
+  if (from && joint) return fail(RL_ERR_UNSUPPORTED, "the sliding-window driver has no per-instance start lines");
   if (!out_xy && !out_points) return fail(RL_ERR_ARG, "need out_xy or out_points");
   if (B <= 0) return fail(RL_ERR_ARG, "B <= 0");
   if (max_iter <= 0 || max_iter > RL_MAX_ITER) return fail(RL_ERR_ARG, "max_iter out of range");
@@ -566,7 +596,7 @@ static int solve_batch_common(rl_ctx* ctx, const rl_track* trk, int form, const 
   const int n = trk->n, N = trk->N, k = trk->k;
   const int i_min = k / 2, i_max = n - (k - k / 2) - (joint ? 5 : 0);
   if (i_max <= i_min) return fail(RL_ERR_ARG, "too few control points");
-  for (int j = 0; j < max_iter; ++j)
+  for (int j = 0; j < max_iter && !i_start_rows; ++j)
     if (i_start[j] < i_min || i_start[j] >= i_max)
       return fail(RL_ERR_ARG, joint ? "i_start outside [k//2, n-(k-k//2)-span) (optimizer.py:176-178)"
                                     : "i_start outside [k//2, n-(k-k//2)) (optimizer.py:301-303)");
@@ -583,7 +613,7 @@ static int solve_batch_common(rl_ctx* ctx, const rl_track* trk, int form, const 
   // elsewhere; an arithmetic chosen with rl_ctx_set_arith / RL_ARITH is taken literally (and fails where it does not exist).
   // rl_stats.reserved[0] names the arithmetic that ran.
   int arith = ctx->arith;
-  if (!ctx->arith_explicit && arith == RL_ARITH_REFERENCE && (k != 5 || g_dbg_instances > 0)) arith = RL_ARITH_FAST;
+  if (!ctx->arith_explicit && arith == RL_ARITH_REFERENCE && (k != 5 || (g_dbg_instances > 0 && !from))) arith = RL_ARITH_FAST;
   const bool lite = arith == RL_ARITH_BRANCH;
   const bool strict = arith == RL_ARITH_REFERENCE || lite;    // the branch mode shares the reference-order kernel's tables and state
   if (strict) {
@@ -601,7 +631,8 @@ static int solve_batch_common(rl_ctx* ctx, const rl_track* trk, int form, const 
   if (int rc = resolve_bounds(trk, form, in_dev, bd)) return rc;
   a.ringL = bd.ringL; a.ringR = bd.ringR; a.nL = bd.nL; a.nR = bd.nR;
   a.max_iter = max_iter;
-  for (int j = 0; j < max_iter; ++j) a.i_start[j] = i_start[j];
+  for (int j = 0; j < max_iter && !i_start_rows; ++j) a.i_start[j] = i_start[j];
+  a.ctrl0 = ctrl0; a.i_start_rows = i_start_rows;
   a.search = search;
   a.max_dist = 100.0;  // race_track.py:104
 #ifdef RL_ABLATION
@@ -612,7 +643,7 @@ static int solve_batch_common(rl_ctx* ctx, const rl_track* trk, int form, const 
 #else
   const bool dbg_ok = !strict;
 #endif
-  if (g_dbg_instances > 0 && (joint || k == 5) && dbg_ok) {
+  if (g_dbg_instances > 0 && (joint || k == 5) && dbg_ok && !from) {   // (no recording instantiation from per-instance starts)
     const int ninst = std::min(g_dbg_instances, B);
     size_t need = joint ? (size_t)max_iter * (size_t)(i_max - i_min) * (48 + 9 * rl::kJointRowsPerThread * 256 + 2 * n)
                         : (size_t)ninst * max_iter * 2 * (size_t)(i_max - i_min) * (rl::kSweepDumpHead + 2 * n);
@@ -633,7 +664,7 @@ static int solve_batch_common(rl_ctx* ctx, const rl_track* trk, int form, const 
   RL_HIP(hipSetDevice(ctx->device));
   SweepPlan p = plan_sweep(ctx, n, N, a.nL, a.nR, B, joint, strict);
   if (p.lds_bytes > (size_t)ctx->max_lds) return fail(RL_ERR_UNSUPPORTED, "problem does not fit LDS");
-  if (p.residency == rl::Residency::CrossingsLds && (joint || k != 5 || a.dbg)) {   // the mixed residency exists for the k = 5 sweep only
+  if (p.residency == rl::Residency::CrossingsLds && (joint || k != 5 || a.dbg || from)) {   // the mixed residency exists for the k = 5 sweep only
     p.residency = rl::Residency::Global;
     p.lds_bytes = rl::sweep_lds_layout(n, N, a.nL, a.nR, rl::Residency::Global, joint).total * sizeof(double);
     p.gscratch_doubles += (size_t)2 * ((N + 1) & ~1);
@@ -662,6 +693,7 @@ static int solve_batch_common(rl_ctx* ctx, const rl_track* trk, int form, const 
     stats->reserved[0] = arith;
   }
   if (plan_out) *plan_out = p;
+  if (from) return launch_sweep_from(ctx, k, p, a, strict, lite);
   return launch_sweep(ctx, k, p, a, joint, strict, lite);
 }
 
@@ -692,6 +724,83 @@ int rl_mincurv_solve_batch_host(rl_ctx* ctx, const rl_track* trk, int bounds_for
     return solve_batch_common(ctx, trk, bounds_form, din, B, i_start, max_iter, search, dctrl, dxy, nullptr, dns, dst, stats, nullptr);
   });
   return sg.finish(stats);
+}
+
+int rl_mincurv_solve_batch_from_dev(rl_ctx* ctx, const rl_track* trk, int bounds_form, const double* in, int B,
+                                    const double* ctrl0, const int* i_start, int i_start_per_instance, int max_iter,
+                                    int search, double* out_ctrl, double* out_xy, int* n_success, int* status, rl_stats* stats) {
+  if (!out_xy) return fail(RL_ERR_ARG, "out_xy is null");
+  if (!i_start) return fail(RL_ERR_ARG, "i_start is null");
+  return solve_batch_common(ctx, trk, bounds_form, in, B, i_start_per_instance ? nullptr : i_start, max_iter, search, out_ctrl,
+                            out_xy, nullptr, n_success, status, stats, nullptr, false, ctrl0,
+                            i_start_per_instance ? i_start : nullptr);
+}
+
+int rl_mincurv_solve_batch_from_host(rl_ctx* ctx, const rl_track* trk, int bounds_form, const double* in, int B,
+                                     const double* ctrl0, const int* i_start, int i_start_per_instance, int max_iter,
+                                     int search, double* out_ctrl, double* out_xy, int* n_success, int* status, rl_stats* stats) {
+  if (!ctx || !trk || !out_ctrl || !out_xy || !i_start) return fail(RL_ERR_ARG, "null argument");
+  if (B <= 0) return fail(RL_ERR_ARG, "B <= 0");
+  if (max_iter <= 0 || max_iter > RL_MAX_ITER) return fail(RL_ERR_ARG, "max_iter out of range");
+  const int n = trk->n, N = trk->N, k = trk->k;
+  if (i_start_per_instance) {   // host rows are validated here; the kernel's own check is for rows that never were on the host
+    const int i_min = k / 2, i_max = n - (k - k / 2);
+    for (size_t j = 0; j < (size_t)B * max_iter; ++j)
+      if (i_start[j] < i_min || i_start[j] >= i_max) return fail(RL_ERR_ARG, "i_start outside [k//2, n-(k-k//2)) (optimizer.py:301-303)");
+  }
+  const int cols = bounds_cols(bounds_form);
+  if (cols && !in) return fail(RL_ERR_ARG, "bounds input is null");
+  Staging sg(ctx);
+  const double* din = cols ? sg.in(in, (size_t)B * N * cols) : nullptr;
+  const double* dc0 = sg.in(ctrl0, (size_t)B * n * 2);
+  const int* drows = i_start_per_instance ? sg.in(i_start, (size_t)B * max_iter) : nullptr;
+  double *dctrl = sg.out(out_ctrl, (size_t)B * n * 2), *dxy = sg.out(out_xy, (size_t)B * N * 2);
+  int* dns = sg.out_optional(n_success, (size_t)B * 2 * max_iter);
+  int* dst = sg.out_optional(status, B);
+  sg.run_timed([&] {
+    return solve_batch_common(ctx, trk, bounds_form, din, B, i_start_per_instance ? nullptr : i_start, max_iter, search, dctrl, dxy,
+                              nullptr, dns, dst, stats, nullptr, false, dc0, drows);
+  });
+  return sg.finish(stats);
+}
+
+// ---- periodic least-squares fit onto the track's knots (rl_spline_fit.hpp)
+static int spline_fit_check(const rl_ctx* ctx, const rl_track* trk, const double* xy, int B, int P, int stride, const double* out_ctrl,
+                            const double* out_stats, size_t& lds_bytes) {
+  if (!ctx || !trk || !xy || !out_ctrl || !out_stats) return fail(RL_ERR_ARG, "null argument");
+  if (B <= 0) return fail(RL_ERR_ARG, "B <= 0");
+  if (stride < 2) return fail(RL_ERR_ARG, "stride < 2");
+  const int m = trk->n - trk->k;
+  if (m < 2 * trk->k + 1 || m > rl::kFitMaxM) return fail(RL_ERR_UNSUPPORTED, "spline fit: 2k+1 <= n-k <= 192");
+  if (P < 1 || P > rl::kFitMaxP) return fail(RL_ERR_UNSUPPORTED, "spline fit: 1 <= P <= 4096");
+  lds_bytes = rl::fit_lds_layout(trk->k, m, P).total_bytes;
+  if (lds_bytes > (size_t)ctx->max_lds) return fail(RL_ERR_UNSUPPORTED, "spline fit: problem does not fit LDS");
+  return RL_OK;
+}
+
+int rl_spline_fit_batch_dev(rl_ctx* ctx, const rl_track* trk, const double* xy, int B, int P, int stride, const double* u,
+                            int u_per_instance, double* out_ctrl, double* out_stats) {
+  size_t lds = 0;
+  if (int rc = spline_fit_check(ctx, trk, xy, B, P, stride, out_ctrl, out_stats, lds)) return rc;
+  RL_HIP(hipSetDevice(ctx->device));
+  const rl::TrackDev td = trk->dev();
+  return by_degree(trk->k, [&](auto kc) {
+    return launch(ctx, rl::k_spline_fit<RL_DEGREE(kc)>, dim3(B), dim3(rl::kFitThreads), lds, td, xy, P, stride, u,
+                  u_per_instance, out_ctrl, out_stats);
+  });
+}
+
+int rl_spline_fit_batch_host(rl_ctx* ctx, const rl_track* trk, const double* xy, int B, int P, int stride, const double* u,
+                             int u_per_instance, double* out_ctrl, double* out_stats) {
+  size_t lds = 0;
+  if (int rc = spline_fit_check(ctx, trk, xy, B, P, stride, out_ctrl, out_stats, lds)) return rc;
+  Staging sg(ctx);
+  const double* dxy = sg.in(xy, (size_t)B * P * stride);
+  const double* du = sg.in(u, u_per_instance ? (size_t)B * P : (size_t)P);
+  double* dctrl = sg.out(out_ctrl, (size_t)B * trk->n * 2);
+  double* dstats = sg.out(out_stats, (size_t)B * 4);
+  sg.run([&] { return rl_spline_fit_batch_dev(ctx, trk, dxy, B, P, stride, du, u_per_instance, dctrl, dstats); });
+  return sg.finish();
 }
 
 // ------------------------------------------------------------------------------------------------

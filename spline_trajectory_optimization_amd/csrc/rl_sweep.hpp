@@ -40,6 +40,9 @@ struct SweepArgs {
   size_t aux_stride;       // doubles per instance
   int* n_raised;           // [B] or null: steps whose re-sampling raised (control point written, table stale, not counted)
   int* raise_flag;         // [B]: set by the plain reference-order kernel when an instance needs the RAISE instantiation
+  // per-instance start lines (SweepConfigFrom instantiations only; rl_mincurv_solve_batch_from_*)
+  const double* ctrl0;     // null (the track's initial control points) or [B,n,2]: the line instance b starts from
+  const int* i_start_rows; // null (i_start above, shared) or DEVICE [B,max_iter]: instance b's start indices, validated in the kernel
 };
 
 // In-kernel stamps (diagnostic build -DRL_STAMPS only, tools/stamp_sweep.py): where a wave's cycles go, per phase.
@@ -166,6 +169,15 @@ struct SweepConfig {
   static_assert(DRIVER == Driver::Sweep || ARITH == Arith::Fast || ARITH == Arith::Reference, "the sliding-window driver exists in the fast and in the reference-order arithmetic");
   // all-global sweep: ~31 KB of LDS, four workgroups per CU -- which caps it at 128 VGPRs
   static constexpr int workgroups_per_cu = (RESIDENCY == Residency::Global && DRIVER == Driver::Sweep) ? 4 : 1;
+  // per-instance start lines: false here, so that every instantiation on a SweepConfig compiles from the code it always had
+  static constexpr bool from = false;
+};
+// The same sweep started per instance from a.ctrl0[b] and a.i_start_rows[b] (rl_mincurv_solve_batch_from_*): instantiations
+// of their own, under names of their own, next to the ones above.
+template <int K_, Residency RESIDENCY, Arith ARITH = Arith::Fast>
+struct SweepConfigFrom : SweepConfig<K_, RESIDENCY, Driver::Sweep, ARITH, false> {
+  static_assert(RESIDENCY != Residency::CrossingsLds, "per-instance start lines: all-LDS or all-global residency");
+  static constexpr bool from = true;
 };
 
 template <class Cfg>
@@ -176,6 +188,7 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
   constexpr bool JOINT = Cfg::driver == Driver::Window, DUMP = Cfg::DUMP;
   constexpr bool STRICT = Cfg::arith != Arith::Fast, RAISE = Cfg::arith == Arith::ReferenceRaise, LITE = Cfg::arith == Arith::Branch;
   constexpr bool STAGED = !RINGS_LDS;   // staged windows: rings in global memory
+  constexpr bool FROM = Cfg::from;      // per-instance start line and start indices
   if constexpr (RAISE) { if (!a.raise_flag || a.raise_flag[blockIdx.x] == 0) return; }
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   double* smem = reinterpret_cast<double*>(smem_raw);
@@ -220,7 +233,15 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
   using SR = StrictRows<K>;
 
   // ---- prologue: control points, ring vertices, chunk circles
-  for (int j = tid; j < n; j += BLOCK) { cx[j] = tr.c0[j]; cy[j] = tr.c0[n + j]; }
+  bool from_c0 = true;
+  if constexpr (FROM) {
+    if (a.ctrl0) {
+      from_c0 = false;
+      const double2* c = reinterpret_cast<const double2*>(a.ctrl0) + (size_t)b * n;
+      for (int j = tid; j < n; j += BLOCK) { const double2 v = c[j]; cx[j] = v.x; cy[j] = v.y; }
+    }
+  }
+  if (from_c0) for (int j = tid; j < n; j += BLOCK) { cx[j] = tr.c0[j]; cy[j] = tr.c0[n + j]; }
   if (a.form == 1) {  // widths: vertex i = p0_i + w_l n0_i  /  p0_i - w_r n0_i
     const double2* w = reinterpret_cast<const double2*>(a.in) + (size_t)b * N;
     for (int i = tid; i < N; i += BLOCK) {
@@ -575,6 +596,24 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
 #endif
   const int ignore_front = K / 2, ignore_rear = K - ignore_front;  // optimizer.py:297-302
   const int i_max = n - ignore_rear, i_min = ignore_front;
+  // outer iterations this instance runs and where each starts: the kernel arguments, or (FROM) the instance's own row, read in a
+  // branch of its own -- one pointer that selects between the argument array and global memory would cost every reader scratch.
+  // A row with an index outside [i_min, i_max) runs no step (status -1, the start line comes back).
+  int n_iter = a.max_iter;
+  bool bad_row = false;
+  if constexpr (FROM) {
+    if (a.i_start_rows) {
+      for (int it = 0; it < a.max_iter; ++it) {
+        const int st = a.i_start_rows[(size_t)b * a.max_iter + it];
+        if (st < i_min || st >= i_max) bad_row = true;
+      }
+      if (bad_row) n_iter = 0;
+    }
+  }
+  auto start_of = [&](int it) -> int {
+    if constexpr (FROM) { if (a.i_start_rows) return a.i_start_rows[(size_t)b * a.max_iter + it]; }
+    return a.i_start[it];
+  };
   const double* __restrict__ D0 = tr.D;
   const double* __restrict__ D2 = tr.D + (size_t)2 * (K + 1) * N;
   int n_skipped = 0;
@@ -585,11 +624,11 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
     double* c12 = smem + L.off_c12;      // derivative-spline coefficients around the NEXT control point: c1x | c1y | c2x | c2y, 2K each
     double* terms = smem + L.off_terms;  // [6][kTermStride] cost terms of the current chunk of support samples
     const int steps = i_max - i_min;
-    const int total_steps = a.max_iter * 2 * steps;
+    const int total_steps = n_iter * 2 * steps;
     auto step_index = [&](int q) {       // optimizer.py:303-324
       const int it = q / (2 * steps), pass = (q / steps) & 1, stp = q % steps;
       const int i_loop = pass == 0 ? stp : steps - stp;
-      int idx = i_loop + a.i_start[it];
+      int idx = i_loop + start_of(it);
       if (idx >= i_max) idx = idx - i_max + i_min;
       return idx;
     };
@@ -857,7 +896,7 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
     int idx_n = total_steps > 0 ? step_index(0) : 0;
     int s0_n = tr.sup[2 * idx_n + lane_zero()], s1_n = tr.sup[2 * idx_n + 1 + lane_zero()];
     // (outer iteration, pass, step) of the next step, advanced by counting: step_index() divides three times
-    int it_n = 0, pass_n = 0, stp_n = 0, ist_n = total_steps > 0 ? a.i_start[0] : 0;
+    int it_n = 0, pass_n = 0, stp_n = 0, ist_n = total_steps > 0 ? start_of(0) : 0;
     for (int q = 0; q < total_steps; ++q) {
       const int it = it_n, pass = pass_n;
       const int idx = idx_n;
@@ -866,7 +905,7 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
         if (++stp_n == steps) {
           stp_n = 0;
           pass_n ^= 1;
-          if (pass_n == 0) { ++it_n; ist_n = a.i_start[it_n]; }
+          if (pass_n == 0) { ++it_n; ist_n = start_of(it_n); }
         }
         idx_n = (pass_n == 0 ? stp_n : steps - stp_n) + ist_n;
         if (idx_n >= i_max) idx_n = idx_n - i_max + i_min;
@@ -1587,8 +1626,8 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
       if (tid == 0 && a.n_success) a.n_success[(size_t)b * 2 * a.max_iter + 2 * it + 1] = 0;
     }
   } else
-  for (int it = 0; it < a.max_iter; ++it) {
-    const int st = a.i_start[it];
+  for (int it = 0; it < n_iter; ++it) {
+    const int st = start_of(it);
     for (int pass = 0; pass < 2; ++pass) {
       int ok_count = 0;
       const int steps = i_max - i_min;
@@ -1761,6 +1800,12 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
   // (the reference-order loop ends its steps with a barrier that orders LDS only: the bound points the table below reads were
   // written to global memory by other waves -- one full barrier here makes them visible)
   if constexpr (STRICT && !RINGS_LDS) __syncthreads();
+  if constexpr (FROM) {
+    if (bad_row) {
+      n_skipped = -1;
+      if (a.n_success) for (int q = tid; q < 2 * a.max_iter; q += BLOCK) a.n_success[(size_t)b * 2 * a.max_iter + q] = 0;
+    }
+  }
   if (tid == 0 && a.status) a.status[b] = n_skipped;
   for (int j = tid; j < n; j += BLOCK) {
     reinterpret_cast<double2*>(a.out_ctrl)[(size_t)b * n + j] = make_double2(cx[j], cy[j]);

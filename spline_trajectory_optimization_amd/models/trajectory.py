@@ -217,6 +217,28 @@ class BSplineTrajectory:
     def copy(self):
         return copy.deepcopy(self)
 
+    def refit(self, coordinates, u=None):
+        """A copy on the SAME knots whose control points are the periodic least-squares fit through `coordinates` [P,2]
+        (u None: chord-length parameters; else [P] in [0,1]) -> rl_spline_fit_batch_host.  What the reference's optimiser
+        wanted inside its loop (optimizer.py:327, commented out) without FITPACK choosing new knots.  `_length` is
+        recomputed.  ValueError when the fit fails (rank deficient or non-finite input)."""
+        from .. import _lib
+        pts = np.ascontiguousarray(coordinates, dtype=np.float64)
+        if pts.ndim != 2 or pts.shape[1] < 2:
+            raise ValueError("coordinates should be P * 2")
+        knots, cx, cy, k = self._tck()
+        trk = _lib.Track(_lib.Context.get(), knots, cx, cy, k, 8)
+        ctrl, stats = ops.spline_fit_host(trk, pts[None, :, :2], None if u is None else np.asarray(u, dtype=np.float64))
+        if stats[0, 0] != 0:
+            raise ValueError(f"refit failed: status {int(stats[0, 0])} "
+                             f"({'rank deficient' if stats[0, 0] == 1 else 'non-finite input or parameter outside [0,1]'}), "
+                             f"pivot ratio {stats[0, 3]:.3e}")
+        out = self.copy()
+        out._spl_x.c[:] = ctrl[0, :, 0]
+        out._spl_y.c[:] = ctrl[0, :, 1]
+        out._length = out.eval_sectional_length((0.0, 1.0))
+        return out
+
     def set_control_point(self, idx, coord):
         self._spl_x.c[idx], self._spl_y.c[idx] = coord[0], coord[1]
 

@@ -183,12 +183,25 @@ def mincurv_sweep_joint(track, cx, cy, i_start, want_points=True, arith=None):
     return cx, cy, pts, ns, st
 
 
-def solve_batch_host(track, bounds_form, bounds, i_start, search=_lib.SEARCH_WINDOWED, B=None, arith=None):
+def _i_start_rows(i_start, B):
+    """(host int32 array, per_instance, max_iter) of a start-index argument [max_iter] or [B,max_iter]."""
+    i_start = np.ascontiguousarray(i_start, dtype=np.int32)
+    if i_start.ndim == 2:
+        if i_start.shape[0] != B:
+            raise ValueError(f"i_start: expected [{B},max_iter] or [max_iter], got {i_start.shape}")
+        return i_start, 1, i_start.shape[1]
+    if i_start.ndim != 1:
+        raise ValueError(f"i_start: expected [{B},max_iter] or [max_iter], got {i_start.shape}")
+    return i_start, 0, len(i_start)
+
+
+def solve_batch_host(track, bounds_form, bounds, i_start, search=_lib.SEARCH_WINDOWED, B=None, arith=None, ctrl0=None):
     """Batched sweep with host (numpy) buffers.  bounds: widths [B,N,2] / points [B,N,4] / None.
+    ctrl0: None (every instance starts from the track's control points) or [B,n,2], instance b's start line;
+    i_start: [max_iter] shared or [B,max_iter] per instance (rl_mincurv_solve_batch_from_host; the defaults go to
+    rl_mincurv_solve_batch_host).
     Returns (ctrl [B,n,2], xy [B,N,2], n_success [B,max_iter,2], status [B], stats)."""
     ctx = track.ctx
-    i_start, ip = as_i(i_start)
-    max_iter = len(i_start)
     if bounds is not None:
         bounds, bp = as_d(bounds)
         B = bounds.shape[0]
@@ -196,31 +209,64 @@ def solve_batch_host(track, bounds_form, bounds, i_start, search=_lib.SEARCH_WIN
         assert bounds.shape == (B, track.N, cols), bounds.shape
     else:
         bp = None
+        if B is None and ctrl0 is not None:
+            B = np.shape(ctrl0)[0]
         assert B is not None and bounds_form == _lib.BOUNDS_SHARED_RINGS
+    i_start, per, max_iter = _i_start_rows(i_start, B)
+    ip = i_start.ctypes.data_as(_ip)
     ctrl = np.zeros((B, track.n, 2)); xy = np.zeros((B, track.N, 2))
     ns = np.zeros((B, max_iter, 2), dtype=np.int32); status = np.zeros(B, dtype=np.int32)
     st = Stats()
     with _arith_scope(ctx, arith):
-        check(ctx.lib.rl_mincurv_solve_batch_host(ctx.h, track.h, int(bounds_form), bp, int(B), ip,
-                                                  max_iter, int(search), ctrl.ctypes.data_as(_dp),
-                                                  xy.ctypes.data_as(_dp), ns.ctypes.data_as(_ip),
-                                                  status.ctypes.data_as(_ip), ctypes.byref(st)))
+        if ctrl0 is None and not per:
+            check(ctx.lib.rl_mincurv_solve_batch_host(ctx.h, track.h, int(bounds_form), bp, int(B), ip,
+                                                      max_iter, int(search), ctrl.ctypes.data_as(_dp),
+                                                      xy.ctypes.data_as(_dp), ns.ctypes.data_as(_ip),
+                                                      status.ctypes.data_as(_ip), ctypes.byref(st)))
+        else:
+            cp = None
+            if ctrl0 is not None:
+                ctrl0, cp = as_d(ctrl0)
+                if ctrl0.shape != (B, track.n, 2):
+                    raise ValueError(f"ctrl0: expected shape {(B, track.n, 2)}, got {ctrl0.shape}")
+            check(ctx.lib.rl_mincurv_solve_batch_from_host(ctx.h, track.h, int(bounds_form), bp, int(B), cp, ip, per,
+                                                           max_iter, int(search), ctrl.ctypes.data_as(_dp),
+                                                           xy.ctypes.data_as(_dp), ns.ctypes.data_as(_ip),
+                                                           status.ctypes.data_as(_ip), ctypes.byref(st)))
     return ctrl, xy, ns, status, st
 
 
-def solve_batch_torch(track, bounds_form, bounds, i_start, search=_lib.SEARCH_WINDOWED, out=None, arith=None):
+def solve_batch_torch(track, bounds_form, bounds, i_start, search=_lib.SEARCH_WINDOWED, out=None, arith=None, ctrl0=None):
     """Batched sweep on DEVICE tensors (torch is plumbing for memory and streams only).
-    bounds: float64 cuda tensor [B,N,2|4].  Enqueues on torch's current stream, no sync.
-    Returns dict(ctrl, xy, n_success, status) of cuda tensors."""
+    bounds: float64 cuda tensor [B,N,2|4] (None with BOUNDS_SHARED_RINGS, which then needs ctrl0 for the batch size).
+    ctrl0: None or a float64 cuda tensor [B,n,2], instance b's start line; i_start: [max_iter] (host) or [B,max_iter] as a
+    numpy array or an int32 cuda tensor, which the kernel validates (status -1 for a row with an index out of range):
+    rl_mincurv_solve_batch_from_dev; the defaults go to rl_mincurv_solve_batch_dev.
+    Enqueues on torch's current stream, no sync.  Returns dict(ctrl, xy, n_success, status) of cuda tensors."""
     import torch
     ctx = track.ctx
-    assert bounds.is_cuda and bounds.dtype == torch.float64 and bounds.is_contiguous()
-    B = bounds.shape[0]
-    cols = {_lib.BOUNDS_WIDTHS: 2, _lib.BOUNDS_POINTS: 4}[bounds_form]
-    assert tuple(bounds.shape) == (B, track.N, cols)
-    i_start, ip = as_i(i_start)
-    max_iter = len(i_start)
-    dev = bounds.device
+    if bounds is None:
+        if bounds_form != _lib.BOUNDS_SHARED_RINGS or ctrl0 is None:
+            raise ValueError("bounds: None needs BOUNDS_SHARED_RINGS and ctrl0 [B,n,2]")
+        B, dev = int(ctrl0.shape[0]), ctrl0.device
+    else:
+        assert bounds.is_cuda and bounds.dtype == torch.float64 and bounds.is_contiguous()
+        B, dev = bounds.shape[0], bounds.device
+        cols = {_lib.BOUNDS_WIDTHS: 2, _lib.BOUNDS_POINTS: 4}[bounds_form]
+        assert tuple(bounds.shape) == (B, track.N, cols)
+    rows = None
+    if isinstance(i_start, torch.Tensor):
+        if i_start.dim() == 1:
+            i_start = i_start.cpu().numpy()
+        else:
+            rows = _check_torch(i_start, "i_start", (B, i_start.shape[1]), torch.int32)
+            per, max_iter = 1, int(i_start.shape[1])
+    if rows is None:
+        i_start, per, max_iter = _i_start_rows(i_start, B)
+        if per:
+            rows = torch.from_numpy(i_start).to(dev)
+    if ctrl0 is not None:
+        _check_torch(ctrl0, "ctrl0", (B, track.n, 2))
     if out is None:
         out = {
             "ctrl": torch.empty((B, track.n, 2), dtype=torch.float64, device=dev),
@@ -230,13 +276,80 @@ def solve_batch_torch(track, bounds_form, bounds, i_start, search=_lib.SEARCH_WI
         }
     ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
     st = Stats()
+    p = lambda t_: None if t_ is None else ctypes.c_void_p(t_.data_ptr())  # noqa: E731
     with _arith_scope(ctx, arith):
-        check(ctx.lib.rl_mincurv_solve_batch_dev(
-            ctx.h, track.h, int(bounds_form), ctypes.c_void_p(bounds.data_ptr()), int(B), ip, max_iter,
-            int(search), ctypes.c_void_p(out["ctrl"].data_ptr()), ctypes.c_void_p(out["xy"].data_ptr()),
-            ctypes.c_void_p(out["n_success"].data_ptr()), ctypes.c_void_p(out["status"].data_ptr()),
-            ctypes.byref(st)))
+        if ctrl0 is None and not per:
+            check(ctx.lib.rl_mincurv_solve_batch_dev(
+                ctx.h, track.h, int(bounds_form), p(bounds), int(B), i_start.ctypes.data_as(_ip), max_iter,
+                int(search), p(out["ctrl"]), p(out["xy"]), p(out["n_success"]), p(out["status"]), ctypes.byref(st)))
+        else:
+            ip = p(rows) if per else ctypes.c_void_p(i_start.ctypes.data)
+            check(ctx.lib.rl_mincurv_solve_batch_from_dev(
+                ctx.h, track.h, int(bounds_form), p(bounds), int(B), p(ctrl0), ip, per, max_iter,
+                int(search), p(out["ctrl"]), p(out["xy"]), p(out["n_success"]), p(out["status"]), ctypes.byref(st)))
     out["stats"] = st
+    return out
+
+
+FIT_STATS_COLUMNS = ("status", "rms_residual", "max_residual", "pivot_ratio")   # rl_spline_fit_batch_*: out_stats[B,4]
+
+
+def _fit_u(u, B, P):
+    """(shape, u_per_instance) of a parameter argument [P] or [B,P]; ValueError otherwise."""
+    if u is None:
+        return None, 0
+    shape = tuple(u.shape)
+    if shape == (P,):
+        return shape, 0
+    if shape == (B, P):
+        return shape, 1
+    raise ValueError(f"u: expected [{P}] or [{B},{P}], got {shape}")
+
+
+def spline_fit_host(track, xy, u=None):
+    """Periodic least-squares B-spline through P points per instance on the track's knots (rl_spline_fit_batch_host): what
+    splprep([x, y], u=u, t=knots, task=-1, per=True, k=k) returns for the closed loop.  xy numpy [B,P,2] or [B,P,19] (x, y in
+    the first two columns; a single [P,2|19] is a batch of one); u None (chord length), [P] or [B,P] in [0,1].
+    Returns (ctrl [B,n,2], stats [B,4] in the order of FIT_STATS_COLUMNS); an instance with status != 0 gets the track's
+    control points."""
+    xy = np.ascontiguousarray(xy, dtype=np.float64)
+    if xy.ndim == 2:
+        xy = xy[None]
+    if xy.ndim != 3 or xy.shape[2] < 2:
+        raise ValueError(f"xy: expected [B,P,2] or [B,P,19], got {xy.shape}")
+    B, P, stride = xy.shape
+    up = None
+    if u is not None:
+        u, up = as_d(u)
+    _, per = _fit_u(u, B, P)
+    ctx = track.ctx
+    ctrl = np.empty((B, track.n, 2)); stats = np.empty((B, 4))
+    check(ctx.lib.rl_spline_fit_batch_host(ctx.h, track.h, xy.ctypes.data_as(_dp), B, P, stride, up, per,
+                                           ctrl.ctypes.data_as(_dp), stats.ctypes.data_as(_dp)))
+    return ctrl, stats
+
+
+def spline_fit_torch(track, xy, u=None, out=None):
+    """spline_fit_host on DEVICE tensors (float64 cuda, contiguous): xy [B,P,2] or [B,P,19] (the stride is the last
+    dimension), u None, [P] or [B,P].  Enqueues on torch's current stream, no sync (rl_spline_fit_batch_dev).
+    Returns (ctrl [B,n,2], stats [B,4]) cuda tensors (`out` = such a pair, if given)."""
+    import torch
+    if getattr(xy, "ndim", None) != 3 or xy.shape[2] < 2:
+        raise ValueError("xy: expected [B,P,2] or [B,P,19]")
+    B, P, stride = (int(v) for v in xy.shape)
+    _check_torch(xy, "xy", (B, P, stride))
+    ushape, per = _fit_u(u, B, P)
+    if ushape:
+        _check_torch(u, "u", ushape)
+    dev = xy.device
+    if out is None:
+        out = (torch.empty((B, track.n, 2), dtype=torch.float64, device=dev),
+               torch.empty((B, 4), dtype=torch.float64, device=dev))
+    _check_torch(out[0], "out[0]", (B, track.n, 2)); _check_torch(out[1], "out[1]", (B, 4))
+    ctx = track.ctx
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    p = lambda t_: None if t_ is None else ctypes.c_void_p(t_.data_ptr())  # noqa: E731
+    check(ctx.lib.rl_spline_fit_batch_dev(ctx.h, track.h, p(xy), B, P, stride, p(u), per, p(out[0]), p(out[1])))
     return out
 
 

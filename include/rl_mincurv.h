@@ -126,6 +126,8 @@ int rl_ctx_set_numpy_raise(rl_ctx* ctx, int on);
  *   "tables_search"   RL_SEARCH_BRUTE | _CULLED | _WINDOWED (default): ring search of rl_tables_batch_* and rl_pose_tables_batch_*
  *   "tables_rings"    0 = rl_tables_batch_* and rl_pose_tables_batch_* keep an instance's ring vertices in LDS where they fit
  *                     (default), 1 = in the arena
+ *   "frenet_search"   1 = rl_frenet_batch_* bounds a point from the piece the previous point of its line landed on (default),
+ *                     0 = from the table of the pieces alone
  * Defaults come from RL_QSS_DF / RL_QSS_V1 / RL_QSS_DF_WAVES / RL_QSS_DF_BAIL_AT, read ONCE in rl_ctx_create. */
 int rl_ctx_set_option(rl_ctx* ctx, const char* name, int value);
 /* test aid: out[n,5] = yaw, cos / sin(yaw + pi/2), cos / sin(yaw - pi/2) of the tangents (dx, dy), as the
@@ -528,6 +530,44 @@ int rl_pose_tables_batch_dev(rl_ctx* ctx, const rl_track* trk, int form, const d
 int rl_pose_tables_batch_host(rl_ctx* ctx, const rl_track* trk, int form, const double* X, int B, int N, const double* ss,
                               const double* cxs, const double* cys, int M, int bounds_form, const double* bounds,
                               const double* base, int base_per_instance, const double* T, double* points);
+
+/* ---- global -> Frenet (csrc/rl_frenet.hpp): the inverse of RaceTrack.frenet_to_global for B lines of P points, one launch.
+ * The centre line is given as for RL_POSE_FRENET above (ss[M+1], cxs[4][M], cys[4][M]; ss[M] = L).  For every point p = (x, y):
+ *   s   in [0, L): the abscissa of the GLOBAL minimiser of |p - c(s)| over the closed centre line (a root of
+ *       f(s) = (c(s) - p) . c'(s) with f'(s) >= 0; a foot on a breakpoint belongs to the piece that starts there; L is returned as 0)
+ *   n   (p - c(s)) . (-c'_y, c'_x) / |c'|: left of the centre line is positive, frenet_to_global(s, n, .) gives p back
+ *   xi  atan2(sin d, cos d), d = yaw - atan2(c'_y, c'_x): the inverse of frenet_to_global's heading; 0 where no heading is given
+ *   g   f'(s) / |c'(s)|^2 = 1 - kappa(s) n up to the pieces' parametric speed: the factor the double-track model's s_dot divides
+ *       by and the conditioning of the projection (g -> 0: p sits at the centre of curvature, s is not defined)
+ *   points  [B,P,stride], x and y in columns 0 and 1; stride 19: a Trajectory table, the heading is column 3 (YAW) and `yaw` is
+ *           ignored; stride 2: the heading is yaw[B,P], or none when `yaw` is NULL
+ *   out     [B,P,4] = (s, n, xi, g)
+ *   status  NULL or int32 [B,P]: 0 ok; 1 a non-finite coordinate (four NaNs for that point, nothing else changes); 2 the
+ *           refinement reached its iteration cap (the best iterate is returned)
+ *   stats   NULL or [B,4]: points with status != 0, min g and max |n| over the status-0 points (+inf and 0 where there is none),
+ *           the largest number of refinement evaluations a point's foot took
+ * Results do not depend on the batch position, on the order of the points or on the search ("frenet_search" of
+ * rl_ctx_set_option: 1, the default, starts from the piece the previous point of the line landed on; 0 bounds every point from
+ * the table alone): identical bits.  Limits: M >= 3, P >= 1; the table of the pieces is LDS resident (24 B per piece + 6 KiB):
+ * RL_ERR_UNSUPPORTED where it does not fit (M up to about 2400 in 64 KiB).  RL_ERR_ARG for nulls, B <= 0, P < 1, M < 3, a stride
+ * other than 2 or 19.  *_dev: device pointers throughout (the pieces too), the context's stream, no synchronisation, no scratch.
+ * *_host: host pointers, synchronises. */
+int rl_frenet_batch_dev(rl_ctx* ctx, const double* points, int B, int P, int stride, const double* yaw, const double* ss,
+                        const double* cxs, const double* cys, int M, double* out, int* status, double* stats);
+int rl_frenet_batch_host(rl_ctx* ctx, const double* points, int B, int P, int stride, const double* yaw, const double* ss,
+                         const double* cxs, const double* cys, int M, double* out, int* status, double* stats);
+/* A projected line at given abscissae (what a min-time NLP start needs: its nodes are fixed s_j).  Per instance fr[P,4] of
+ * rl_frenet_batch_*, C >= 0 channels vals[P,C] (e.g. SPEED; NULL for C = 0) and the node abscissae s_nodes[Nn] shared by the
+ * batch (wrapped into [0, L)).  The s_i must be finite and cyclically strictly increasing -- exactly one i with
+ * s_{(i+1) % P} <= s_i -- and no point may carry NaNs (status 1 of the projection).  Per node: the bracketing pair by binary search
+ * in the sequence rotated to start behind the wrap, the wrap pair bridged with + L; n, xi and the channels linear in s, the
+ * right neighbour's xi first brought to within pi of the left one (align_yaw).
+ *   out [B,Nn,2+C] = (n, xi, channels)      status int32 [B]: 0 ok; 1 not monotone or a bad point: the instance's rows are zeros
+ * RL_ERR_ARG for nulls, B <= 0, P < 1, Nn < 1, C < 0, C > 0 without vals, L <= 0.  *_dev / *_host as above. */
+int rl_frenet_resample_dev(rl_ctx* ctx, const double* fr, const double* vals, int C, int B, int P, const double* s_nodes, int Nn,
+                           double L, double* out, int* status);
+int rl_frenet_resample_host(rl_ctx* ctx, const double* fr, const double* vals, int C, int B, int P, const double* s_nodes, int Nn,
+                            double L, double* out, int* status);
 
 /* Per-instance summary of simulated tables points [B,N,19]: out [B,8] = lap time (sum of TIME, added in index order), the
  * reference's total_time (TIME[0], simulator.py:378), its average_speed (DIST_TO_SF_FWD[0] / TIME[0], :379-380), max / min

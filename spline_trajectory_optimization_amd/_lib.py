@@ -118,6 +118,14 @@ _SIGNATURES = {
                                                 ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp]),
     "rl_pose_tables_batch_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp,
                                                  ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_int, _dp, _dp]),
+    "rl_frenet_batch_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int,
+                                           _vp, _vp, _vp]),
+    "rl_frenet_batch_host": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int,
+                                            _dp, _ip, _dp]),
+    "rl_frenet_resample_dev": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
+                                              ctypes.c_double, _vp, _vp]),
+    "rl_frenet_resample_host": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_int,
+                                               ctypes.c_double, _dp, _ip]),
     "rl_table_summary_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp]),
     "rl_table_summary_host": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _ip, _dp]),
 }
@@ -213,7 +221,7 @@ class Context:
 
     def set_option(self, name, value):
         """Test hooks (include/rl_mincurv.h: rl_ctx_set_option): "qss_kernel", "qss_df_waves", "qss_df_bail_at",
-        "tables_search", "tables_rings"."""
+        "tables_search", "tables_rings", "frenet_search"."""
         check(self.lib.rl_ctx_set_option(self.h, name.encode(), int(value)))
 
     def set_numpy_raise(self, on):

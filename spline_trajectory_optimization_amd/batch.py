@@ -215,6 +215,61 @@ def min_time_initial_guess(points):
     return s, X, U, T
 
 
+MIN_TIME_U0 = (1.0, -1.0, 0.001, 0.0)   # the reference's constant controls of an initial guess (min_time_optimizer.py:146-151)
+
+
+def min_time_centerline_guess_torch(s_nodes, base, B):
+    """The guess optimise_track_batch hands the NLP without start lines: on the centre line with the QSS table's speeds and
+    times.  s_nodes [N], base [N,19] (simulated centre-line table), cuda tensors.  Returns (X0 [B,N,6], U0 [B,N,4], T0 [B,N])."""
+    import torch
+    N = int(s_nodes.shape[0])
+    X = torch.zeros((B, N, 6), dtype=torch.float64, device=s_nodes.device)
+    X[:, :, 0] = s_nodes
+    X[:, :, 5] = base[:, 4]
+    U = torch.tensor(MIN_TIME_U0, dtype=torch.float64, device=s_nodes.device).repeat(B, N, 1).contiguous()
+    T = base[:, 16].repeat(B, 1).contiguous()
+    return X, U, T
+
+
+def min_time_guess_from_lines_torch(race_track, points, s_nodes, kappa_nodes, base, pieces=None):
+    """Initial guesses of the min-time NLP from B lines in global coordinates, e.g. the simulated tables of a min-curvature
+    batch (lap_times_torch(...)["points"]): project every line onto race_track's centre line (ops.frenet_torch), take its
+    lateral offset, relative heading and SPEED at the NLP's nodes (ops.frenet_resample_torch), and from them
+        X0[b,j] = (s_j, n_j, xi_j, 0, 0, v_j),  U0 = MIN_TIME_U0,  T0[b,j] = (s_{j+1} - s_j) (1 - n_j kappa_j) / (v_j cos xi_j)
+    (the last step closes with the track length; the model's s_dot at zero slip).  points [B,P,19], s_nodes [N], kappa_nodes
+    [N], base [N,19] (the simulated centre-line table): float64 cuda tensors; pieces: race_track.centerline_pieces() as cuda
+    tensors (None uploads them).  An instance whose line cannot be used -- a point that did not project, an abscissa that
+    is not cyclically increasing, a step time that is not positive and finite -- gets the centre-line guess of
+    min_time_centerline_guess_torch instead (torch.where: no host round trip).  Enqueues on torch's current stream, no sync.
+    Returns (X0 [B,N,6], U0 [B,N,4], T0 [B,N], status int32 [B]: 0 = from the line, 1 = projection / abscissa, 2 = step time)."""
+    import torch
+    dev = points.device
+    if pieces is None:
+        pieces = tuple(torch.from_numpy(a).to(dev) for a in race_track.centerline_pieces())
+    if getattr(points, "ndim", None) != 3 or points.shape[2] != _lib.NCOL:
+        raise ValueError("points: expected [B,P,19]")
+    B, N = int(points.shape[0]), int(s_nodes.shape[0])
+    ops._check_torch(kappa_nodes, "kappa_nodes", (N,))
+    ops._check_torch(base, "base", (N, _lib.NCOL))
+    length = float(race_track.center_s.get_length())
+    fr, _, fstats = ops.frenet_torch(pieces, points)
+    res, rstatus = ops.frenet_resample_torch(fr, points[:, :, 4:5].contiguous(), s_nodes, length)
+    n, xi, v = res[:, :, 0], res[:, :, 1], res[:, :, 2]
+    ds = torch.cat([s_nodes[1:], s_nodes.new_full((1,), length)]) - s_nodes
+    T = ds[None, :] * (1.0 - n * kappa_nodes[None, :]) / (v * torch.cos(xi))
+    bad_line = (rstatus != 0) | (fstats[:, 0] != 0)
+    bad_time = ~(torch.isfinite(T) & (T > 0)).all(dim=1)
+    status = torch.where(bad_line, 1, torch.where(bad_time, 2, 0)).to(torch.int32)
+    Xc, U, Tc = min_time_centerline_guess_torch(s_nodes, base, B)
+    X = torch.zeros_like(Xc)
+    X[:, :, 0] = s_nodes
+    X[:, :, 1], X[:, :, 2], X[:, :, 5] = n, xi, v
+    use = (status != 0)
+    X = torch.where(use[:, None, None], Xc, X).contiguous()
+    T = torch.where(use[:, None], Tc, T).contiguous()
+    return X, U, T, status
+
+
 def signed_curvature(points):
     """Centre-line curvature with sign at the samples of a sampled table (the turn radius of column 5 is
     unsigned): heading change per arc length, central differences over the closed line."""

@@ -71,6 +71,7 @@ struct rl_ctx {
   int qss_kernel = -1, qss_df_waves = 4, qss_df_bail_at = 0;
   // test hooks of rl_tables_batch_*: ring search (RL_SEARCH_*), 1 = ring vertices in the arena even where they fit LDS
   int tables_search = RL_SEARCH_WINDOWED, tables_rings_global = 0;
+  int frenet_search = 1;         // test hook of rl_frenet_batch_*: 0 = every point from the table's own bound, 1 = from the previous point's piece
   // Device scratch owned by the context (grow-only): the *_dev entry points of the QSS simulator and the
   // min-time solve carve their work arrays out of it, so that steady-state calls allocate nothing.
   void* arena = nullptr;

@@ -25,6 +25,7 @@
 #include "rl_tables.hpp"
 #include "rl_pose_tables.hpp"
 #include "rl_spline_fit.hpp"
+#include "rl_frenet.hpp"
 
 namespace {
 double* g_dbg_buf = nullptr;   // rl_debug_dump_enable: step / window dump of the sweep kernels (tests)
@@ -376,6 +377,7 @@ int rl_ctx_set_option(rl_ctx* ctx, const char* name, int value) {
   else if (k == "qss_df_bail_at") { if (value < 0) return fail(RL_ERR_ARG, "qss_df_bail_at >= 0"); ctx->qss_df_bail_at = value; }
   else if (k == "tables_search") { if (value < RL_SEARCH_BRUTE || value > RL_SEARCH_WINDOWED) return fail(RL_ERR_ARG, "tables_search: RL_SEARCH_BRUTE, _CULLED or _WINDOWED"); ctx->tables_search = value; }
   else if (k == "tables_rings") { if (value != 0 && value != 1) return fail(RL_ERR_ARG, "tables_rings: 0 (LDS where they fit) or 1 (arena)"); ctx->tables_rings_global = value; }
+  else if (k == "frenet_search") { if (value != 0 && value != 1) return fail(RL_ERR_ARG, "frenet_search: 0 (table bound for every point) or 1 (from the previous point's piece)"); ctx->frenet_search = value; }
   else return fail(RL_ERR_ARG, "unknown option '" + k + "'");
   return RL_OK;
 }
@@ -1380,6 +1382,78 @@ int rl_pose_tables_batch_host(rl_ctx* ctx, const rl_track* trk, int form, const 
   sg.run([&] {
     return rl_pose_tables_batch_dev(ctx, trk, form, dX, B, N, dss, dcx, dcy, M, bounds_form, din, dbase, base_per_instance, dT, dpts);
   });
+  return sg.finish();
+}
+
+// ---- global -> Frenet: projection of lines onto the centre line, and their coordinates at node abscissae (rl_frenet.hpp)
+static int frenet_check(const rl_ctx* ctx, const double* points, int B, int P, int stride, const double* ss, const double* cxs,
+                        const double* cys, int M, const double* out, size_t& lds_bytes) {
+  if (!ctx || !points || !ss || !cxs || !cys || !out) return fail(RL_ERR_ARG, "null argument");
+  if (B <= 0 || P < 1) return fail(RL_ERR_ARG, "frenet: B >= 1 and P >= 1");
+  if (M < 3) return fail(RL_ERR_ARG, "frenet: at least 3 pieces");
+  if (stride != 2 && stride != RL_NCOL) return fail(RL_ERR_ARG, "frenet: stride 2 (points) or 19 (tables)");
+  lds_bytes = rl::frenet_lds_layout(M).total_bytes;
+  if (lds_bytes > (size_t)ctx->max_lds) return fail(RL_ERR_UNSUPPORTED, "frenet: the table of the pieces does not fit LDS");
+  return RL_OK;
+}
+
+int rl_frenet_batch_dev(rl_ctx* ctx, const double* points, int B, int P, int stride, const double* yaw, const double* ss,
+                        const double* cxs, const double* cys, int M, double* out, int* status, double* stats) {
+  size_t lds = 0;
+  RL_TRY(frenet_check(ctx, points, B, P, stride, ss, cxs, cys, M, out, lds));
+  RL_HIP(hipSetDevice(ctx->device));
+  rl::FrenetArgs a;
+  a.points = points; a.B = B; a.P = P; a.stride = stride; a.yaw = yaw;
+  a.ss = ss; a.cxs = cxs; a.cys = cys; a.M = M;
+  a.search = ctx->frenet_search;
+  a.out = out; a.status = status; a.stats = stats;
+  return launch(ctx, rl::k_frenet, dim3(B), dim3(rl::kFrenetThreads), lds, a);
+}
+
+int rl_frenet_batch_host(rl_ctx* ctx, const double* points, int B, int P, int stride, const double* yaw, const double* ss,
+                         const double* cxs, const double* cys, int M, double* out, int* status, double* stats) {
+  size_t lds = 0;
+  RL_TRY(frenet_check(ctx, points, B, P, stride, ss, cxs, cys, M, out, lds));
+  Staging sg(ctx);
+  const double* dpts = sg.in(points, (size_t)B * P * stride);
+  const double* dyaw = sg.in(yaw, (size_t)B * P);
+  const double* dss = sg.in(ss, (size_t)M + 1);
+  const double* dcx = sg.in(cxs, (size_t)4 * M);
+  const double* dcy = sg.in(cys, (size_t)4 * M);
+  double* dout = sg.out(out, (size_t)B * P * 4);
+  int* dst = sg.out(status, (size_t)B * P);
+  double* dstats = sg.out(stats, (size_t)B * 4);
+  sg.run([&] { return rl_frenet_batch_dev(ctx, dpts, B, P, stride, dyaw, dss, dcx, dcy, M, dout, dst, dstats); });
+  return sg.finish();
+}
+
+static int frenet_resample_check(const rl_ctx* ctx, const double* fr, int C, int B, int P, const double* s_nodes, int Nn, double L,
+                                 const double* out, const int* status) {
+  if (!ctx || !fr || !s_nodes || !out || !status) return fail(RL_ERR_ARG, "null argument");
+  if (B <= 0 || P < 1 || Nn < 1 || C < 0) return fail(RL_ERR_ARG, "frenet resample: B >= 1, P >= 1, Nn >= 1, C >= 0");
+  if (!(L > 0.0)) return fail(RL_ERR_ARG, "frenet resample: the track length must be positive");
+  return RL_OK;
+}
+
+int rl_frenet_resample_dev(rl_ctx* ctx, const double* fr, const double* vals, int C, int B, int P, const double* s_nodes, int Nn,
+                           double L, double* out, int* status) {
+  RL_TRY(frenet_resample_check(ctx, fr, C, B, P, s_nodes, Nn, L, out, status));
+  if (C > 0 && !vals) return fail(RL_ERR_ARG, "frenet resample: C channels without vals");
+  RL_HIP(hipSetDevice(ctx->device));
+  return launch(ctx, rl::k_frenet_resample, dim3(B), dim3(rl::kResampleThreads), (size_t)16, fr, vals, C, P, s_nodes, Nn, L, out, status);
+}
+
+int rl_frenet_resample_host(rl_ctx* ctx, const double* fr, const double* vals, int C, int B, int P, const double* s_nodes, int Nn,
+                            double L, double* out, int* status) {
+  RL_TRY(frenet_resample_check(ctx, fr, C, B, P, s_nodes, Nn, L, out, status));
+  if (C > 0 && !vals) return fail(RL_ERR_ARG, "frenet resample: C channels without vals");
+  Staging sg(ctx);
+  const double* dfr = sg.in(fr, (size_t)B * P * 4);
+  const double* dvals = C > 0 ? sg.in(vals, (size_t)B * P * C) : nullptr;
+  const double* dnodes = sg.in(s_nodes, (size_t)Nn);
+  double* dout = sg.out(out, (size_t)B * Nn * (2 + C));
+  int* dst = sg.out(status, (size_t)B);
+  sg.run([&] { return rl_frenet_resample_dev(ctx, dfr, dvals, C, B, P, dnodes, Nn, L, dout, dst); });
   return sg.finish();
 }
 

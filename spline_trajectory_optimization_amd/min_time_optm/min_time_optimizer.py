@@ -328,7 +328,7 @@ def pose_table(race_track, traj_d, X):
 
 
 def optimise_track_batch(race_track, vehicle, model, left=None, right=None, average_track_width=7.0, speed_cap=30.0,
-                         max_iter=200, tol=1e-6, device=None, track=None):
+                         max_iter=200, tol=1e-6, device=None, track=None, start_points=None):
     """optimise_track for B instances of one track that differ in their boundary distances, as ONE chain on torch's current
     stream with device tensors throughout: QSS warm start (k_qss_sim) -> initial guess -> NLP solve (k_mt_*) -> tables of
     the batch (k_pose_tables) -> their summary (k_table_summary).  No result travels to the host in between; the host set-up is
@@ -341,6 +341,10 @@ def optimise_track_batch(race_track, vehicle, model, left=None, right=None, aver
     step runs on; None builds one (device allocations and table kernels: set-up, not part of the chain).  A track that is
     destroyed frees device memory, which waits for the device: the one used is therefore returned under "track", and the
     chain stays asynchronous for as long as the caller holds the result; pass it back in for the next call.
+    start_points: None, or [B,P,19] simulated tables of B lines in global coordinates (numpy or cuda tensors), e.g.
+    batch.lap_times_torch(...)["points"] of a min-curvature batch on the same track: instance b then starts from line b
+    projected onto the centre line (batch.min_time_guess_from_lines_torch) instead of from the centre line, and the result
+    gains "start_status" (int32 [B]: 0 = started from its line, otherwise from the centre line, see that function).
     Returns dict(points [B,N,19], X [B,N,6], U [B,N,4], T [B,N], stats [B,12], summary [B,8]) of cuda tensors plus "track":
     stats as include/rl_mincurv.h: rl_mintime_solve_batch, summary in the order of ops.SUMMARY_COLUMNS (summary[:, 0] is the
     lap time)."""
@@ -369,12 +373,17 @@ def optimise_track_batch(race_track, vehicle, model, left=None, right=None, aver
     base = base[0]
     # initial guess (min_time_optimizer.py:146-151 as written; DoubleTrackProblem's "reference" mode)
     s_d = up(s)
-    X = torch.zeros((B, N, 6), dtype=torch.float64, device=dev)
-    X[:, :, 0] = s_d
-    X[:, :, 5] = base[:, Trajectory.SPEED]
-    U = torch.tensor([1.0, -1.0, 0.001, 0.0], dtype=torch.float64, device=dev).repeat(B, N, 1).contiguous()
-    T = base[:, Trajectory.TIME].repeat(B, 1).contiguous()
-    stats = ops.mintime_solve_torch(dict(model), s_d, up(race_track.curvature_intp(s)), left_d, right_d, margin,
+    kappa_d = up(race_track.curvature_intp(s))
+    pieces = tuple(up(a) for a in race_track.centerline_pieces())
+    start_status = None
+    if start_points is None:
+        X, U, T = batch.min_time_centerline_guess_torch(s_d, base, B)
+    else:
+        start_d = up(start_points)
+        if start_d.ndim != 3 or int(start_d.shape[0]) != B or int(start_d.shape[2]) != 19:
+            raise ValueError(f"start_points: expected [{B},P,19]")
+        X, U, T, start_status = batch.min_time_guess_from_lines_torch(race_track, start_d, s_d, kappa_d, base, pieces=pieces)
+    stats = ops.mintime_solve_torch(dict(model), s_d, kappa_d, left_d, right_d, margin,
                                     float(race_track.center_s.get_length()), X, U, T, float(average_track_width),
                                     float(speed_cap), max_iter=int(max_iter), tol=float(tol))
     if track is None:
@@ -389,7 +398,9 @@ def optimise_track_batch(race_track, vehicle, model, left=None, right=None, aver
         cx, cy, nx, ny = up(race_track.x_intp(s)), up(race_track.y_intp(s)), -torch.sin(yaw0), torch.cos(yaw0)
         bounds = torch.stack([cx + nx * left_d, cy + ny * left_d, cx + nx * right_d, cy + ny * right_d], dim=2).contiguous()
         form = _lib.BOUNDS_POINTS
-    points = batch.min_time_tables_torch(race_track, track, X, T, form, bounds, base=base,
-                                         pieces=tuple(up(a) for a in race_track.centerline_pieces()))
+    points = batch.min_time_tables_torch(race_track, track, X, T, form, bounds, base=base, pieces=pieces)
     summary = ops.table_summary_torch(points)
-    return {"points": points, "X": X, "U": U, "T": T, "stats": stats, "summary": summary, "track": track}
+    out = {"points": points, "X": X, "U": U, "T": T, "stats": stats, "summary": summary, "track": track}
+    if start_status is not None:
+        out["start_status"] = start_status
+    return out

@@ -111,6 +111,24 @@ class RaceTrack:
         return np.stack([self.x_intp(s) - np.sin(yaw0).reshape(-1) * t, self.y_intp(s) + np.cos(yaw0).reshape(-1) * t,
                          phi.reshape(-1)], axis=-1).view(_DMLike)
 
+    def global_to_frenet(self, x, y, yaw=None, device=None):
+        """(x, y[, heading]) -> [P,3] = (abscissa, lateral offset, relative heading): the inverse of frenet_to_global, the
+        globally nearest foot on the closed centre line (ops.frenet_host, kernel k_frenet; xi = 0 without a heading).
+        ValueError naming the first point that cannot be projected (a non-finite coordinate, or a refinement that did not
+        converge: the point sits at the centre line's centre of curvature)."""
+        from .. import ops
+        pts = np.ascontiguousarray(np.stack([np.asarray(x, dtype=np.float64).reshape(-1),
+                                             np.asarray(y, dtype=np.float64).reshape(-1)], axis=-1)[None])
+        if yaw is not None:
+            yaw = np.ascontiguousarray(np.asarray(yaw, dtype=np.float64).reshape(1, -1))
+        fr, status, _ = ops.frenet_host(self.centerline_pieces(), pts, yaw, device=device)
+        bad = np.nonzero(status[0])[0]
+        if len(bad):
+            i = int(bad[0])
+            raise ValueError(f"global_to_frenet: point {i} ({pts[0, i, 0]!r}, {pts[0, i, 1]!r}) has status {int(status[0, i])} "
+                             "(1: non-finite coordinate, 2: no converged foot on the centre line)")
+        return fr[0, :, :3].copy()
+
     def fill_trajectory_boundaries(self, traj: Trajectory):
         """Fills the boundary properties of a trajectory in place (race_track.py:98-104)."""
         traj.fill_bounds(self.left_r, self.right_r, max_dist=100.0)

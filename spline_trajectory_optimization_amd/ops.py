@@ -614,6 +614,133 @@ def pose_tables_torch(track, form, X, pieces, bounds_form, bounds, base=None, T=
     return out
 
 
+FRENET_COLUMNS = ("s", "n", "xi", "g")   # rl_frenet_batch_*: out[B,P,4]
+FRENET_STATS_COLUMNS = ("bad_points", "min_g", "max_abs_n", "max_evaluations")   # stats[B,4]
+
+
+def _frenet_shapes(pieces, points, yaw):
+    """(B, P, stride, M) of a projection call; ValueError for a bad rank, stride or a missing piece -- before any library call."""
+    if pieces is None or len(pieces) != 3:
+        raise ValueError("pieces: (ss [M+1], cxs [4,M], cys [4,M]) of the centre line (RaceTrack.centerline_pieces)")
+    M = int(pieces[0].shape[0]) - 1
+    if M < 3:
+        raise ValueError("pieces: at least three pieces")
+    if getattr(points, "ndim", None) != 3 or points.shape[2] not in (2, _lib.NCOL):
+        raise ValueError("points: expected [B,P,2] or [B,P,19]")
+    B, P, stride = (int(v) for v in points.shape)
+    if B <= 0 or P < 1:
+        raise ValueError("points: needs at least one instance of one point")
+    if yaw is not None and stride == _lib.NCOL:
+        raise ValueError("yaw: a [B,P,19] table carries its heading in column 3 (YAW)")
+    return B, P, stride, M
+
+
+def frenet_host(pieces, points, yaw=None, device=None):
+    """Global -> Frenet for B lines of P points (rl_frenet_batch_host): for every point the globally nearest foot on the closed
+    centre line.  pieces = RaceTrack.centerline_pieces(); points [B,P,2] (yaw None or [B,P]) or tables [B,P,19] (heading = YAW
+    column); numpy float64, C-contiguous.  Returns (fr [B,P,4] in the order of FRENET_COLUMNS, status int32 [B,P],
+    stats [B,4] in the order of FRENET_STATS_COLUMNS)."""
+    B, P, stride, M = _frenet_shapes(pieces, points, yaw)
+    _check_np(points, "points", (B, P, stride))
+    _check_np(pieces[0], "pieces[0]", (M + 1,)); _check_np(pieces[1], "pieces[1]", (4, M)); _check_np(pieces[2], "pieces[2]", (4, M))
+    if yaw is not None:
+        _check_np(yaw, "yaw", (B, P))
+    ctx = Context.get(device)
+    fr = np.empty((B, P, 4)); status = np.empty((B, P), dtype=np.int32); stats = np.empty((B, 4))
+    p = lambda a: None if a is None else a.ctypes.data_as(_dp)  # noqa: E731
+    check(ctx.lib.rl_frenet_batch_host(ctx.h, p(points), B, P, stride, p(yaw), p(pieces[0]), p(pieces[1]), p(pieces[2]), M,
+                                       p(fr), status.ctypes.data_as(_ip), p(stats)))
+    return fr, status, stats
+
+
+def frenet_torch(pieces, points, yaw=None, out=None):
+    """frenet_host on DEVICE tensors (float64 cuda, contiguous, the pieces too, all on one device): enqueues on torch's current
+    stream, no sync (rl_frenet_batch_dev).  Returns (fr [B,P,4], status int32 [B,P], stats [B,4]) cuda tensors (`out` = such
+    a triple, if given)."""
+    import torch
+    B, P, stride, M = _frenet_shapes(pieces, points, yaw)
+    _check_torch(points, "points", (B, P, stride))
+    _check_torch(pieces[0], "pieces[0]", (M + 1,)); _check_torch(pieces[1], "pieces[1]", (4, M)); _check_torch(pieces[2], "pieces[2]", (4, M))
+    if yaw is not None:
+        _check_torch(yaw, "yaw", (B, P))
+    dev = points.device
+    if out is None:
+        out = (torch.empty((B, P, 4), dtype=torch.float64, device=dev), torch.empty((B, P), dtype=torch.int32, device=dev),
+               torch.empty((B, 4), dtype=torch.float64, device=dev))
+    _check_torch(out[0], "out[0]", (B, P, 4)); _check_torch(out[1], "out[1]", (B, P), torch.int32); _check_torch(out[2], "out[2]", (B, 4))
+    for name, t_ in (("yaw", yaw),) + tuple((f"pieces[{j}]", q) for j, q in enumerate(pieces)) + tuple((f"out[{j}]", q) for j, q in enumerate(out)):
+        if t_ is not None and t_.device != dev:
+            raise ValueError(f"{name}: on {t_.device}, points is on {dev}")
+    ctx = Context.get(dev.index)
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    p = lambda t_: None if t_ is None else ctypes.c_void_p(t_.data_ptr())  # noqa: E731
+    check(ctx.lib.rl_frenet_batch_dev(ctx.h, p(points), B, P, stride, p(yaw), p(pieces[0]), p(pieces[1]), p(pieces[2]), M,
+                                      p(out[0]), p(out[1]), p(out[2])))
+    return out
+
+
+def _resample_shapes(fr, vals, s_nodes, length):
+    """(B, P, C, Nn) of a resample call; ValueError for a bad rank or length -- before any library call."""
+    if getattr(fr, "ndim", None) != 3 or fr.shape[2] != 4:
+        raise ValueError("fr: expected [B,P,4] (ops.frenet_*)")
+    B, P = int(fr.shape[0]), int(fr.shape[1])
+    if B <= 0 or P < 1:
+        raise ValueError("fr: needs at least one instance of one point")
+    C = 0
+    if vals is not None:
+        if getattr(vals, "ndim", None) != 3:
+            raise ValueError(f"vals: expected [{B},{P},C]")
+        C = int(vals.shape[2])
+        if C < 1:
+            raise ValueError("vals: at least one channel, or None")
+    if getattr(s_nodes, "ndim", None) != 1 or int(s_nodes.shape[0]) < 1:
+        raise ValueError("s_nodes: expected [Nn]")
+    if not float(length) > 0.0:
+        raise ValueError("length: the track length must be positive")
+    return B, P, C, int(s_nodes.shape[0])
+
+
+def frenet_resample_host(fr, vals, s_nodes, length, device=None):
+    """A projected line at node abscissae (rl_frenet_resample_host): fr [B,P,4] of frenet_host, vals None or [B,P,C] channels,
+    s_nodes [Nn] shared by the batch, length = the track length; numpy float64, C-contiguous.  Returns (out [B,Nn,2+C] =
+    (n, xi, channels), status int32 [B]: 1 = the line's s is not cyclically strictly increasing or a point is bad; zero rows)."""
+    B, P, C, Nn = _resample_shapes(fr, vals, s_nodes, length)
+    _check_np(fr, "fr", (B, P, 4))
+    if C:
+        _check_np(vals, "vals", (B, P, C))
+    _check_np(s_nodes, "s_nodes", (Nn,))
+    ctx = Context.get(device)
+    out = np.empty((B, Nn, 2 + C)); status = np.empty((B,), dtype=np.int32)
+    p = lambda a: None if a is None else a.ctypes.data_as(_dp)  # noqa: E731
+    check(ctx.lib.rl_frenet_resample_host(ctx.h, p(fr), p(vals) if C else None, C, B, P, p(s_nodes), Nn, float(length), p(out),
+                                          status.ctypes.data_as(_ip)))
+    return out, status
+
+
+def frenet_resample_torch(fr, vals, s_nodes, length, out=None):
+    """frenet_resample_host on DEVICE tensors (float64 cuda, contiguous, one device): torch's current stream, no sync
+    (rl_frenet_resample_dev).  Returns (out [B,Nn,2+C], status int32 [B]) cuda tensors."""
+    import torch
+    B, P, C, Nn = _resample_shapes(fr, vals, s_nodes, length)
+    _check_torch(fr, "fr", (B, P, 4))
+    if C:
+        _check_torch(vals, "vals", (B, P, C))
+    _check_torch(s_nodes, "s_nodes", (Nn,))
+    dev = fr.device
+    if out is None:
+        out = (torch.empty((B, Nn, 2 + C), dtype=torch.float64, device=dev), torch.empty((B,), dtype=torch.int32, device=dev))
+    _check_torch(out[0], "out[0]", (B, Nn, 2 + C)); _check_torch(out[1], "out[1]", (B,), torch.int32)
+    for name, t_ in (("vals", vals), ("s_nodes", s_nodes), ("out[0]", out[0]), ("out[1]", out[1])):
+        if t_ is not None and t_.device != dev:
+            raise ValueError(f"{name}: on {t_.device}, fr is on {dev}")
+    ctx = Context.get(dev.index)
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    p = lambda t_: None if t_ is None else ctypes.c_void_p(t_.data_ptr())  # noqa: E731
+    check(ctx.lib.rl_frenet_resample_dev(ctx.h, p(fr), p(vals) if C else None, C, B, P, p(s_nodes), Nn, float(length), p(out[0]),
+                                         p(out[1])))
+    return out
+
+
 def table_summary(points, iters=None, device=None):
     """Per-instance summary of simulated tables [B,N,19] (numpy): [B,8] in the order of SUMMARY_COLUMNS -- lap time (TIME
     added up in index order) and the scalars of the reference's SimulationResult (simulator.py:375-386).  iters [B] int32

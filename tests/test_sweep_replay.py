@@ -61,6 +61,16 @@ def rl():
     _lib.Context.get(0).set_arith(_lib.ARITH_DEFAULT)
 
 
+def noisy_verdict(rep):
+    """[S] bool from the oracle's re-derivations rep [S, REPLAY_STRIDE]: the steps whose verdict the decision rule below excuses
+    -- the oracle's own margin (hi - lo of a coordinate's clamp interval, or the slack of a b == 0 row) is inside its noise radius."""
+    lohi_o, rad_o, zslack = rep[:, 5:9], rep[:, 11:15], rep[:, 15]
+    eps = 8.0 * 2.220446049250313e-16 * 2048.0
+    width_o = np.stack([lohi_o[:, 1] - lohi_o[:, 0], lohi_o[:, 3] - lohi_o[:, 2]], axis=1)
+    width_noise = np.stack([rad_o[:, 0] + rad_o[:, 1], rad_o[:, 2] + rad_o[:, 3]], axis=1)
+    return (np.abs(width_o) <= 4.0 * width_noise).any(axis=1) | (np.abs(zslack) <= 4.0 * eps)
+
+
 def check_steps(rec, rep, n, label):
     """rec [S, HEAD+2n] kernel records, rep [S, REPLAY_STRIDE] oracle re-derivations."""
     S = len(rec)
@@ -69,8 +79,7 @@ def check_steps(rec, rep, n, label):
     ok_g = rec[:, 10] == 1.0
     z_g = rec[:, 11:13]
     st_o = rep[:, 0].astype(int)
-    H_o, g_o, lohi_o, x_o, rad_o, zslack = rep[:, 1:3], rep[:, 3:5], rep[:, 5:9], rep[:, 9:11], rep[:, 11:15], rep[:, 15]
-    eps = 8.0 * 2.220446049250313e-16 * 2048.0
+    H_o, g_o, lohi_o, x_o, rad_o = rep[:, 1:3], rep[:, 3:5], rep[:, 5:9], rep[:, 9:11], rep[:, 11:15]
     # ---- an empty support (no samples in it: sparse samplings): no terms and no rows -- H = g = 0 exactly on both sides, a
     # failed step (DESIGN.md "Empty supports"); the relative measures below are taken over the other steps
     empty = rep[:, 16] == 0
@@ -94,12 +103,10 @@ def check_steps(rec, rep, n, label):
     assert (dlohi <= tol).all(), (label, "clamp interval outside the row's noise radius", worst)
     # ---- decision
     ok_o = st_o == 0
-    width_o = np.stack([lohi_o[:, 1] - lohi_o[:, 0], lohi_o[:, 3] - lohi_o[:, 2]], axis=1)
-    width_noise = np.stack([rad_o[:, 0] + rad_o[:, 1], rad_o[:, 2] + rad_o[:, 3]], axis=1)
-    noisy_verdict = (np.abs(width_o) <= 4.0 * width_noise).any(axis=1) | (np.abs(zslack) <= 4.0 * eps)
+    noisy = noisy_verdict(rep)
     differ = ok_g != ok_o
-    assert not (differ & ~noisy_verdict).any(), (label, "verdict differs outside the noise bound",
-                                                  np.where(differ & ~noisy_verdict)[0][:10].tolist())
+    assert not (differ & ~noisy).any(), (label, "verdict differs outside the noise bound",
+                                         np.where(differ & ~noisy)[0][:10].tolist())
     # ---- clamp: the kernel's own numbers, bit for bit (IEEE division, then max, then min)
     with np.errstate(all="ignore"):
         zx = np.minimum(np.maximum(-g_g[:, 0] / H_g[:, 0], lohi_g[:, 0]), lohi_g[:, 1])
@@ -127,7 +134,11 @@ def check_steps(rec, rep, n, label):
         assert np.array_equal(ex, cx[s + 1]) and np.array_equal(ey, cy[s + 1]), (label, "state chain broken at step", s)
     return {"steps": S, "accepted": int(ok_g.sum()), "verdict_differs_in_noise": int(differ.sum()),
             "max_rel_H": float(relH.max(initial=0.0)), "max_rel_g": float(relg.max(initial=0.0)), "max_interval_over_tol": float(worst),
-            "noisy_verdict_steps": int(noisy_verdict.sum()), "empty_support_steps": int(empty.sum())}
+            "noisy_verdict_steps": int(noisy.sum()), "empty_support_steps": int(empty.sum())}
+
+
+MGKT_WIDTH_SEED = 1234   # tests/test_kart_track_cpu.py::test_replay_noise_share_of_the_oracle_trajectory checks the choice on the CPU
+NOISE_SHARE_MAX = 0.05   # of an MGKT batch's steps may be excused by the noise-radius rule (noisy_verdict)
 
 
 def _monza_widths(rl, fits, rings, N, B, seed):
@@ -139,15 +150,25 @@ def _monza_widths(rl, fits, rings, N, B, seed):
     return rl.batch.width_batch(wl, wr, B, seed=seed)
 
 
-@pytest.mark.parametrize("N,B,max_iter,n_inst", [(400, 8, 2, 4), (58, 8, 2, 8), (2000, 1024, 5, 1024)])
-def test_sweep_steps_teacher_forced(rl, fits, rings, N, B, max_iter, n_inst):
+@pytest.mark.parametrize("track,N,B,max_iter,n_inst", [("monza", 400, 8, 2, 4), ("monza", 58, 8, 2, 8), ("monza", 2000, 1024, 5, 1024),
+                                                       ("mgkt", 200, 8, 2, 4)],
+                         ids=["400-8-2-4", "58-8-2-8", "2000-1024-5-1024", "mgkt-200-8-2-4"])
+def test_sweep_steps_teacher_forced(rl, fits, rings, track, N, B, max_iter, n_inst):
     """(2000, 1024, 5): the benchmarked configuration itself (Monza widths, B=1024, max_iter=5, the
     global-residency kernel variant bench.py runs): EVERY step of EVERY instance of the batch (1024 x 610 steps).
     (58, 8, 2): a sparse sampling -- control point 7 has no support sample (tests/sparse_cases.py), so every pass takes one
-    step with M = 0.  The oracle replays run eight at a time (ctypes releases the GIL)."""
-    t, cx, cy, k, length = spline(fits, "c100")
+    step with M = 0.  The oracle replays run eight at a time (ctypes releases the GIL).
+    mgkt: the kart circuit (tests/kart_cases.py, `base`): hairpins, a ring search that loses its certificate on one sample in
+    eight, failing steps, lines on the boundary -- where rows sit near the noise radius far more often than on Monza, so the
+    share of steps the noise-radius rule excuses is printed and held to NOISE_SHARE_MAX."""
+    if track == "mgkt":
+        import kart_cases as kc
+        t, cx, cy, k, length = kc.case("base")[:5]
+        widths = kc.widths("base", N, B, MGKT_WIDTH_SEED)
+    else:
+        t, cx, cy, k, length = spline(fits, "c100")
+        widths = _monza_widths(rl, fits, rings, N, B, seed=1234)
     n = len(cx)
-    widths = _monza_widths(rl, fits, rings, N, B, seed=1234)
     i_start = rl.batch.default_i_start(n, k, max_iter, seed=0)
     trk = rl.lib.Track(rl.lib.Context.get(0), t, cx, cy, k, N)
     # the product instantiation first: the recording one must reproduce it bit for bit
@@ -186,6 +207,10 @@ def test_sweep_steps_teacher_forced(rl, fits, rings, N, B, max_iter, n_inst):
     worst = {key: max(i[key] for i in infos) for key in ("max_rel_H", "max_rel_g", "max_interval_over_tol")}
     print(f"[replay N={N} B={B} it={max_iter}] ALL {n_inst} instances: {tot} {worst}")
     assert tot["steps"] == n_inst * steps
+    share = tot["noisy_verdict_steps"] / tot["steps"]
+    print(f"[replay N={N} B={B} it={max_iter}] share of steps excused by the noise-radius rule: {share:.4f}")
+    if track == "mgkt":
+        assert share <= NOISE_SHARE_MAX and tot["accepted"] < tot["steps"]
     from sparse_cases import empty_points
     n_empty = len(empty_points(t, k, n, N))
     assert tot["empty_support_steps"] == n_inst * 2 * max_iter * n_empty and (N != 58 or n_empty > 0)

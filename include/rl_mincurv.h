@@ -47,6 +47,8 @@ typedef struct rl_track rl_track;   /* device-resident tables of one (spline kno
 
 /* per-instance QP/sweep outcome, mirrors "raise -> skip" at optimizer.py:291-293 */
 enum { RL_OK = 0, RL_ERR_ARG = -1, RL_ERR_HIP = -2, RL_ERR_NOMEM = -3, RL_ERR_UNSUPPORTED = -4 };
+/* iters of rl_qss_sim[_dev] with the test hook "qss_df_redo" = 0: RL_QSS_HANDED_BACK - reason (rl_ctx_set_option) */
+enum { RL_QSS_HANDED_BACK = -100 };
 
 /* how the per-instance track boundaries are given to rl_mincurv_solve_batch_dev */
 enum {
@@ -123,6 +125,13 @@ int rl_ctx_set_numpy_raise(rl_ctx* ctx, int on);
  *   "qss_df_waves"    1 | 2 | 4 waves per instance of the dataflow kernel (default 4)
  *   "qss_df_bail_at"  g > 0: the dataflow kernel hands every instance back to the list-order kernel at iteration g (the path
  *                     taken when its tables overflow); 0 = never
+ *   "qss_df_redo"     1 = the list-order kernel runs behind the dataflow kernel and recomputes what that one handed back (default);
+ *                     0 = it does not: a handed-back instance returns iters = RL_QSS_HANDED_BACK - reason and its rows of
+ *                     `points` keep the bits they came in with.  reason: 2 an agent beyond iteration N - 1, 3 more unnumbered
+ *                     fronts than the scratch holds, 4 no free exit record, 5 front ids beyond the table, 7 "qss_df_bail_at"
+ *                     (capacities and the hook); 6 an empty queue with live agents, 8 the window-counter guard, 9 more than
+ *                     3 N + 64 passes per iteration (the scheduler is broken: no input may produce these).  This option alone changes what a
+ *                     call returns, and only for handed-back instances; it exists so that tests can see them.
  *   "tables_search"   RL_SEARCH_BRUTE | _CULLED | _WINDOWED (default): ring search of rl_tables_batch_* and rl_pose_tables_batch_*
  *   "tables_rings"    0 = rl_tables_batch_* and rl_pose_tables_batch_* keep an instance's ring vertices in LDS where they fit
  *                     (default), 1 = in the arena

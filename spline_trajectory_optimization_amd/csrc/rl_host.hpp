@@ -67,8 +67,9 @@ struct rl_ctx {
   int np_raise_at_start = 0;     // rl_ctx_set_numpy_raise: the reference-order sweep starts with np.seterr(all='raise') in effect
   // test hooks of the QSS simulator (rl_ctx_set_option; defaults from RL_QSS_DF / RL_QSS_V1 / RL_QSS_DF_WAVES / RL_QSS_DF_BAIL_AT, read
   // once in rl_ctx_create): which kernel (-1 = by the rounds the batch takes, 0 = list order, 1 = dataflow), waves per instance of
-  // the dataflow kernel, the iteration at which it hands every instance back (0 = never)
-  int qss_kernel = -1, qss_df_waves = 4, qss_df_bail_at = 0;
+  // the dataflow kernel, the iteration at which it hands every instance back (0 = never), whether the list-order kernel re-runs
+  // what it handed back (1; 0 = no: such an instance returns iters = RL_QSS_HANDED_BACK - reason and keeps its input rows)
+  int qss_kernel = -1, qss_df_waves = 4, qss_df_bail_at = 0, qss_df_redo = 1;
   // test hooks of rl_tables_batch_*: ring search (RL_SEARCH_*), 1 = ring vertices in the arena even where they fit LDS
   int tables_search = RL_SEARCH_WINDOWED, tables_rings_global = 0;
   int frenet_search = 1;         // test hook of rl_frenet_batch_*: 0 = every point from the table's own bound, 1 = from the previous point's piece

@@ -584,6 +584,7 @@ struct QssArgs {
   // The lookup tables BY VALUE (acc_x [m+1], acc_c [4m], dcc_x [m'+1], dcc_c [4m'] back to back) when they fit: the
   // launch then reads no host memory after the call returns.  tab_n = 0: the four pointers above are device arrays.
   int tab_n;
+  int df_report;         // k_qss_dfw only, tests: 1 = a handed-back instance reports iters = -100 - reason instead of -2 (no k_qss_sim behind)
   int* dbg;              // optional [B][12]: passes, chunks, examinations, steps, wake pushes, numbering events, spawned fronts, bail reason
   int df_bail_at;        // k_qss_dfw only, tests: hand the instance back once a step of this iteration has run (0: never)
   int redo;              // k_qss_sim only: 1 = run just the instances k_qss_dfw handed back (iters[b] == -2)

@@ -375,6 +375,7 @@ int rl_ctx_set_option(rl_ctx* ctx, const char* name, int value) {
   if (k == "qss_kernel") { if (value < -1 || value > 1) return fail(RL_ERR_ARG, "qss_kernel: -1 (auto), 0 (list order), 1 (dataflow)"); ctx->qss_kernel = value; }
   else if (k == "qss_df_waves") { if (value != 1 && value != 2 && value != 4) return fail(RL_ERR_ARG, "qss_df_waves: 1, 2 or 4"); ctx->qss_df_waves = value; }
   else if (k == "qss_df_bail_at") { if (value < 0) return fail(RL_ERR_ARG, "qss_df_bail_at >= 0"); ctx->qss_df_bail_at = value; }
+  else if (k == "qss_df_redo") { if (value != 0 && value != 1) return fail(RL_ERR_ARG, "qss_df_redo: 0 or 1"); ctx->qss_df_redo = value; }
   else if (k == "tables_search") { if (value < RL_SEARCH_BRUTE || value > RL_SEARCH_WINDOWED) return fail(RL_ERR_ARG, "tables_search: RL_SEARCH_BRUTE, _CULLED or _WINDOWED"); ctx->tables_search = value; }
   else if (k == "tables_rings") { if (value != 0 && value != 1) return fail(RL_ERR_ARG, "tables_rings: 0 (LDS where they fit) or 1 (arena)"); ctx->tables_rings_global = value; }
   else if (k == "frenet_search") { if (value != 0 && value != 1) return fail(RL_ERR_ARG, "frenet_search: 0 (table bound for every point) or 1 (from the previous point's piece)"); ctx->frenet_search = value; }
@@ -1175,7 +1176,7 @@ int rl_qss_sim_dev(rl_ctx* ctx, double* points, int B, int N, const double* acc_
   a.max_lon_acc = params[0]; a.max_lon_dcc = params[1]; a.max_left_acc = params[2];
   a.max_right_acc = params[3]; a.max_speed = params[4]; a.max_jerk = params[5];
   a.flags = dfl; a.fresh = dnw; a.cst = dcst; a.cap = cap; a.iters = iters;
-  a.tab_n = 0; a.redo = 0; a.dbg = nullptr; a.df_bail_at = ctx->qss_df_bail_at;
+  a.tab_n = 0; a.redo = 0; a.dbg = nullptr; a.df_bail_at = ctx->qss_df_bail_at; a.df_report = ctx->qss_df_redo ? 0 : 1;
   if (by_value) {
     double* q = a.tab;
     for (int i = 0; i <= acc_m; ++i) *q++ = acc_x[i];
@@ -1229,7 +1230,8 @@ int rl_qss_sim_dev(rl_ctx* ctx, double* points, int B, int N, const double* acc_
     }
     a.redo = 1;
   }
-  RL_TRY(launch(ctx, rl::k_qss_sim, dim3(B), dim3(64), lds, a));
+  // (test hook "qss_df_redo" = 0: what the dataflow kernel handed back stays handed back, iters = RL_QSS_HANDED_BACK - reason)
+  if (!use_df || ctx->qss_df_redo) RL_TRY(launch(ctx, rl::k_qss_sim, dim3(B), dim3(64), lds, a));
   RL_HIP(ar.end());
   return RL_OK;
 }

@@ -27,7 +27,7 @@
 //     under the dataflow rules a front would have to wait for the front before it even where that one turns out to stop
 //     without writing -- one chain through all N fronts, which delays every later iteration too.
 //   * the one rule that concerns fronts NOT YET BORN (an enter agent that lags far behind could still spawn a front whose exit
-//     side would have had to run before mine) never fires on real profiles but would cost a scan of up to 45 worldlines per
+//     side would have had to run before mine) fires a few times per lap at most (tests/test_qss_cpu.py) but would cost a scan of up to 45 worldlines per
 //     examination; it is answered from lower bounds of 2 g - w per block of four enter worldlines, which only grow (so need no
 //     ordering among the lanes that refresh them) and cannot raise a false alarm by what lies beyond the range asked about.
 //
@@ -43,7 +43,10 @@
 //
 // Everything a step or a test touches lives in LDS (156 KB at N = 2000; N <= 2110: one workgroup = one instance per CU, four waves).
 // Instances whose size or front count exceeds the tables report iters = -2 and are re-run by k_qss_sim (launched right behind,
-// a no-op for every other instance).
+// a no-op for every other instance).  The reason stays on the device unless the test hook "qss_df_redo" = 0 asks for it
+// (QssArgs::df_report): then no k_qss_sim follows and the instance returns iters = -100 - reason, its rows of `points` untouched.
+// Reasons: 2 an agent beyond iteration N - 1, 3 unnumbered fronts, 4 exit records, 5 front ids (capacities); 7 the hook
+// df_bail_at; 6 empty queue with live agents, 8 window-counter guard, 9 more than 3 N + 64 passes per iteration (a broken scheduler).
 #pragma once
 #include "rl_kernels.hpp"
 
@@ -867,7 +870,11 @@ __global__ __launch_bounds__(64 * W) void k_qss_dfw(QssArgs a) {
     { const int q2 = scal[DFS_Q2NE]; qne = q2 - q2be; q2be = q2; }
     { u16* t = Q; Q = Q2; Q2 = t; }
     if (qnx + qne == 0 && scal[DFS_NE] + scal[DFS_NX] > 0) bail = 6;
-    if (d_pass > 64 * N) bail = 9;
+    // Every pass runs at least the logically earliest pending step, which is one of iteration gmin; no agent is born into gmin and
+    // at most N enter + HX exit agents are alive, so gmin moves on after at most N + HX passes.  (Not "64 N passes": a train that
+    // closes on itself -- a constant-radius circle -- is one chain through all N samples, N + 4 passes per iteration, and runs into
+    // the iteration limit, reason 2, only after N iterations.)
+    if (d_pass > (N + HX) * ((gmin < N ? gmin : N) + 1)) bail = 9;
     DFW_TICK(7);
   }
   // the last iteration any step ran in = the reference's iteration counter
@@ -880,7 +887,7 @@ __global__ __launch_bounds__(64 * W) void k_qss_dfw(QssArgs a) {
     d[0] = d_pass; d[1] = d_chunk; d[2] = scal[DFS_DEXAM]; d[3] = scal[DFS_DSTEP]; d[4] = d_qmax; d[5] = d_num; d[6] = scal[DFS_NU]; d[7] = bail;
     d[8] = (int)((tp[0] + tp[1]) >> 10); d[9] = (int)((tp[2] + tp[3]) >> 10); d[10] = (int)((tp[4] + tp[5] + tp[6]) >> 10); d[11] = (int)(tp[7] >> 10);
   }
-  if (bail && !err) { if (tid == 0) a.iters[b] = -2; return; }
+  if (bail && !err) { if (tid == 0) a.iters[b] = a.df_report ? -100 - bail : -2; return; }
   if (tid == 0) a.iters[b] = err ? -1 : maxg;
   for (int i = tid; i < N; i += TT) {
     double* p = P + (size_t)i * 19;

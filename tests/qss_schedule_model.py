@@ -150,21 +150,26 @@ def run(lg, N, R, start=1):
     unnumbered = []
     passes = exams = steps = maxg = 0
     INF = 1 << 40
+    rules = collections.Counter()        # which rule decided an examination (RULES below)
+
+    def hit(rule, key):
+        rules[rule] += 1
+        return key
 
     def blocked_by(a):
         """None when the agent may step, else the list it sleeps on."""
         g, idv = a.g, a.id
         if g > gmin + R:
-            return "WIN"
+            return hit("window", "WIN")
         assert idv != UNN       # fronts without a number are not queued
         if a.d == 1:
             c, p = a.w, a.w + g
             for h in X[c]:                                   # same worldline: (g, id) order
                 if h is not a and (h.g, h.id) < (g, idv):
-                    return ("X", c)
+                    return hit("exit: not the next of its worldline", ("X", c))
             for F in X[(c - 1) % N]:                         # the follower of this iteration writes my source
                 if F.id < idv and F.g <= g:
-                    return ("X", (c - 1) % N)
+                    return hit("exit: follower writes my source", ("X", (c - 1) % N))
             k = 1                                            # agents ahead that lag behind in iterations (nearest occupied worldline)
             while k <= R + 2:
                 lst = X[(c + k) % N]
@@ -175,7 +180,7 @@ def run(lg, N, R, start=1):
                             if k == 1 and Lh.g == g and Lh.id > idv:
                                 exc = True
                             else:
-                                return ("X", (c + k) % N)
+                                return hit("exit: exit agent ahead lags", ("X", (c + k) % N))
                     if not exc:
                         break
                 k += 1
@@ -184,7 +189,7 @@ def run(lg, N, R, start=1):
                 if e is not None:
                     pe = wu - e.g
                     if pe >= p + 2 or (pe == p + 1 and e.g <= g):
-                        return ("E", wu % N)
+                        return hit("exit: enter agent coming towards me", ("E", wu % N))
                     if pe <= p:
                         break
             if g - 2 >= gmin_e:                                        # fronts that enter agents behind me may still spawn
@@ -193,19 +198,19 @@ def run(lg, N, R, start=1):
                     if e is not None:
                         pe = wu - e.g
                         if pe <= p and e.g + 1 + (p - pe) < g:
-                            return ("E", wu % N)
-            return None
+                            return hit("exit: front not yet born", ("E", wu % N))
+            return hit("ready", None)
         c, p = a.w, a.w - g
         B = E[(c + 1) % N]
         if B is not None and B.id < idv and B.g <= g:                  # the agent one sample ahead writes my source
-            return ("E", (c + 1) % N)
+            return hit("enter: agent ahead writes my source", ("E", (c + 1) % N))
         k = 1
         while k <= R + 2:                                              # agents behind that lag behind in iterations
             h = E[(c - k) % N]
             if h is not None:
                 if h.g <= g - k + 1:
                     if not (k == 1 and h.g == g and h.id > idv):
-                        return ("E", (c - k) % N)
+                        return hit("enter: enter agent behind lags", ("E", (c - k) % N))
                 else:
                     break
             k += 1
@@ -216,7 +221,7 @@ def run(lg, N, R, start=1):
                 for x in lst:
                     px = cu + x.g
                     if px <= p - 2 or (px == p - 1 and x.g < g):
-                        return ("X", cu % N)
+                        return hit("enter: exit agent coming towards me", ("X", cu % N))
                     if px <= p - 1:
                         passed = False
                 if passed:
@@ -227,8 +232,8 @@ def run(lg, N, R, start=1):
                 if e is not None and e is not a:
                     pe = wu - e.g
                     if pe <= p - 1 and e.g + (p - pe) < g:
-                        return ("E", wu % N)
-        return None
+                        return hit("enter: front not yet born", ("E", wu % N))
+        return hit("ready", None)
 
     while Q:
         passes += 1
@@ -294,7 +299,23 @@ def run(lg, N, R, start=1):
                 next_id += 1
         Q = [a for a in Q2 if a.alive]
     assert (done >= 0).all(), "steps never released"
-    return dict(passes=passes, steps=steps, examinations=exams, iterations=maxg)
+    return dict(passes=passes, steps=steps, examinations=exams, iterations=maxg, rules={r: rules[r] for r in RULES})
+
+
+# what an examination can end on, in the order the rules are tried ("front not yet born" is the rule of which csrc/rl_qss_df.hpp
+# says that it never fires on real profiles)
+RULES = ("ready", "window", "exit: not the next of its worldline", "exit: follower writes my source", "exit: exit agent ahead lags",
+         "exit: enter agent coming towards me", "exit: front not yet born", "enter: agent ahead writes my source",
+         "enter: enter agent behind lags", "enter: exit agent coming towards me", "enter: front not yet born")
+UNBORN = ("exit: front not yet born", "enter: front not yet born")
+
+
+def rule_table(rows):
+    """rows: (label, rules dict) -> the table as text, one line per input, one column per rule."""
+    head = "input".ljust(34) + "".join(f"{i:>8d}" for i in range(len(RULES)))
+    legend = "\n".join(f"  {i}: {r}" for i, r in enumerate(RULES))
+    body = "\n".join(lab.ljust(34) + "".join(f"{rl[r]:>8d}" for r in RULES) for lab, rl in rows)
+    return "examinations decided by each rule\n" + legend + "\n" + head + "\n" + body
 
 
 # ------------------------------------------------------------------------------------------------ random trajectories

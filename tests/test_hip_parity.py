@@ -617,16 +617,28 @@ def test_drop_in_api(rl, fits, rings):
 
 
 @contextlib.contextmanager
-def qss_options(rl, qss_kernel=-1, qss_df_waves=4, qss_df_bail_at=0):
+def qss_options(rl, qss_kernel=-1, qss_df_waves=4, qss_df_bail_at=0, qss_df_redo=1):
     """The simulator's test hooks for the calls inside (rl_ctx_set_option), the defaults again afterwards."""
     ctx = rl.lib.Context.get(0)
     try:
-        for k_, v_ in (("qss_kernel", qss_kernel), ("qss_df_waves", qss_df_waves), ("qss_df_bail_at", qss_df_bail_at)):
+        for k_, v_ in (("qss_kernel", qss_kernel), ("qss_df_waves", qss_df_waves), ("qss_df_bail_at", qss_df_bail_at),
+                       ("qss_df_redo", qss_df_redo)):
             ctx.set_option(k_, v_)
         yield ctx
     finally:
-        for k_, v_ in (("qss_kernel", -1), ("qss_df_waves", 4), ("qss_df_bail_at", 0)):
+        for k_, v_ in (("qss_kernel", -1), ("qss_df_waves", 4), ("qss_df_bail_at", 0), ("qss_df_redo", 1)):
             ctx.set_option(k_, v_)
+
+
+def dataflow_alone(rl, pts, veh, label):
+    """One forced call of the dataflow kernel with NOTHING behind it ("qss_df_redo" = 0): the list-order kernel that
+    rl_qss_sim_dev launches behind it would recompute -- and so hide -- every instance the scheduler gave back.  No instance may
+    come back; the reason code is in the message (tests/qss_cases.py)."""
+    from qss_cases import assert_not_handed_back
+    with qss_options(rl, qss_kernel=1, qss_df_redo=0):
+        out, it = rl.ops.qss_sim(pts, *veh)
+    assert_not_handed_back(it, label)
+    return out, it
 
 
 def _sim_inputs():
@@ -647,6 +659,8 @@ def test_qss_simulator_golden(rl):
     out, it = rl.ops.qss_sim(pts, *veh)
     ref, oit = orc.qss_sim(pts, *veh)
     assert it[0] == oit > 10
+    alone, ita = dataflow_alone(rl, pts, veh, "G6")
+    np.testing.assert_array_equal(alone, out); assert ita[0] == oit
     np.testing.assert_array_equal(out[:, 18], g["iter_flag"])          # which turn owns each point
     np.testing.assert_allclose(out[:, 4], g["speed"], rtol=0, atol=1e-12)
     np.testing.assert_allclose(out[:, 14], g["lon_acc"], rtol=0, atol=1e-11)
@@ -676,6 +690,8 @@ def test_qss_simulator_batch_and_bank(rl, fits):
         batch.append(p)
     batch = np.stack(batch)
     out, it = rl.ops.qss_sim(batch, *veh)
+    alone, ita = dataflow_alone(rl, batch, veh, "batch of 6, N = 800")
+    np.testing.assert_array_equal(alone, out); np.testing.assert_array_equal(ita, it)
     for b in range(len(batch)):
         ref, oit = orc.qss_sim(batch[b], *veh)
         assert it[b] == oit
@@ -712,6 +728,9 @@ def test_qss_sizes_around_the_dataflow_tables(rl, fits, monkeypatch):
             assert int(np.atleast_1d(it)[0]) == oit > 5, N
             np.testing.assert_array_equal(out[:, 18], ref[:, 18])
             np.testing.assert_allclose(out[:, [4, 14, 15, 16]], ref[:, [4, 14, 15, 16]], rtol=0, atol=1e-10)
+            if N in (256, 2048, 2110):      # the sizes the dataflow kernel takes
+                alone, ita = dataflow_alone(rl, p, veh, f"Monza N = {N}")
+                np.testing.assert_array_equal(alone, out); assert int(np.atleast_1d(ita)[0]) == oit
 
 
 @pytest.mark.parametrize("kernel", ["dataflow, one wave", "dataflow, four waves", "list-order"])  # k_qss_dfw<1>, <4>; k_qss_sim

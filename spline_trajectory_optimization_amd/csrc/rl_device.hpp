@@ -5,7 +5,7 @@
 // table reads (sample index = lane index).  No CUDA idioms, no compatibility layer.
 #pragma once
 #include <hip/hip_runtime.h>
-
+#include "rl_sep.hpp"   // chunk_separation: the separation pass of the windowed search, shared with the host check
 
 namespace rl {
 

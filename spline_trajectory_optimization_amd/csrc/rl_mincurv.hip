@@ -137,8 +137,10 @@ SweepPlan plan_sweep(const rl_ctx* ctx, int n, int N, int nL, int nR, int B, boo
   p.residency = want == 1 ? Residency::Lds : want == 2 ? Residency::CrossingsLds : Residency::Global;
   rl::SweepLds L = rl::sweep_lds_layout(n, N, nL, nR, p.residency, joint, strict);
   p.lds_bytes = L.total * sizeof(double);
-  // crossings (fast mode: one double per sample and side) or bound points (reference-order mode: two)
-  p.gscratch_doubles = (p.residency != Residency::Global ? 0 : (size_t)2 * ((N + 1) & ~1) * (strict ? 2 : 1)) +
+  // crossings (fast mode: one double per sample and side) or bound points (reference-order mode: two), and behind them the
+  // table's X, Y where the sweep keeps them (rl_sweep.hpp: sweep_keeps_table_xy)
+  const size_t per_sample_arrays = rl::sweep_keeps_table_xy(joint, strict) ? 3 : 2;
+  p.gscratch_doubles = (p.residency != Residency::Global ? 0 : per_sample_arrays * ((N + 1) & ~1) * (strict ? 2 : 1)) +
                        (p.residency == Residency::Lds ? 0 : (size_t)2 * (nL + rl::kRingPad) + (size_t)2 * (nR + rl::kRingPad));
   return p;
 }
@@ -651,7 +653,7 @@ static int solve_batch_common(rl_ctx* ctx, const rl_track* trk, int form, const 
     size_t need = joint ? (size_t)max_iter * (size_t)(i_max - i_min) * (48 + 9 * rl::kJointRowsPerThread * 256 + 2 * n)
                         : (size_t)ninst * max_iter * 2 * (size_t)(i_max - i_min) * (rl::kSweepDumpHead + 2 * n);
 #ifdef RL_STAMPS
-    need = std::max(need, (size_t)B * 4 * 16);   // diagnostic build: per-wave phase stamps of every instance
+    need = std::max(need, (size_t)B * 4 * 17);   // diagnostic build: per-wave phase stamps of every instance, [B][4][16], and behind them [B][4] prologue cycles
 #endif
     a.dbg_instances = ninst;
     if (g_dbg_len < need) {

@@ -76,8 +76,13 @@ enum class Residency { Lds, Global, CrossingsLds };
 struct SweepLds {
   int cpad, nLp, nRp, ncL, ncR;
   size_t off_cx, off_cy, off_red, off_sL, off_sR, off_rL, off_rR, off_cL, off_cR, off_pL, off_pR, off_hint, off_joint, off_stage,
-         off_c12, off_terms, total;
+         off_c12, off_terms, off_pxy, total;
 };
+// The reference-order and branch sweeps (not the sliding window) keep the table's X, Y per sample next to its bound points, in
+// the same residency: the rows of a step read them instead of summing them again (the reference reads its table too,
+// optimizer.py:235-248).  The table is never stale there: every control point a step writes has its support and its
+// alias's support re-sampled in that step.
+__host__ __device__ constexpr bool sweep_keeps_table_xy(bool joint, bool strict) { return strict && !joint; }
 constexpr int kSweepWaves = 4;   // waves of the sweep workgroup (the staged stretches are per wave)
 constexpr int kSweepThreads = kWave * kSweepWaves;
 // reference-order mode: the six cost terms of up to kTermChunk samples wait in LDS for their sequential summation
@@ -87,6 +92,7 @@ constexpr int kTermChunk = 256;
 constexpr int kTermStride = kTermChunk + 2;   // 6 lanes read 6 rows at the same index: 2064 B apart = 4 banks apart, no conflict (stride 256: six-fold)
 constexpr int kC12Doubles = 4 * (2 * kMaxK) + 8;
 constexpr int kRedCoordMax = 194;   // slot of the reduction scratch (8 x 24 + 4 doubles) that keeps the rings' coordinate bound
+constexpr int kRedRadiusMax = 192;  // prologue only: a bound on the radii of the chunk circles (the separation pass prunes by it)
 
 // joint: the sliding-window instantiation (its QP scratch and per-sample flags are carved only then).  With the rings in
 // global memory every wave gets two staged stretches (left / right ring, rl_device.hpp: kStage vertices each): at N = 2000
@@ -113,11 +119,12 @@ __host__ __device__ inline SweepLds sweep_lds_layout(int n, int N, int nL, int n
   L.off_joint = o; o += joint ? 128 + (size_t)((N + 15) / 16) * 2 : 0;  // joint variant: QP scratch + 1 byte per sample
   L.off_hint = o; o += (size_t)(((size_t)2 * ((N + 3) & ~3) * sizeof(unsigned short) + 15) / 16) * 2;  // u16 [2][Npad]
   L.off_c12 = o; o += strict ? (joint ? (size_t)4 * L.cpad : kC12Doubles) : 0;   // sliding window: c1x, c1y, c2x, c2y of the whole spline
-  L.off_sL = L.off_sR = L.off_rL = L.off_rR = 0;
+  L.off_sL = L.off_sR = L.off_rL = L.off_rR = L.off_pxy = 0;
   if (sigma_in_lds) {
     const size_t per = (size_t)((N + 1) & ~1) * (strict ? 2 : 1);
     L.off_sL = o; o += per;
     L.off_sR = o; o += per;
+    if (sweep_keeps_table_xy(joint, strict)) { L.off_pxy = o; o += per; }
   }
   L.off_stage = 0;
   L.off_terms = 0;
@@ -190,6 +197,10 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
   constexpr bool STAGED = !RINGS_LDS;   // staged windows: rings in global memory
   constexpr bool FROM = Cfg::from;      // per-instance start line and start indices
   if constexpr (RAISE) { if (!a.raise_flag || a.raise_flag[blockIdx.x] == 0) return; }
+#ifdef RL_STAMPS
+  unsigned long long st_entry = 0;
+  RL_STAMP(st_entry);
+#endif
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   double* smem = reinterpret_cast<double*>(smem_raw);
   const TrackDev& tr = a.tr;
@@ -210,18 +221,23 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
   unsigned short* hints = reinterpret_cast<unsigned short*>(smem + L.off_hint);  // [2][Npad]
   const int Npad = (N + 3) & ~3;
   double* sL; double* sR; double2* rL; double2* rR;
+  constexpr bool TABLE_XY = sweep_keeps_table_xy(JOINT, STRICT);
+  double2* pXY = nullptr;   // TABLE_XY: the table's X, Y of every sample, where the bound points are
   {
     // three residencies of the per-instance state: crossings sL/sR and ring vertices each either in LDS or
     // in the instance's global scratch (rl_mincurv.hip: plan_sweep)
     double* g = a.gscratch + (size_t)b * a.gscratch_stride;
     const size_t per_side = (size_t)((N + 1) & ~1) * (STRICT ? 2 : 1);   // reference-order mode: bound POINTS (double2)
-    if (SIGMA_LDS) { sL = smem + L.off_sL; sR = smem + L.off_sR; }
-    else { sL = g; sR = sL + per_side; g = sR + per_side; }
+    if (SIGMA_LDS) { sL = smem + L.off_sL; sR = smem + L.off_sR; if (TABLE_XY) pXY = reinterpret_cast<double2*>(smem + L.off_pxy); }
+    else {
+      sL = g; sR = sL + per_side; g = sR + per_side;
+      if (TABLE_XY) { pXY = reinterpret_cast<double2*>(g); g += per_side; }
+    }
     if (RINGS_LDS) {
       rL = reinterpret_cast<double2*>(smem + L.off_rL);
       rR = reinterpret_cast<double2*>(smem + L.off_rR);
     } else {
-      if (RL_ABLATE(a, 8)) g = a.gscratch + (SIGMA_LDS ? 0 : 2 * per_side);   // timing only: every instance reads instance 0's rings (L2-hot)
+      if (RL_ABLATE(a, 8)) g = a.gscratch + (SIGMA_LDS ? 0 : (TABLE_XY ? 3 : 2) * per_side);   // timing only: every instance reads instance 0's rings (L2-hot)
       rL = reinterpret_cast<double2*>(g);
       rR = rL + a.nL + kRingPad;
     }
@@ -299,32 +315,25 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
     }
     __syncthreads();
     if (a.search == 2) {
-      for (int c = tid; c < L.ncL + L.ncR; c += BLOCK) {
-        const bool left = c < L.ncL;
-        const int cc = left ? c : c - L.ncL;
-        const double* circ = left ? circL : circR;
-        const int nc = left ? L.ncL : L.ncR;
-        const double mx = circ[3 * cc], my = circ[3 * cc + 1], r = circ[3 * cc + 2];
-        double gap = INFINITY;
-        for (int q = 0; q < nc; ++q) {
-          int dq = q - cc;
-          if (dq < 0) dq = -dq;
-          if (nc - dq < dq) dq = nc - dq;  // cyclic distance in ring order
-          if (dq <= kNear) continue;
-          const double ex = circ[3 * q] - mx, ey = circ[3 * q + 1] - my;
-          gap = fmin(gap, sqrt(ex * ex + ey * ey) - r - circ[3 * q + 2]);
-        }
-        (left ? sepL : sepR)[cc] = gap * (1.0 - 1e-9) - 1e-9;
-      }
-      if (wave == 0) {   // a bound on every ring coordinate, for the quick sign pass of the window scan (+inf: no quick pass)
-        double m = 0.0;
+      if (wave == 0) {   // a bound on every ring coordinate, for the quick sign pass of the window scan (+inf: no quick pass),
+                         // and one on every chunk radius, for the separation pass (rl_sep.hpp; a NaN radius: +inf, no pruning)
+        double m = 0.0, rm = 0.0;
         for (int c = lane; c < L.ncL + L.ncR; c += kWave) {
           const double* o = c < L.ncL ? circL + 3 * c : circR + 3 * (c - L.ncL);
           const double v = fmax(fabs(o[0]), fabs(o[1])) + o[2];
           m = v <= 0x1p+1000 ? fmax(m, v) : INFINITY;
+          rm = o[2] <= 0x1p+1000 ? fmax(rm, o[2]) : INFINITY;
         }
         m = wave_max_bfly(m);
-        if (lane == 0) red[kRedCoordMax] = m;
+        rm = wave_max_bfly(rm);
+        if (lane == 0) { red[kRedCoordMax] = m; red[kRedRadiusMax] = rm; }
+      }
+      __syncthreads();
+      const double rmax = red[kRedRadiusMax];
+      for (int c = tid; c < L.ncL + L.ncR; c += BLOCK) {
+        const bool left = c < L.ncL;
+        const int cc = left ? c : c - L.ncL;
+        (left ? sepL : sepR)[cc] = chunk_separation(left ? circL : circR, left ? L.ncL : L.ncR, cc, kNear, rmax);
       }
       __syncthreads();
     }
@@ -367,7 +376,10 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
   int* n_degen = reinterpret_cast<int*>(red + 190);
   bool flag_mode = false;   // refresh() also re-derives the flags of the samples it re-samples (RAISE) / looks for one (plain)
   bool saw_degenerate = false;   // plain reference-order kernel: a flagged sample was seen while numpy is in raise mode
-  auto refresh = [&](int i0, int i1, int j0, int j1, int mode, int l_first = -1) {
+  // from_base (reference-order first fill of a line that IS the track's c0): position and the two normal directions of a sample
+  // are the track's base_s -- k_build_tables_strict formed them once per track with point()'s operations on point()'s
+  // operands (the same unfused sums over c0 and the D0 / D1 rows it stored, the same correctly rounded heading)
+  auto refresh = [&](int i0, int i1, int j0, int j1, int mode, int l_first = -1, bool from_base = false) {
     const int m0 = i1 - i0, m1 = j1 - j0, m = m0 + m1;
     const double* cmax = red + kRedCoordMax;
     if constexpr (STRICT) {
@@ -435,12 +447,22 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
 #endif
           // both stretches travel while the heading is computed
           int baseL = -1, baseR = -1;
-          point(i, px, py, hd, flag_mode && active, [&]() {
+          auto prefetch = [&]() {
             if constexpr (STAGED) {
               baseL = stage_prefetch(reinterpret_cast<const double2*>(rL), nL, L.ncL, active, (int)hints[i], stgL, lane);
               baseR = stage_prefetch(reinterpret_cast<const double2*>(rR), nR, L.ncR, active, (int)hints[Npad + i], stgR, lane);
             }
-          });
+          };
+          if (from_base) {
+            const double* bs = tr.base_s;
+            px = bs[i]; py = bs[(size_t)N + i];
+            hd.cl = bs[(size_t)2 * N + i]; hd.sl = bs[(size_t)3 * N + i];
+            hd.cr = bs[(size_t)4 * N + i]; hd.sr = bs[(size_t)5 * N + i];
+            hd.yaw = 0.0;   // not read below
+            prefetch();
+          } else {
+            point(i, px, py, hd, flag_mode && active, prefetch);
+          }
           RL_FSTAMP(0);
           const double dLx = a.max_dist * hd.cl, dLy = a.max_dist * hd.sl;   // trajectory.py:87-88, norm = +pi/2
           const double dRx = a.max_dist * hd.cr, dRy = a.max_dist * hd.sr;   //                      norm = -pi/2
@@ -454,6 +476,7 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
             const double2 Lp = make_double2(uf_madd(px, hl.best_s, dLx), uf_madd(py, hl.best_s, dLy));
             const double2 Rp = make_double2(uf_madd(px, hr.best_s, dRx), uf_madd(py, hr.best_s, dRy));
             bL[i] = Lp; bR[i] = Rp;
+            if constexpr (TABLE_XY) pXY[i] = make_double2(px, py);   // the table's X, Y: what the rows of the next steps read
             hints[i] = (unsigned short)(hl.edge == kNoEdge ? 0xFFFF : hl.edge);
             hints[Npad + i] = (unsigned short)(hr.edge == kNoEdge ? 0xFFFF : hr.edge);
             if (JOINT) note_outside_pts(i, px, py, Lp, Rp);
@@ -477,6 +500,7 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
           h = side ? search_ring_brute<true>(rR, nR, px, py, dx, dy) : search_ring_brute<true>(rL, nL, px, py, dx, dy);
         }
         (side ? bR : bL)[i] = make_double2(uf_madd(px, h.best_s, dx), uf_madd(py, h.best_s, dy));
+        if constexpr (TABLE_XY) { if (side == 0) pXY[i] = make_double2(px, py); }
         hints[side * Npad + i] = (unsigned short)(h.edge == kNoEdge ? 0xFFFF : h.edge);
       }
       if constexpr (RAISE) { if (delta != 0) atomicAdd(n_degen, delta); }
@@ -585,7 +609,9 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
     // rings built from per-sample widths / bound points: vertex i sits on sample i's normal
     for (int i = tid; i < 2 * Npad; i += BLOCK) hints[i] = (unsigned short)(i >= Npad ? i - Npad : i);
     __syncthreads();
-    refresh(0, N, 0, 0, 2);  // optimizer.py:259
+    // optimizer.py:259.  The plain and the raise reference-order sweep started from the track's own line: from base_s
+    // (flag_mode is off until the loop begins; the branch mode's normal is not the table's, the window driver stays as it was)
+    refresh(0, N, 0, 0, 2, -1, STRICT && !LITE && !JOINT && from_c0);
   } else {
     refresh(0, N, 0, 0, mode == 2 ? 1 : mode);  // first fill also seeds the hints
   }
@@ -749,8 +775,8 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
           }
           {
 #pragma clang fp contract(off)
-            const double x = seq_dot<K + 1>(cx + (l - K), Ds + (size_t)SR::D0 * N, N, i);
-            const double y = seq_dot<K + 1>(cy + (l - K), Ds + (size_t)SR::D0 * N, N, i);
+            const double2 ps = pXY[i];    // the table's X, Y (refresh: point(), the reference-order sums)
+            const double x = ps.x, y = ps.y;
             const double B0 = Ds[(size_t)(SR::D0 + aa) * N + i];
             const double2 Lp = bL[i], Rp = bR[i];
             const double nzx = x - B0 * zx, nzy = y - B0 * zy;
@@ -852,13 +878,10 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
             double t0[K + 1];
             load_rows<K + 1>(t0, Ds + (size_t)SR::D0 * N, N, ir);
             const double2 Lp = bL[ir], Rp = bR[ir];
+            // the table's X, Y as the last re-sampling of the sample stored them (refresh: point()); a stale table's from its snapshot
+            const double2 ps = (RAISE && stale) ? ptab[ir] : pXY[ir];
             __builtin_amdgcn_sched_barrier(0);
-            double x, y;                    // the table's X, Y: of the current spline unless the table is stale
-            if (RAISE && stale) { const double2 ps = ptab[ir]; x = ps.x; y = ps.y; }
-            else {
-              x = seq_dot_v<K + 1>(cx + (l - K), t0);
-              y = seq_dot_v<K + 1>(cy + (l - K), t0);
-            }
+            const double x = ps.x, y = ps.y;
             // the basis value of idx at the sample is one of the K+1 table values in registers (a look-up would be a second,
             // dependent memory round trip): a support sample has idx - l + K in 0..K
             const int aa = idx - l + K;
@@ -1787,6 +1810,7 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
     for (int q = 0; q < 8; ++q) o[8 + q] = (double)st_fine[q];
     if constexpr (STRICT) { o[11] = (double)st_cnt[3]; o[12] = (double)st_cnt[2]; o[14] = (double)st_cnt[1]; }   // scans, pass-2 rounds, exact sign passes (slot 14 otherwise: tiles that took the full heading)
     o[6] = (double)(st_t1 - st_begin);
+    a.dbg[(size_t)a.B * NW * 16 + (size_t)b * NW + wave] = (double)(st_begin - st_entry);   // the prologue: entry -> first step
     {   // where the wave ran: HW_ID (wave slot, SIMD, CU, shader array, shader engine) and the XCC
       unsigned hw, xcc;
       asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));

@@ -179,22 +179,18 @@ __device__ __forceinline__ int tables_chunk_tables(int search, const double2* rL
     }
     __syncthreads();
     if (mode == 2) {
+      // a bound on every chunk radius for the pruned separation pass (rl_sep.hpp; a NaN radius: +inf, no pruning): every wave
+      // forms it for itself, which needs neither a slot of LDS nor another barrier
+      double rmax = 0.0;
+      for (int c = lane; c < ncL + ncR; c += kWave) {
+        const double rc = c < ncL ? circL[3 * c + 2] : circR[3 * (c - ncL) + 2];
+        rmax = rc <= 0x1p+1000 ? fmax(rmax, rc) : INFINITY;
+      }
+      rmax = wave_max_bfly(rmax);
       for (int c = tid; c < ncL + ncR; c += BLOCK) {
         const bool left = c < ncL;
         const int cc = left ? c : c - ncL;
-        const double* circ = left ? circL : circR;
-        const int nc = left ? ncL : ncR;
-        const double mx = circ[3 * cc], my = circ[3 * cc + 1], r = circ[3 * cc + 2];
-        double gap = INFINITY;
-        for (int q = 0; q < nc; ++q) {
-          int dq = q - cc;
-          if (dq < 0) dq = -dq;
-          if (nc - dq < dq) dq = nc - dq;   // cyclic distance in ring order
-          if (dq <= kNear) continue;
-          const double ex = circ[3 * q] - mx, ey = circ[3 * q + 1] - my;
-          gap = fmin(gap, sqrt(ex * ex + ey * ey) - r - circ[3 * q + 2]);
-        }
-        (left ? sepL : sepR)[cc] = gap * (1.0 - 1e-9) - 1e-9;
+        (left ? sepL : sepR)[cc] = chunk_separation(left ? circL : circR, left ? ncL : ncR, cc, kNear, rmax);
       }
       if (wave == 0) {   // a bound on every ring coordinate, for the quick sign pass of the window scan (+inf: no quick pass)
         double m = 0.0;

@@ -22,12 +22,17 @@ lib = _lib.load()
 _lib.check(lib.rl_debug_dump_enable(1))
 for _ in range(2):
     out = ops.solve_batch_host(trk, _lib.BOUNDS_WIDTHS, W, ist, arith=ARITH)
-buf = np.zeros(B * 4 * 16)
+buf = np.zeros(B * 4 * 17)
 _lib.check(lib.rl_debug_read(buf.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(buf)))
-s = buf.reshape(B, 4, 16)
+s = buf[:B * 4 * 16].reshape(B, 4, 16)
+pro = buf[B * 4 * 16:].reshape(B, 4)   # kernel entry -> first step: rings, chunk circles, separation pass, first fill
 tot = s[:, :, 6]
 names = ["phase 1 (cost + constraints + reductions)", "barrier A", "phase 2 (QP, wave 0)", "barrier B", "phase 3 (refresh)", "barrier C"]
 res = {"kernel_ms": out[4].kernel_ms, "B": B, "arith": ARITH, "cycles_per_wave_mean": float(tot.mean())}
+# a wave's lifetime here: prologue + loop (the epilogue is not stamped)
+res["prologue (entry -> first step)"] = {"share_of_lifetime_all_waves": float((pro / (pro + tot)).mean()),
+                                         "share_of_lifetime_wave0": float((pro[:, 0] / (pro[:, 0] + tot[:, 0])).mean()),
+                                         "cycles_per_wave_mean": float(pro.mean())}
 for q, nm in enumerate(names):
     res[nm] = {"share_all_waves": float((s[:, :, q] / tot).mean()), "share_wave0": float((s[:, 0, q] / tot[:, 0]).mean()),
                "cycles_per_step_mean": float(s[:, :, q].mean() / 610)}

@@ -275,6 +275,42 @@ int rl_mincurv_solve_batch_from_host(rl_ctx* ctx, const rl_track* trk, int bound
                                      int search, double* out_ctrl, double* out_xy, int* n_success, int* status,
                                      rl_stats* stats);
 
+/* ---- the sliding-window driver (run_joint_min_curvature_qp, rl_mincurv_sweep_joint above) batched: B instances in one launch,
+ * one workgroup each, per instance its own bounds (all three forms), its own start line and its own start indices.
+ *   bounds_form, in, ctrl0, i_start, i_start_per_instance, search, out_ctrl, out_xy, stats
+ *           as rl_mincurv_solve_batch_from_dev / _host: ctrl0 NULL or [B,n,2] in scipy's periodic layout, used as given;
+ *           i_start HOST [max_iter], or [B,max_iter] (HOST for *_host, DEVICE for *_dev).  RL_BOUNDS_WIDTHS rings are built
+ *           about TRK's initial control points, not about ctrl0.
+ *   start indices   the window driver's range is [k//2, n-(k-k//2)-5) (optimizer.py:176-178).  Host rows outside it:
+ *           RL_ERR_ARG.  Device rows are validated in the kernel: an instance with a bad row runs no window, status[b] = -1,
+ *           out_ctrl[b] = its start line, out_xy[b] = that line's samples, n_success[b,:] = 0.
+ *   n_success   [B,max_iter] (may be NULL): the windows updated per outer iteration
+ *   status      [B]: the number of windows that were not updated (no feasible QP, or raised)
+ * Degree 5 only; the fast and the reference-order arithmetic (the default resolves to the reference-order one on degree-5
+ * splines).  RL_ARITH_BRANCH, a degree-3 track and a window wider than 768 samples: RL_ERR_UNSUPPORTED.  Both residencies
+ * (all-LDS, all-global).  rl_ctx_set_numpy_raise applies as for the sweep; the reference-order window loop models numpy's
+ * raise mode inline (one launch).  The step dump (rl_debug_dump_enable) does not record these calls and does not change
+ * what they return.  The calls always run instantiations of their own (also with ctrl0 == NULL and shared indices);
+ * rl_mincurv_sweep_joint is unchanged.  From the track's line with shared indices, instance b returns the bits
+ * rl_mincurv_sweep_joint returns for the same bounds, in either arithmetic.
+ *
+ * Continuation.  Fast arithmetic: a run of a + b outer iterations equals a run of a iterations followed by a run of b
+ * iterations from ctrl0 = the first run's out_ctrl with the remaining start indices, bit for bit (control points, samples,
+ * the counts of the last b iterations): the table is a function of the control points.  Reference-order arithmetic: the same
+ * with rl_ctx_set_numpy_raise(ctx, 1) before the second run, under two conditions: (1) no window raised (the oracle's
+ * last_raised() == 0 in both parts and in the whole run) -- a raise leaves a stale table, which control points cannot carry;
+ * (2) at least one window of the first a iterations was updated -- the reference enters raise mode at the first window that
+ * reaches the simulator call (optimizer.py:208), not at the end of iteration 0, so a first part without any update leaves
+ * the uninterrupted run outside raise mode where the resumed run is inside it. */
+int rl_mincurv_solve_batch_joint_dev(rl_ctx* ctx, const rl_track* trk, int bounds_form, const double* in, int B,
+                                     const double* ctrl0, const int* i_start, int i_start_per_instance, int max_iter,
+                                     int search, double* out_ctrl, double* out_xy, int* n_success, int* status,
+                                     rl_stats* stats);
+int rl_mincurv_solve_batch_joint_host(rl_ctx* ctx, const rl_track* trk, int bounds_form, const double* in, int B,
+                                      const double* ctrl0, const int* i_start, int i_start_per_instance, int max_iter,
+                                      int search, double* out_ctrl, double* out_xy, int* n_success, int* status,
+                                      rl_stats* stats);
+
 /* ---- least-squares periodic B-spline through P points per instance ON trk's KNOTS (degree trk->k; csrc/rl_spline_fit.hpp):
  * what scipy.interpolate.splprep([x,y], u=u, t=trk's knots, task=-1, per=True, k=k) returns for the closed loop (FITPACK
  * clocur; the reference's own fit, models/trajectory.py:219-222, is task 0 of the same routine).  This is how a line that is

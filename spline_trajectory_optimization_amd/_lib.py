@@ -79,6 +79,10 @@ _SIGNATURES = {
                                                        ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.POINTER(Stats)]),
     "rl_mincurv_solve_batch_from_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, ctypes.c_int, _dp, _ip, ctypes.c_int,
                                                         ctypes.c_int, ctypes.c_int, _dp, _dp, _ip, _ip, ctypes.POINTER(Stats)]),
+    "rl_mincurv_solve_batch_joint_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int,
+                                                        ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.POINTER(Stats)]),
+    "rl_mincurv_solve_batch_joint_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, ctypes.c_int, _dp, _ip, ctypes.c_int,
+                                                         ctypes.c_int, ctypes.c_int, _dp, _dp, _ip, _ip, ctypes.POINTER(Stats)]),
     "rl_spline_fit_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
                                                _vp, _vp]),
     "rl_spline_fit_batch_host": (ctypes.c_int, [_vp, _vp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_int,

@@ -106,26 +106,39 @@ def width_batch(w_left, w_right, B, seed=1234, eps=0.15, floor=1.5):
     return w
 
 
-def default_i_start(n, k, max_iter, seed=0):
-    """A pinned stand-in for the unseeded np.random.randint of optimizer.py:303."""
+def i_start_range(n, k, driver="sweep"):
+    """[lo, hi) of np.random.randint for the start index: optimizer.py:303 (driver "sweep") or the sliding window's,
+    optimizer.py:178 (driver "window")."""
+    if driver == "window":
+        return ops.window_i_start_range(n, k)
+    if driver != "sweep":
+        raise ValueError(f"driver: expected 'sweep' or 'window', got {driver!r}")
+    return k // 2, n - (k - k // 2)
+
+
+def default_i_start(n, k, max_iter, seed=0, driver="sweep"):
+    """A pinned stand-in for the unseeded np.random.randint of optimizer.py:303 (driver "window": of optimizer.py:178)."""
+    lo, hi = i_start_range(n, k, driver)
     rng = np.random.RandomState(seed)
-    return np.array([rng.randint(k // 2, n - (k - k // 2)) for _ in range(max_iter)], dtype=np.int32)
+    return np.array([rng.randint(lo, hi) for _ in range(max_iter)], dtype=np.int32)
 
 
-def default_i_start_batch(n, k, max_iter, B, seed=0):
+def default_i_start_batch(n, k, max_iter, B, seed=0, driver="sweep"):
     """B draws of the start indices, row b = default_i_start(seed=seed + b): int32 [B,max_iter] for the per-instance
     form of ops.solve_batch_host / _torch ("how much does the line depend on the draw": B draws, one launch)."""
-    return np.stack([default_i_start(n, k, max_iter, seed=seed + b) for b in range(B)]).astype(np.int32)
+    return np.stack([default_i_start(n, k, max_iter, seed=seed + b, driver=driver) for b in range(B)]).astype(np.int32)
 
 
-def polish_lines_torch(track, xy, bounds_form, bounds, i_start, u=None, search=_lib.SEARCH_WINDOWED, arith=None):
+def polish_lines_torch(track, xy, bounds_form, bounds, i_start, u=None, search=_lib.SEARCH_WINDOWED, arith=None,
+                       driver="sweep"):
     """Lines that are not the track's -> sweep: fit every instance's points onto the track's knots (ops.spline_fit_torch:
     xy [B,P,2] points or [B,P,19] tables, e.g. the pose tables of a min-time batch), then sweep every instance from its fit
     (ops.solve_batch_torch with ctrl0 = the fit), both enqueued on torch's current stream with no host round trip.  An
     instance whose fit failed (fit_stats[:,0] != 0) starts from the track's control points.  i_start [max_iter] or
-    [B,max_iter].  Returns the dict of solve_batch_torch plus fit_ctrl [B,n,2] and fit_stats [B,4]."""
+    [B,max_iter].  driver: "sweep" or "window" (the sliding-window driver polishes the fit).  Returns the dict of
+    solve_batch_torch plus fit_ctrl [B,n,2] and fit_stats [B,4]."""
     fit_ctrl, fit_stats = ops.spline_fit_torch(track, xy, u=u)
-    out = ops.solve_batch_torch(track, bounds_form, bounds, i_start, search=search, arith=arith, ctrl0=fit_ctrl)
+    out = ops.solve_batch_torch(track, bounds_form, bounds, i_start, search=search, arith=arith, ctrl0=fit_ctrl, driver=driver)
     out["fit_ctrl"] = fit_ctrl
     out["fit_stats"] = fit_stats
     return out

@@ -217,6 +217,24 @@ int launch_sweep_from(const rl_ctx* ctx, int k, const SweepPlan& p, const rl::Sw
   return fail(RL_ERR_UNSUPPORTED, "spline degree must be 3 or 5");
 }
 
+// The sliding window from per-instance start lines / start indices (rl_mincurv_solve_batch_joint_*): the SweepConfigWindowFrom
+// instantiations, in the residency the plan chose, in the two arithmetics the window driver exists in (the reference-order
+// loop models numpy's raise mode inline: one launch).
+template <rl::Arith ARITH>
+int launch_sweep_window_from_in(const rl_ctx* ctx, const SweepPlan& p, const rl::SweepArgs& a) {
+  using rl::Residency; using rl::SweepConfigWindowFrom;
+  const dim3 grid(a.B), block(rl::kSweepThreads);
+  return p.residency == Residency::Lds
+             ? launch(ctx, rl::k_sweep<SweepConfigWindowFrom<Residency::Lds, ARITH>>, grid, block, p.lds_bytes, a)
+             : launch(ctx, rl::k_sweep<SweepConfigWindowFrom<Residency::Global, ARITH>>, grid, block, p.lds_bytes, a);
+}
+int launch_sweep_window_from(const rl_ctx* ctx, int k, const SweepPlan& p, const rl::SweepArgs& a, bool strict) {
+  using rl::Arith;
+  if (k != 5) return fail(RL_ERR_UNSUPPORTED, "the sliding-window variant is built for degree 5 (span 5)");
+  if (strict) return launch_sweep_window_from_in<Arith::Reference>(ctx, p, a);
+  return launch_sweep_window_from_in<Arith::Fast>(ctx, p, a);
+}
+
 // tables of the reference-order mode (rl_kernels.hpp: k_build_tables_strict), built on first use
 int ensure_strict_tables(const rl_ctx* ctx, const rl_track* trk) {
   if (trk->strict_valid) return RL_OK;
@@ -588,17 +606,19 @@ static int solve_batch_common(rl_ctx* ctx, const rl_track* trk, int form, const 
                               int B, const int* i_start, int max_iter, int search,
                               double* out_ctrl, double* out_xy, double* out_points, int* n_success,
                               int* status, rl_stats* stats, SweepPlan* plan_out, bool joint = false,
-                              const double* ctrl0 = nullptr, const int* i_start_rows = nullptr) {
+                              const double* ctrl0 = nullptr, const int* i_start_rows = nullptr, bool joint_batch = false) {
   // ctrl0 / i_start_rows (DEVICE, rl_mincurv_solve_batch_from_*): per-instance start lines / start indices; `i_start` is then
-  // unused when rows are given
-  const bool from = ctrl0 || i_start_rows;
+  // unused when rows are given.  joint_batch (rl_mincurv_solve_batch_joint_*): the sliding window on the SweepConfigWindowFrom
+  // instantiations, whatever ctrl0 and the rows are -- one path, one n_success layout [B,max_iter]
+  const bool from = ctrl0 || i_start_rows || joint_batch;
   if (!ctx || !trk || (!i_start && !i_start_rows) || !out_ctrl) return fail(RL_ERR_ARG, "null argument");
-  if (from && joint) return fail(RL_ERR_UNSUPPORTED, "the sliding-window driver has no per-instance start lines");
+  if (from && joint && !joint_batch) return fail(RL_ERR_UNSUPPORTED, "the sliding-window driver has no per-instance start lines");
   if (!out_xy && !out_points) return fail(RL_ERR_ARG, "need out_xy or out_points");
   if (B <= 0) return fail(RL_ERR_ARG, "B <= 0");
   if (max_iter <= 0 || max_iter > RL_MAX_ITER) return fail(RL_ERR_ARG, "max_iter out of range");
   if (search < RL_SEARCH_BRUTE || search > RL_SEARCH_WINDOWED) return fail(RL_ERR_ARG, "bad search mode");
   const int n = trk->n, N = trk->N, k = trk->k;
+  if (joint_batch && k != 5) return fail(RL_ERR_UNSUPPORTED, "the sliding-window variant is built for degree 5 (span 5)");
   const int i_min = k / 2, i_max = n - (k - k / 2) - (joint ? 5 : 0);
   if (i_max <= i_min) return fail(RL_ERR_ARG, "too few control points");
   for (int j = 0; j < max_iter && !i_start_rows; ++j)
@@ -698,6 +718,7 @@ static int solve_batch_common(rl_ctx* ctx, const rl_track* trk, int form, const 
     stats->reserved[0] = arith;
   }
   if (plan_out) *plan_out = p;
+  if (joint_batch) return launch_sweep_window_from(ctx, k, p, a, strict);
   if (from) return launch_sweep_from(ctx, k, p, a, strict, lite);
   return launch_sweep(ctx, k, p, a, joint, strict, lite);
 }
@@ -731,6 +752,40 @@ int rl_mincurv_solve_batch_host(rl_ctx* ctx, const rl_track* trk, int bounds_for
   return sg.finish(stats);
 }
 
+// Host pointers of the per-instance entry points (rl_mincurv_solve_batch_from_host / _joint_host): validates host rows against
+// the driver's range, stages, runs solve_batch_common, copies back.  joint_batch: the sliding-window driver (its range ends a span
+// earlier, it counts once per outer iteration).
+static int solve_batch_from_host_common(rl_ctx* ctx, const rl_track* trk, int bounds_form, const double* in, int B,
+                                        const double* ctrl0, const int* i_start, int i_start_per_instance, int max_iter,
+                                        int search, double* out_ctrl, double* out_xy, int* n_success, int* status,
+                                        rl_stats* stats, bool joint_batch) {
+  if (!ctx || !trk || !out_ctrl || !out_xy || !i_start) return fail(RL_ERR_ARG, "null argument");
+  if (B <= 0) return fail(RL_ERR_ARG, "B <= 0");
+  if (max_iter <= 0 || max_iter > RL_MAX_ITER) return fail(RL_ERR_ARG, "max_iter out of range");
+  const int n = trk->n, N = trk->N, k = trk->k;
+  if (i_start_per_instance) {   // host rows are validated here; the kernel's own check is for rows that never were on the host
+    const int i_min = k / 2, i_max = n - (k - k / 2) - (joint_batch ? 5 : 0);
+    for (size_t j = 0; j < (size_t)B * max_iter; ++j)
+      if (i_start[j] < i_min || i_start[j] >= i_max)
+        return fail(RL_ERR_ARG, joint_batch ? "i_start outside [k//2, n-(k-k//2)-span) (optimizer.py:176-178)"
+                                            : "i_start outside [k//2, n-(k-k//2)) (optimizer.py:301-303)");
+  }
+  const int cols = bounds_cols(bounds_form);
+  if (cols && !in) return fail(RL_ERR_ARG, "bounds input is null");
+  Staging sg(ctx);
+  const double* din = cols ? sg.in(in, (size_t)B * N * cols) : nullptr;
+  const double* dc0 = sg.in(ctrl0, (size_t)B * n * 2);
+  const int* drows = i_start_per_instance ? sg.in(i_start, (size_t)B * max_iter) : nullptr;
+  double *dctrl = sg.out(out_ctrl, (size_t)B * n * 2), *dxy = sg.out(out_xy, (size_t)B * N * 2);
+  int* dns = sg.out_optional(n_success, (size_t)B * (joint_batch ? 1 : 2) * max_iter);
+  int* dst = sg.out_optional(status, B);
+  sg.run_timed([&] {
+    return solve_batch_common(ctx, trk, bounds_form, din, B, i_start_per_instance ? nullptr : i_start, max_iter, search, dctrl, dxy,
+                              nullptr, dns, dst, stats, nullptr, joint_batch, dc0, drows, joint_batch);
+  });
+  return sg.finish(stats);
+}
+
 int rl_mincurv_solve_batch_from_dev(rl_ctx* ctx, const rl_track* trk, int bounds_form, const double* in, int B,
                                     const double* ctrl0, const int* i_start, int i_start_per_instance, int max_iter,
                                     int search, double* out_ctrl, double* out_xy, int* n_success, int* status, rl_stats* stats) {
@@ -744,29 +799,26 @@ int rl_mincurv_solve_batch_from_dev(rl_ctx* ctx, const rl_track* trk, int bounds
 int rl_mincurv_solve_batch_from_host(rl_ctx* ctx, const rl_track* trk, int bounds_form, const double* in, int B,
                                      const double* ctrl0, const int* i_start, int i_start_per_instance, int max_iter,
                                      int search, double* out_ctrl, double* out_xy, int* n_success, int* status, rl_stats* stats) {
-  if (!ctx || !trk || !out_ctrl || !out_xy || !i_start) return fail(RL_ERR_ARG, "null argument");
-  if (B <= 0) return fail(RL_ERR_ARG, "B <= 0");
-  if (max_iter <= 0 || max_iter > RL_MAX_ITER) return fail(RL_ERR_ARG, "max_iter out of range");
-  const int n = trk->n, N = trk->N, k = trk->k;
-  if (i_start_per_instance) {   // host rows are validated here; the kernel's own check is for rows that never were on the host
-    const int i_min = k / 2, i_max = n - (k - k / 2);
-    for (size_t j = 0; j < (size_t)B * max_iter; ++j)
-      if (i_start[j] < i_min || i_start[j] >= i_max) return fail(RL_ERR_ARG, "i_start outside [k//2, n-(k-k//2)) (optimizer.py:301-303)");
-  }
-  const int cols = bounds_cols(bounds_form);
-  if (cols && !in) return fail(RL_ERR_ARG, "bounds input is null");
-  Staging sg(ctx);
-  const double* din = cols ? sg.in(in, (size_t)B * N * cols) : nullptr;
-  const double* dc0 = sg.in(ctrl0, (size_t)B * n * 2);
-  const int* drows = i_start_per_instance ? sg.in(i_start, (size_t)B * max_iter) : nullptr;
-  double *dctrl = sg.out(out_ctrl, (size_t)B * n * 2), *dxy = sg.out(out_xy, (size_t)B * N * 2);
-  int* dns = sg.out_optional(n_success, (size_t)B * 2 * max_iter);
-  int* dst = sg.out_optional(status, B);
-  sg.run_timed([&] {
-    return solve_batch_common(ctx, trk, bounds_form, din, B, i_start_per_instance ? nullptr : i_start, max_iter, search, dctrl, dxy,
-                              nullptr, dns, dst, stats, nullptr, false, dc0, drows);
-  });
-  return sg.finish(stats);
+  return solve_batch_from_host_common(ctx, trk, bounds_form, in, B, ctrl0, i_start, i_start_per_instance, max_iter, search,
+                                      out_ctrl, out_xy, n_success, status, stats, false);
+}
+
+// ---- the sliding-window driver, batched: per-instance start lines, start indices and bounds
+int rl_mincurv_solve_batch_joint_dev(rl_ctx* ctx, const rl_track* trk, int bounds_form, const double* in, int B,
+                                     const double* ctrl0, const int* i_start, int i_start_per_instance, int max_iter,
+                                     int search, double* out_ctrl, double* out_xy, int* n_success, int* status, rl_stats* stats) {
+  if (!out_xy) return fail(RL_ERR_ARG, "out_xy is null");
+  if (!i_start) return fail(RL_ERR_ARG, "i_start is null");
+  return solve_batch_common(ctx, trk, bounds_form, in, B, i_start_per_instance ? nullptr : i_start, max_iter, search, out_ctrl,
+                            out_xy, nullptr, n_success, status, stats, nullptr, true, ctrl0,
+                            i_start_per_instance ? i_start : nullptr, true);
+}
+
+int rl_mincurv_solve_batch_joint_host(rl_ctx* ctx, const rl_track* trk, int bounds_form, const double* in, int B,
+                                      const double* ctrl0, const int* i_start, int i_start_per_instance, int max_iter,
+                                      int search, double* out_ctrl, double* out_xy, int* n_success, int* status, rl_stats* stats) {
+  return solve_batch_from_host_common(ctx, trk, bounds_form, in, B, ctrl0, i_start, i_start_per_instance, max_iter, search,
+                                      out_ctrl, out_xy, n_success, status, stats, true);
 }
 
 // ---- periodic least-squares fit onto the track's knots (rl_spline_fit.hpp)

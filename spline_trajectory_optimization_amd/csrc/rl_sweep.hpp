@@ -186,6 +186,13 @@ struct SweepConfigFrom : SweepConfig<K_, RESIDENCY, Driver::Sweep, ARITH, false>
   static_assert(RESIDENCY != Residency::CrossingsLds, "per-instance start lines: all-LDS or all-global residency");
   static constexpr bool from = true;
 };
+// The sliding window started per instance (rl_mincurv_solve_batch_joint_*): a.ctrl0[b], a.i_start_rows[b], rows validated against
+// the window's range, n_success[B,max_iter].  A type of its own again: rl_mincurv_sweep_joint keeps its instantiations.
+template <Residency RESIDENCY, Arith ARITH = Arith::Fast>
+struct SweepConfigWindowFrom : SweepConfig<5, RESIDENCY, Driver::Window, ARITH, false> {
+  static_assert(RESIDENCY != Residency::CrossingsLds, "the sliding-window driver: all-LDS or all-global residency");
+  static constexpr bool from = true;
+};
 
 template <class Cfg>
 __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep(SweepArgs a) {
@@ -624,14 +631,16 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
   const int i_max = n - ignore_rear, i_min = ignore_front;
   // outer iterations this instance runs and where each starts: the kernel arguments, or (FROM) the instance's own row, read in a
   // branch of its own -- one pointer that selects between the argument array and global memory would cost every reader scratch.
-  // A row with an index outside [i_min, i_max) runs no step (status -1, the start line comes back).
+  // A row with an index outside [i_min, i_max) runs no step (status -1, the start line comes back).  The sliding window's
+  // range ends a span earlier (optimizer.py:176-178: j_max of its loop below).
   int n_iter = a.max_iter;
   bool bad_row = false;
   if constexpr (FROM) {
     if (a.i_start_rows) {
+      constexpr int row_span = JOINT ? 5 : 0;
       for (int it = 0; it < a.max_iter; ++it) {
         const int st = a.i_start_rows[(size_t)b * a.max_iter + it];
-        if (st < i_min || st >= i_max) bad_row = true;
+        if (st < i_min || st >= i_max - row_span) bad_row = true;
       }
       if (bad_row) n_iter = 0;
     }
@@ -1135,8 +1144,8 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
       }
     };
     if (STRICT && jdegen && a.np_raise_at_start) jraise = true;
-    for (int it = 0; it < a.max_iter; ++it) {
-      const int st = a.i_start[it];
+    for (int it = 0; it < n_iter; ++it) {
+      const int st = start_of(it);
       int ok_count = 0;
       for (int stp = 0; stp < j_max - i_min; ++stp) {  // :180-183
         int kk = stp + st;
@@ -1645,8 +1654,12 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
           ++n_skipped;
         }
       }
-      if (tid == 0 && a.n_success) a.n_success[(size_t)b * 2 * a.max_iter + 2 * it] = ok_count;
-      if (tid == 0 && a.n_success) a.n_success[(size_t)b * 2 * a.max_iter + 2 * it + 1] = 0;
+      if constexpr (FROM) {   // rl_mincurv_solve_batch_joint_*: [B,max_iter], the windows updated per outer iteration
+        if (tid == 0 && a.n_success) a.n_success[(size_t)b * a.max_iter + it] = ok_count;
+      } else {
+        if (tid == 0 && a.n_success) a.n_success[(size_t)b * 2 * a.max_iter + 2 * it] = ok_count;
+        if (tid == 0 && a.n_success) a.n_success[(size_t)b * 2 * a.max_iter + 2 * it + 1] = 0;
+      }
     }
   } else
   for (int it = 0; it < n_iter; ++it) {
@@ -1827,7 +1840,8 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
   if constexpr (FROM) {
     if (bad_row) {
       n_skipped = -1;
-      if (a.n_success) for (int q = tid; q < 2 * a.max_iter; q += BLOCK) a.n_success[(size_t)b * 2 * a.max_iter + q] = 0;
+      constexpr int per_iter = JOINT ? 1 : 2;   // the sliding window counts once per outer iteration
+      if (a.n_success) for (int q = tid; q < per_iter * a.max_iter; q += BLOCK) a.n_success[(size_t)b * per_iter * a.max_iter + q] = 0;
     }
   }
   if (tid == 0 && a.status) a.status[b] = n_skipped;

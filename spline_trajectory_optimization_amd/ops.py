@@ -195,13 +195,35 @@ def _i_start_rows(i_start, B):
     return i_start, 0, len(i_start)
 
 
-def solve_batch_host(track, bounds_form, bounds, i_start, search=_lib.SEARCH_WINDOWED, B=None, arith=None, ctrl0=None):
+def window_i_start_range(n, k):
+    """[lo, hi) of the sliding-window driver's start indices (optimizer.py:176-178), span 5."""
+    return k // 2, n - (k - k // 2) - 5
+
+
+def _check_driver(driver):
+    if driver not in ("sweep", "window"):
+        raise ValueError(f"driver: expected 'sweep' or 'window', got {driver!r}")
+    return driver == "window"
+
+
+def _check_window_rows(track, i_start):
+    """Host start indices of the sliding-window driver: ValueError outside its range."""
+    lo, hi = window_i_start_range(track.n, track.k)
+    if i_start.size and (int(i_start.min()) < lo or int(i_start.max()) >= hi):
+        raise ValueError(f"i_start: the window driver's start indices lie in [{lo},{hi}), got [{int(i_start.min())},{int(i_start.max())}]")
+
+
+def solve_batch_host(track, bounds_form, bounds, i_start, search=_lib.SEARCH_WINDOWED, B=None, arith=None, ctrl0=None,
+                     driver="sweep"):
     """Batched sweep with host (numpy) buffers.  bounds: widths [B,N,2] / points [B,N,4] / None.
     ctrl0: None (every instance starts from the track's control points) or [B,n,2], instance b's start line;
     i_start: [max_iter] shared or [B,max_iter] per instance (rl_mincurv_solve_batch_from_host; the defaults go to
     rl_mincurv_solve_batch_host).
-    Returns (ctrl [B,n,2], xy [B,N,2], n_success [B,max_iter,2], status [B], stats)."""
+    driver: "sweep" (run_min_curvature_qp) or "window" (run_joint_min_curvature_qp, rl_mincurv_solve_batch_joint_host: start
+    indices in window_i_start_range, n_success [B,max_iter]).
+    Returns (ctrl [B,n,2], xy [B,N,2], n_success [B,max_iter,2] (driver "window": [B,max_iter]), status [B], stats)."""
     ctx = track.ctx
+    window = _check_driver(driver)
     if bounds is not None:
         bounds, bp = as_d(bounds)
         B = bounds.shape[0]
@@ -215,10 +237,21 @@ def solve_batch_host(track, bounds_form, bounds, i_start, search=_lib.SEARCH_WIN
     i_start, per, max_iter = _i_start_rows(i_start, B)
     ip = i_start.ctypes.data_as(_ip)
     ctrl = np.zeros((B, track.n, 2)); xy = np.zeros((B, track.N, 2))
-    ns = np.zeros((B, max_iter, 2), dtype=np.int32); status = np.zeros(B, dtype=np.int32)
+    ns = np.zeros((B, max_iter) if window else (B, max_iter, 2), dtype=np.int32); status = np.zeros(B, dtype=np.int32)
     st = Stats()
     with _arith_scope(ctx, arith):
-        if ctrl0 is None and not per:
+        if window:
+            _check_window_rows(track, i_start)
+            cp = None
+            if ctrl0 is not None:
+                ctrl0, cp = as_d(ctrl0)
+                if ctrl0.shape != (B, track.n, 2):
+                    raise ValueError(f"ctrl0: expected shape {(B, track.n, 2)}, got {ctrl0.shape}")
+            check(ctx.lib.rl_mincurv_solve_batch_joint_host(ctx.h, track.h, int(bounds_form), bp, int(B), cp, ip, per,
+                                                            max_iter, int(search), ctrl.ctypes.data_as(_dp),
+                                                            xy.ctypes.data_as(_dp), ns.ctypes.data_as(_ip),
+                                                            status.ctypes.data_as(_ip), ctypes.byref(st)))
+        elif ctrl0 is None and not per:
             check(ctx.lib.rl_mincurv_solve_batch_host(ctx.h, track.h, int(bounds_form), bp, int(B), ip,
                                                       max_iter, int(search), ctrl.ctypes.data_as(_dp),
                                                       xy.ctypes.data_as(_dp), ns.ctypes.data_as(_ip),
@@ -236,15 +269,20 @@ def solve_batch_host(track, bounds_form, bounds, i_start, search=_lib.SEARCH_WIN
     return ctrl, xy, ns, status, st
 
 
-def solve_batch_torch(track, bounds_form, bounds, i_start, search=_lib.SEARCH_WINDOWED, out=None, arith=None, ctrl0=None):
+def solve_batch_torch(track, bounds_form, bounds, i_start, search=_lib.SEARCH_WINDOWED, out=None, arith=None, ctrl0=None,
+                      driver="sweep"):
     """Batched sweep on DEVICE tensors (torch is plumbing for memory and streams only).
     bounds: float64 cuda tensor [B,N,2|4] (None with BOUNDS_SHARED_RINGS, which then needs ctrl0 for the batch size).
     ctrl0: None or a float64 cuda tensor [B,n,2], instance b's start line; i_start: [max_iter] (host) or [B,max_iter] as a
     numpy array or an int32 cuda tensor, which the kernel validates (status -1 for a row with an index out of range):
     rl_mincurv_solve_batch_from_dev; the defaults go to rl_mincurv_solve_batch_dev.
-    Enqueues on torch's current stream, no sync.  Returns dict(ctrl, xy, n_success, status) of cuda tensors."""
+    driver: "sweep" or "window" (the sliding-window driver, rl_mincurv_solve_batch_joint_dev: n_success [B,max_iter]; host
+    start indices are checked against window_i_start_range here, a cuda tensor of rows by the kernel).
+    Enqueues on torch's current stream, no sync.  Returns dict(ctrl, xy, n_success [B,max_iter,2] (driver "window":
+    [B,max_iter]), status) of cuda tensors."""
     import torch
     ctx = track.ctx
+    window = _check_driver(driver)
     if bounds is None:
         if bounds_form != _lib.BOUNDS_SHARED_RINGS or ctrl0 is None:
             raise ValueError("bounds: None needs BOUNDS_SHARED_RINGS and ctrl0 [B,n,2]")
@@ -263,6 +301,8 @@ def solve_batch_torch(track, bounds_form, bounds, i_start, search=_lib.SEARCH_WI
             per, max_iter = 1, int(i_start.shape[1])
     if rows is None:
         i_start, per, max_iter = _i_start_rows(i_start, B)
+        if window:
+            _check_window_rows(track, i_start)
         if per:
             rows = torch.from_numpy(i_start).to(dev)
     if ctrl0 is not None:
@@ -271,14 +311,19 @@ def solve_batch_torch(track, bounds_form, bounds, i_start, search=_lib.SEARCH_WI
         out = {
             "ctrl": torch.empty((B, track.n, 2), dtype=torch.float64, device=dev),
             "xy": torch.empty((B, track.N, 2), dtype=torch.float64, device=dev),
-            "n_success": torch.empty((B, max_iter, 2), dtype=torch.int32, device=dev),
+            "n_success": torch.empty((B, max_iter) if window else (B, max_iter, 2), dtype=torch.int32, device=dev),
             "status": torch.empty((B,), dtype=torch.int32, device=dev),
         }
     ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
     st = Stats()
     p = lambda t_: None if t_ is None else ctypes.c_void_p(t_.data_ptr())  # noqa: E731
     with _arith_scope(ctx, arith):
-        if ctrl0 is None and not per:
+        if window:
+            ip = p(rows) if per else ctypes.c_void_p(i_start.ctypes.data)
+            check(ctx.lib.rl_mincurv_solve_batch_joint_dev(
+                ctx.h, track.h, int(bounds_form), p(bounds), int(B), p(ctrl0), ip, per, max_iter,
+                int(search), p(out["ctrl"]), p(out["xy"]), p(out["n_success"]), p(out["status"]), ctypes.byref(st)))
+        elif ctrl0 is None and not per:
             check(ctx.lib.rl_mincurv_solve_batch_dev(
                 ctx.h, track.h, int(bounds_form), p(bounds), int(B), i_start.ctypes.data_as(_ip), max_iter,
                 int(search), p(out["ctrl"]), p(out["xy"]), p(out["n_success"]), p(out["status"]), ctypes.byref(st)))

@@ -520,6 +520,22 @@ int rl_qss_sim(rl_ctx* ctx, double* points, int B, int N, const double* acc_x, c
 int rl_qss_sim_dev(rl_ctx* ctx, double* points, int B, int N, const double* acc_x, const double* acc_c,
                    int acc_m, const double* dcc_x, const double* dcc_c, int dcc_m, const double* params,
                    int* iters);
+/* rl_qss_sim_dev with ONE VEHICLE PER INSTANCE (vehicle sweeps: B grip levels, power curves, speed caps or jerk limits on one
+ * line or on B lines, one launch).  The vehicle arrays carry a leading batch dimension:
+ *   acc_x [B,acc_m+1], acc_c [B,4,acc_m], dcc_x [B,dcc_m+1], dcc_c [B,4,dcc_m], params [B,6]
+ * Breakpoints and coefficients may differ per instance; the piece counts acc_m, dcc_m are common to the batch (the kernels'
+ * LDS layout depends on them).  points and iters as for rl_qss_sim.  EVERY pointer is a DEVICE pointer, the vehicle arrays
+ * included (they are read by the kernels, from the launch until the stream has run them): enqueued on the context's stream,
+ * no synchronisation, scratch from the context's grow-only arena.  Instance b returns the bits rl_qss_sim returns for its
+ * table with vehicle b alone.  Errors, limits, the choice between the list-order and the dataflow kernel (from N and the
+ * piece counts) and the test hooks ("qss_kernel", "qss_df_waves", "qss_df_bail_at", "qss_df_redo") are rl_qss_sim_dev's. */
+int rl_qss_sim_vehicles_dev(rl_ctx* ctx, double* points, int B, int N, const double* acc_x, const double* acc_c,
+                            int acc_m, const double* dcc_x, const double* dcc_c, int dcc_m, const double* params,
+                            int* iters);
+/* Same with HOST pointers throughout: staged to the device, run, copied back, synchronised. */
+int rl_qss_sim_vehicles_host(rl_ctx* ctx, double* points, int B, int N, const double* acc_x, const double* acc_c,
+                             int acc_m, const double* dcc_x, const double* dcc_c, int dcc_m, const double* params,
+                             int* iters);
 
 /* ---- tables of a solved batch (csrc/rl_tables.hpp).  For every instance b: the table BSplineTrajectory.sample_along(ts = i/N)
  * builds from the spline (trk's knots, ctrl[b]) (models/trajectory.py:268-291), then Trajectory.fill_bounds against that

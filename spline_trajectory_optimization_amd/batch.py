@@ -164,24 +164,94 @@ def vehicle_tables(vehicle):
             np.ascontiguousarray(dcc.c), params)
 
 
-def lap_times_torch(track, ctrl, bounds_form, bounds, length, vehicle, bank=None):
+def vehicle_tables_batch(vehicles):
+    """B vehicles as rl_qss_sim_vehicles_* takes them: a sequence of Vehicles or 5-tuples (vehicle_tables) -> the five stacked
+    arrays acc_x [B,m+1], acc_c [B,4,m], dcc_x [B,m'+1], dcc_c [B,4,m'], params [B,6] (numpy float64, C-contiguous).
+    Breakpoints and coefficients may differ per vehicle; the piece counts m, m' are common to the batch (the kernels' LDS
+    layout depends on them): ValueError naming the first vehicle whose counts differ from vehicle 0's."""
+    tabs = [vehicle_tables(v) for v in vehicles]
+    if not tabs:
+        raise ValueError("vehicles: empty sequence")
+    tabs = [tuple(np.asarray(a, dtype=np.float64) for a in t) for t in tabs]
+    m0 = (len(tabs[0][0]) - 1, len(tabs[0][2]) - 1)
+    for b, t in enumerate(tabs):
+        ax, ac, dx, dc, pr = t
+        m = (len(ax) - 1, len(dx) - 1)
+        if ac.shape != (4, m[0]) or dc.shape != (4, m[1]) or pr.shape != (6,):
+            raise ValueError(f"vehicles[{b}]: expected acc_c [4,{m[0]}], dcc_c [4,{m[1]}], params [6]")
+        if m != m0:
+            raise ValueError(f"vehicles[{b}]: {m[0]} / {m[1]} pieces in the acc / dcc lookup, vehicles[0] has {m0[0]} / {m0[1]}: "
+                             "piece counts are common to a batch")
+    return tuple(np.ascontiguousarray(np.stack([t[q] for t in tabs])) for q in range(5))
+
+
+def _one_of(vehicle, vehicles):
+    if (vehicle is None) == (vehicles is None):
+        raise ValueError("exactly one of vehicle (shared by the batch) and vehicles (one per instance) must be given")
+
+
+def _vehicles_stacked(vehicles, B, device=None):
+    """`vehicles` of lap_times_*: B Vehicles / 5-tuples, or the stacked 5-tuple of vehicle_tables_batch as numpy arrays or cuda
+    tensors -> the stacked 5-tuple as cuda tensors on `device`, or as numpy arrays for device None."""
+    stacked = isinstance(vehicles, (tuple, list)) and len(vehicles) == 5 and all(hasattr(a, "ndim") for a in vehicles)
+    veh = tuple(vehicles) if stacked else vehicle_tables_batch(vehicles)
+    if int(veh[4].shape[0]) != B:
+        raise ValueError(f"vehicles: {int(veh[4].shape[0])} vehicles for {B} instances")
+    if device is None:
+        return tuple(a if isinstance(a, np.ndarray) else a.cpu().numpy() for a in veh)
+    import torch
+    return tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(device) if isinstance(a, np.ndarray) else a
+                 for a in veh)
+
+
+def lap_times_torch(track, ctrl, bounds_form, bounds, length, vehicle=None, bank=None, vehicles=None):
     """Which of these B solved lines is the fastest lap, and what is its table: tables of the batch (ops.tables_torch) ->
     QSS simulation in place (ops.qss_sim_torch) -> per-instance summary (ops.table_summary_torch), all enqueued on torch's
     current stream with no host round trip.  ctrl [B,n,2] (e.g. solve_batch_torch(...)["ctrl"]), bounds / bank as for
-    ops.tables_torch, vehicle = a Vehicle or vehicle_tables(...).  Returns dict(points [B,N,19], iters [B] int32,
-    summary [B,8] in the order of ops.SUMMARY_COLUMNS) of cuda tensors."""
-    veh = vehicle_tables(vehicle)
+    ops.tables_torch, vehicle = a Vehicle or vehicle_tables(...).  vehicles (instead of vehicle) = one vehicle per instance
+    (ops.qss_sim_vehicles_torch): B Vehicles / 5-tuples, or the stacked 5-tuple of vehicle_tables_batch as numpy arrays or
+    cuda tensors.  Returns dict(points [B,N,19], iters [B] int32, summary [B,8] in the order of ops.SUMMARY_COLUMNS) of cuda
+    tensors."""
+    _one_of(vehicle, vehicles)
+    if vehicles is None:
+        veh = vehicle_tables(vehicle)
+    else:
+        if getattr(ctrl, "ndim", None) != 3:
+            raise ValueError(f"ctrl: expected [B,{track.n},2]")
+        veh = _vehicles_stacked(vehicles, int(ctrl.shape[0]), ctrl.device)
     points = ops.tables_torch(track, ctrl, bounds_form, bounds, length, bank=bank)
-    iters = ops.qss_sim_torch(points, *veh)
+    iters = ops.qss_sim_torch(points, *veh) if vehicles is None else ops.qss_sim_vehicles_torch(points, *veh)
     summary = ops.table_summary_torch(points, iters)
     return {"points": points, "iters": iters, "summary": summary}
 
 
-def lap_times_host(track, ctrl, bounds_form, bounds, length, vehicle, bank=None):
+def lap_times_grid_torch(track, ctrl, bounds_form, bounds, length, vehicles, bank=None):
+    """Every one of L lines under every one of V vehicles: the L tables once (ops.tables_torch), expanded to L V instances on
+    the device (instance l V + v = line l, vehicle v), ONE QSS launch with per-instance vehicles (ops.qss_sim_vehicles_torch)
+    and the summary, all enqueued on torch's current stream with no host round trip.  ctrl [L,n,2], bounds / bank as for
+    ops.tables_torch; vehicles: V Vehicles / 5-tuples or the stacked 5-tuple of vehicle_tables_batch (numpy or cuda).
+    Returns dict(summary [L,V,8] in the order of ops.SUMMARY_COLUMNS, iters [L,V] int32, points [L,V,N,19]) of cuda tensors."""
+    if getattr(ctrl, "ndim", None) != 3:
+        raise ValueError(f"ctrl: expected [L,{track.n},2]")
+    L = int(ctrl.shape[0])
+    stacked = isinstance(vehicles, (tuple, list)) and len(vehicles) == 5 and all(hasattr(a, "ndim") for a in vehicles)
+    V = int(vehicles[4].shape[0]) if stacked else len(vehicles)
+    veh = _vehicles_stacked(vehicles, V, ctrl.device)
+    lines = ops.tables_torch(track, ctrl, bounds_form, bounds, length, bank=bank)
+    N = int(lines.shape[1])
+    points = lines[:, None].expand(L, V, N, _lib.NCOL).contiguous().view(L * V, N, _lib.NCOL)
+    veh = tuple(a[None].expand((L,) + tuple(a.shape)).contiguous().view((L * V,) + tuple(a.shape[1:])) for a in veh)
+    iters = ops.qss_sim_vehicles_torch(points, *veh)
+    summary = ops.table_summary_torch(points, iters)
+    return {"summary": summary.view(L, V, -1), "iters": iters.view(L, V), "points": points.view(L, V, N, _lib.NCOL)}
+
+
+def lap_times_host(track, ctrl, bounds_form, bounds, length, vehicle=None, bank=None, vehicles=None):
     """lap_times_torch for numpy input (float64, C-contiguous): copies in, runs the same chain on the track's device, copies
     out.  Returns dict(points, iters, summary) of numpy arrays."""
     import torch
-    veh = vehicle_tables(vehicle)
+    _one_of(vehicle, vehicles)
+    veh = vehicle_tables(vehicle) if vehicles is None else None
     B, bshape, kshape, _ = ops._tables_shapes(track, ctrl, bounds_form, bounds, bank)
     ops._check_np(ctrl, "ctrl", (B, track.n, 2))
     if bshape:
@@ -190,7 +260,9 @@ def lap_times_host(track, ctrl, bounds_form, bounds, length, vehicle, bank=None)
         ops._check_np(bank, "bank", kshape)
     dev = torch.device("cuda", track.ctx.device)
     up = lambda a: None if a is None else torch.from_numpy(a).to(dev)  # noqa: E731
-    out = lap_times_torch(track, up(ctrl), bounds_form, up(bounds), length, veh, bank=up(bank))
+    if vehicles is not None:
+        vehicles = _vehicles_stacked(vehicles, B, dev)
+    out = lap_times_torch(track, up(ctrl), bounds_form, up(bounds), length, veh, bank=up(bank), vehicles=vehicles)
     return {k_: v.cpu().numpy() for k_, v in out.items()}
 
 

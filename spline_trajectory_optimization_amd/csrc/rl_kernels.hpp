@@ -570,7 +570,7 @@ __global__ void k_constraint_strict(TrackDev tr, const double* __restrict__ cx, 
 // instances are the parallel axis.
 constexpr int kQssTabMax = 5 * 2 * 24 + 2;   // two tables of up to 24 cubic pieces each in the kernel arguments
 
-struct QssArgs {
+struct QssHead {
   double* points;        // [B,N,19] in place
   int B, N;
   const double* acc_x; const double* acc_c; int acc_m;   // CubicSpline pieces of Vehicle.acc_intp
@@ -588,8 +588,26 @@ struct QssArgs {
   int* dbg;              // optional [B][12]: passes, chunks, examinations, steps, wake pushes, numbering events, spawned fronts, bail reason
   int df_bail_at;        // k_qss_dfw only, tests: hand the instance back once a step of this iteration has run (0: never)
   int redo;              // k_qss_sim only: 1 = run just the instances k_qss_dfw handed back (iters[b] == -2)
+  // One vehicle PER INSTANCE (rl_qss_sim_vehicles_*): params [B,6] on the device, the four table pointers above device arrays
+  // with a leading batch dimension (acc_x [B,m+1], acc_c [B,4m], dcc_x [B,m'+1], dcc_c [B,4m']), tab_n = 0.  nullptr: one
+  // vehicle for the batch, the six scalars and the tables as above.
+  const double* veh;
+};
+struct QssArgs : QssHead {
   double tab[kQssTabMax];
 };
+
+// Per-instance vehicles: instance b's six scalars into the workgroup's copy of the arguments (of QssHead: the by-value tables stay
+// in the kernel arguments) and its table pointers onto the instance's rows, so that everything behind the prologue reads `a`
+// as it does for a shared vehicle.
+__device__ __forceinline__ void qss_instance_vehicle(QssHead& a, int b) {
+  if (!a.veh) return;
+  const double* p = a.veh + (size_t)6 * b;
+  a.max_lon_acc = p[0]; a.max_lon_dcc = p[1]; a.max_left_acc = p[2];
+  a.max_right_acc = p[3]; a.max_speed = p[4]; a.max_jerk = p[5];
+  a.acc_x += (size_t)b * (a.acc_m + 1); a.acc_c += (size_t)b * 4 * a.acc_m;
+  a.dcc_x += (size_t)b * (a.dcc_m + 1); a.dcc_c += (size_t)b * 4 * a.dcc_m;
+}
 
 // scipy PPoly.evaluate (extrapolate=True): power basis summed from the constant term
 __device__ __forceinline__ double ppoly_eval(const double* __restrict__ xb, const double* __restrict__ c,
@@ -631,7 +649,7 @@ struct Ppoly2 {
   }
 };
 
-__device__ __forceinline__ double qss_acc_circle_lon(const QssArgs& a, double lon) {
+__device__ __forceinline__ double qss_acc_circle_lon(const QssHead& a, double lon) {
 #pragma clang fp contract(off)
   lon = lon < a.max_lon_dcc ? a.max_lon_dcc : (lon > a.max_lon_acc ? a.max_lon_acc : lon);  // np.clip
   const double max_lon = lon > 0.0 ? a.max_lon_acc : a.max_lon_dcc;
@@ -671,11 +689,13 @@ __device__ __forceinline__ double qss_lat_acc(double v, double r, double bank) {
 constexpr int kQssStamp = 1024;  // stamp words: [0,512) actual writers, [512,768) potential targets, [768,1024) sources (index mod table size: a shared bucket only costs a false conflict)
 constexpr int kQssWr = 512, kQssSt = 256;
 constexpr int kQssStaticMin = 4;   // fronts still pending after a chunk's first round from which the static mode pays for its set-up
-__global__ __launch_bounds__(64) void k_qss_sim(QssArgs a) {
+__global__ __launch_bounds__(64) void k_qss_sim(QssArgs ka) {
 #pragma clang fp contract(off)  // decisions below compare freshly computed speeds: keep the reference's roundings
   extern __shared__ double qss_lds[];
+  QssHead a = ka;
   const int b = blockIdx.x, N = a.N, lane = threadIdx.x, cap = a.cap;
   if (a.redo && a.iters[b] != -2) return;
+  qss_instance_vehicle(a, b);
   double* P = a.points + (size_t)b * N * 19;
   double* V = qss_lds;             // [N] SPEED
   double* A = qss_lds + N;         // [N] LON_ACC
@@ -694,7 +714,7 @@ __global__ __launch_bounds__(64) void k_qss_sim(QssArgs a) {
   const double lat0 = qss_acc_circle_lon(a, 0.0);
   for (int i = lane; i < kQssStamp; i += 64) STAMP[i] = kFree;
   if (a.tab_n > 0) {
-    for (int i = lane; i < a.tab_n; i += 64) tab[i] = a.tab[i];      // same order as the LDS image
+    for (int i = lane; i < a.tab_n; i += 64) tab[i] = ka.tab[i];      // same order as the LDS image
   } else {
     for (int i = lane; i <= a.acc_m; i += 64) t_ax[i] = a.acc_x[i];
     for (int i = lane; i < 4 * a.acc_m; i += 64) t_ac[i] = a.acc_c[i];

@@ -1189,9 +1189,11 @@ int rl_region_index_dev(rl_ctx* ctx, const double* xy, int B, int N, int stride,
   return region_launch(ctx, xy, stride, n, verts, offsets, R, nullptr, out, nullptr, 0);
 }
 
-int rl_qss_sim_dev(rl_ctx* ctx, double* points, int B, int N, const double* acc_x, const double* acc_c,
-                   int acc_m, const double* dcc_x, const double* dcc_c, int dcc_m, const double* params,
-                   int* iters) {
+// The body of rl_qss_sim_dev and rl_qss_sim_vehicles_dev.  per_instance: the five vehicle arrays are DEVICE arrays with a leading
+// batch dimension and every workgroup reads its own rows (QssArgs::veh); otherwise small host arrays of one vehicle.
+static int qss_sim_enqueue(rl_ctx* ctx, double* points, int B, int N, const double* acc_x, const double* acc_c,
+                           int acc_m, const double* dcc_x, const double* dcc_c, int dcc_m, const double* params,
+                           int* iters, bool per_instance) {
   if (!ctx || !points || !acc_x || !acc_c || !dcc_x || !dcc_c || !params || !iters)
     return fail(RL_ERR_ARG, "null argument");
   if (B <= 0 || N < 2 || acc_m < 1 || dcc_m < 1) return fail(RL_ERR_ARG, "bad sizes");
@@ -1205,19 +1207,20 @@ int rl_qss_sim_dev(rl_ctx* ctx, double* points, int B, int N, const double* acc_
   // arguments, so the call is asynchronous and keeps no pointer to caller memory; longer tables are staged through the arena
   // with pageable copies (the runtime then blocks the host until it has read them).
   const int tab_n = (acc_m + 1) + 4 * acc_m + (dcc_m + 1) + 4 * dcc_m;
-  const bool by_value = tab_n <= rl::kQssTabMax;
+  const bool by_value = !per_instance && tab_n <= rl::kQssTabMax;
+  const bool staged = !per_instance && !by_value;
   Arena ar(ctx);
   double *dax = nullptr, *dac = nullptr, *ddx = nullptr, *ddc = nullptr, *dcst = nullptr;
   int *dfl = nullptr, *dnw = nullptr;
   RL_HIP(ar.carve([&](Arena& x) {
-    if (!by_value) {
+    if (staged) {
       dax = x.take<double>(acc_m + 1); dac = x.take<double>((size_t)4 * acc_m);
       ddx = x.take<double>(dcc_m + 1); ddc = x.take<double>((size_t)4 * dcc_m);
     }
     dfl = x.take<int>((size_t)B * cap * 5); dnw = x.take<int>((size_t)B * cap);
     dcst = x.take<double>((size_t)B * 3 * N);
   }));
-  if (!by_value) {
+  if (staged) {
     RL_HIP(hipMemcpyAsync(dax, acc_x, (acc_m + 1) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     RL_HIP(hipMemcpyAsync(dac, acc_c, (size_t)4 * acc_m * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     RL_HIP(hipMemcpyAsync(ddx, dcc_x, (dcc_m + 1) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
@@ -1227,8 +1230,14 @@ int rl_qss_sim_dev(rl_ctx* ctx, double* points, int B, int N, const double* acc_
   a.points = points; a.B = B; a.N = N;
   a.acc_x = dax; a.acc_c = dac; a.acc_m = acc_m;
   a.dcc_x = ddx; a.dcc_c = ddc; a.dcc_m = dcc_m;
-  a.max_lon_acc = params[0]; a.max_lon_dcc = params[1]; a.max_left_acc = params[2];
-  a.max_right_acc = params[3]; a.max_speed = params[4]; a.max_jerk = params[5];
+  a.veh = nullptr;
+  if (per_instance) {   // the kernels' prologue reads the scalars and the rows of its instance
+    a.acc_x = acc_x; a.acc_c = acc_c; a.dcc_x = dcc_x; a.dcc_c = dcc_c; a.veh = params;
+    a.max_lon_acc = a.max_lon_dcc = a.max_left_acc = a.max_right_acc = a.max_speed = a.max_jerk = 0.0;
+  } else {
+    a.max_lon_acc = params[0]; a.max_lon_dcc = params[1]; a.max_left_acc = params[2];
+    a.max_right_acc = params[3]; a.max_speed = params[4]; a.max_jerk = params[5];
+  }
   a.flags = dfl; a.fresh = dnw; a.cst = dcst; a.cap = cap; a.iters = iters;
   a.tab_n = 0; a.redo = 0; a.dbg = nullptr; a.df_bail_at = ctx->qss_df_bail_at; a.df_report = ctx->qss_df_redo ? 0 : 1;
   if (by_value) {
@@ -1288,6 +1297,36 @@ int rl_qss_sim_dev(rl_ctx* ctx, double* points, int B, int N, const double* acc_
   if (!use_df || ctx->qss_df_redo) RL_TRY(launch(ctx, rl::k_qss_sim, dim3(B), dim3(64), lds, a));
   RL_HIP(ar.end());
   return RL_OK;
+}
+
+int rl_qss_sim_dev(rl_ctx* ctx, double* points, int B, int N, const double* acc_x, const double* acc_c,
+                   int acc_m, const double* dcc_x, const double* dcc_c, int dcc_m, const double* params,
+                   int* iters) {
+  return qss_sim_enqueue(ctx, points, B, N, acc_x, acc_c, acc_m, dcc_x, dcc_c, dcc_m, params, iters, false);
+}
+
+int rl_qss_sim_vehicles_dev(rl_ctx* ctx, double* points, int B, int N, const double* acc_x, const double* acc_c,
+                            int acc_m, const double* dcc_x, const double* dcc_c, int dcc_m, const double* params,
+                            int* iters) {
+  return qss_sim_enqueue(ctx, points, B, N, acc_x, acc_c, acc_m, dcc_x, dcc_c, dcc_m, params, iters, true);
+}
+
+int rl_qss_sim_vehicles_host(rl_ctx* ctx, double* points, int B, int N, const double* acc_x, const double* acc_c,
+                             int acc_m, const double* dcc_x, const double* dcc_c, int dcc_m, const double* params,
+                             int* iters) {
+  if (!ctx || !points || !acc_x || !acc_c || !dcc_x || !dcc_c || !params || !iters)
+    return fail(RL_ERR_ARG, "null argument");
+  if (B <= 0 || N < 2 || acc_m < 1 || dcc_m < 1) return fail(RL_ERR_ARG, "bad sizes");
+  Staging sg(ctx);
+  double* dpts = sg.inout(points, (size_t)B * N * RL_NCOL);
+  const double* dax = sg.in(acc_x, (size_t)B * (acc_m + 1));
+  const double* dac = sg.in(acc_c, (size_t)B * 4 * acc_m);
+  const double* ddx = sg.in(dcc_x, (size_t)B * (dcc_m + 1));
+  const double* ddc = sg.in(dcc_c, (size_t)B * 4 * dcc_m);
+  const double* dpr = sg.in(params, (size_t)B * 6);
+  int* dit = sg.out(iters, B);
+  sg.run([&] { return rl_qss_sim_vehicles_dev(ctx, dpts, B, N, dax, dac, acc_m, ddx, ddc, dcc_m, dpr, dit); });
+  return sg.finish();
 }
 
 int rl_qss_sim(rl_ctx* ctx, double* points, int B, int N, const double* acc_x, const double* acc_c,

@@ -318,13 +318,13 @@ __device__ __forceinline__ int dfw_exam(const DfTab& T, bool isX, int r, int w, 
 
 struct DfStep { int new_stop, e, spawned, wr, nown; double nv, na; };
 struct DfStepCtx {
-  const QssArgs* a; const DfTab* T; double lat0; bool small_tabs; const Ppoly2 *pa2, *pd2;
+  const QssHead* a; const DfTab* T; double lat0; bool small_tabs; const Ppoly2 *pa2, *pd2;
   const double *t_ax, *t_ac, *t_dx, *t_dc;
 };
 // One step of one side of one front (:154-254 enter, :257-348 exit) -- the arithmetic of k_qss_sim, expression for expression.
 __device__ __forceinline__ DfStep dfw_step(const DfStepCtx& C, int side, int li, int ni, double dd, double rn, double gsn, int turn) {
 #pragma clang fp contract(off)
-  const QssArgs& a = *C.a;
+  const QssHead& a = *C.a;
   const DfTab& T = *C.T;
   DfStep o; o.new_stop = 0; o.e = 0; o.spawned = 0; o.wr = 0; o.nown = 0; o.nv = 0.0; o.na = 0.0;
   const double lv = T.V[li], la = T.A[li];
@@ -388,13 +388,15 @@ enum { DFS_Q2N = 0, DFS_Q2NE, DFS_NWIN, DFS_ERR, DFS_BAIL, DFS_FREE, DFS_NSPQ, D
 static_assert(DFS_COUNT <= 32, "scalars");
 
 template <int W>
-__global__ __launch_bounds__(64 * W) void k_qss_dfw(QssArgs a) {
+__global__ __launch_bounds__(64 * W) void k_qss_dfw(QssArgs ka) {
 #pragma clang fp contract(off)  // decisions below compare freshly computed speeds: keep the reference's roundings
   extern __shared__ double qss_lds[];
   typedef unsigned short u16;
   typedef unsigned long long u64;
   constexpr int TT = 64 * W;
+  QssHead a = ka;
   const int b = blockIdx.x, N = a.N, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  qss_instance_vehicle(a, b);
   const DfLayout L = df_layout(N, a.acc_m, a.dcc_m);
   char* lds = reinterpret_cast<char*>(qss_lds);
   DfTab T;
@@ -440,7 +442,7 @@ __global__ __launch_bounds__(64 * W) void k_qss_dfw(QssArgs a) {
   const double lat0 = qss_acc_circle_lon(a, 0.0);
 
   if (a.tab_n > 0) {
-    for (int i = tid; i < a.tab_n; i += TT) tab[i] = a.tab[i];
+    for (int i = tid; i < a.tab_n; i += TT) tab[i] = ka.tab[i];
   } else {
     for (int i = tid; i <= a.acc_m; i += TT) t_ax[i] = a.acc_x[i];
     for (int i = tid; i < 4 * a.acc_m; i += TT) t_ac[i] = a.acc_c[i];

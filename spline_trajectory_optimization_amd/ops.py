@@ -516,6 +516,62 @@ def _check_torch(a, name, shape, dtype=None):
     return a
 
 
+def _vehicles_shapes(acc_x, acc_c, dcc_x, dcc_c, params):
+    """(B, acc_m, dcc_m, shapes of the five arrays) of a stack of vehicles (batch.vehicle_tables_batch); ValueError for a bad
+    rank -- before any library call."""
+    if getattr(params, "ndim", None) != 2 or getattr(acc_x, "ndim", None) != 2 or getattr(dcc_x, "ndim", None) != 2:
+        raise ValueError("vehicles: expected acc_x [B,m+1], acc_c [B,4,m], dcc_x [B,m'+1], dcc_c [B,4,m'], params [B,6]")
+    B, acc_m, dcc_m = int(params.shape[0]), int(acc_x.shape[1]) - 1, int(dcc_x.shape[1]) - 1
+    if B <= 0 or acc_m < 1 or dcc_m < 1:
+        raise ValueError("vehicles: needs at least one vehicle and one piece per lookup table")
+    return B, acc_m, dcc_m, ((B, acc_m + 1), (B, 4, acc_m), (B, dcc_m + 1), (B, 4, dcc_m), (B, 6))
+
+
+_VEHICLE_NAMES = ("acc_x", "acc_c", "dcc_x", "dcc_c", "params")
+
+
+def qss_sim_vehicles(points, acc_x, acc_c, dcc_x, dcc_c, params, device=None):
+    """qss_sim with ONE VEHICLE PER INSTANCE (rl_qss_sim_vehicles_host): points [B,N,19]; acc_x [B,m+1], acc_c [B,4,m],
+    dcc_x [B,m'+1], dcc_c [B,4,m'], params [B,6] as batch.vehicle_tables_batch stacks them (piece counts common to the
+    batch).  numpy float64, C-contiguous.  Returns (points_out, iterations[B])."""
+    B, acc_m, dcc_m, shapes = _vehicles_shapes(acc_x, acc_c, dcc_x, dcc_c, params)
+    if getattr(points, "ndim", None) != 3:
+        raise ValueError(f"points: expected [{B},N,{_lib.NCOL}]")
+    _check_np(points, "points", (B, points.shape[1], _lib.NCOL))
+    veh = (acc_x, acc_c, dcc_x, dcc_c, params)
+    for a, name, shape in zip(veh, _VEHICLE_NAMES, shapes):
+        _check_np(a, name, shape)
+    ctx = Context.get(device)
+    pts = points.copy()
+    it = np.zeros(B, dtype=np.int32)
+    p = lambda a: a.ctypes.data_as(_dp)  # noqa: E731
+    check(ctx.lib.rl_qss_sim_vehicles_host(ctx.h, p(pts), B, int(pts.shape[1]), p(acc_x), p(acc_c), acc_m, p(dcc_x), p(dcc_c),
+                                           dcc_m, p(params), it.ctypes.data_as(_ip)))
+    return pts, it
+
+
+def qss_sim_vehicles_torch(points, acc_x, acc_c, dcc_x, dcc_c, params):
+    """qss_sim_vehicles on DEVICE tensors (float64 cuda, contiguous), the vehicle arrays included, `points` in place: enqueues
+    on torch's current stream, no sync (rl_qss_sim_vehicles_dev).  Returns the iterations tensor [B] (int32, cuda)."""
+    import torch
+    B, acc_m, dcc_m, shapes = _vehicles_shapes(acc_x, acc_c, dcc_x, dcc_c, params)
+    if getattr(points, "ndim", None) != 3:
+        raise ValueError(f"points: expected [{B},N,{_lib.NCOL}]")
+    _check_torch(points, "points", (B, points.shape[1], _lib.NCOL))
+    veh = (acc_x, acc_c, dcc_x, dcc_c, params)
+    for a, name, shape in zip(veh, _VEHICLE_NAMES, shapes):
+        _check_torch(a, name, shape)
+        if a.device != points.device:
+            raise ValueError(f"{name}: on {a.device}, points on {points.device}")
+    ctx = Context.get(points.device.index)
+    ctx.set_stream(torch.cuda.current_stream(points.device).cuda_stream)
+    it = torch.empty((B,), dtype=torch.int32, device=points.device)
+    p = lambda t_: ctypes.c_void_p(t_.data_ptr())  # noqa: E731
+    check(ctx.lib.rl_qss_sim_vehicles_dev(ctx.h, p(points), B, int(points.shape[1]), p(acc_x), p(acc_c), acc_m, p(dcc_x),
+                                          p(dcc_c), dcc_m, p(params), p(it)))
+    return it
+
+
 def _tables_shapes(track, ctrl, bounds_form, bounds, bank):
     """(B, bounds shape | None, bank shape | None, bank_per_instance) of a tables call; ValueError for a bad form / rank."""
     if bounds_form not in _BOUNDS_COLS:

@@ -137,6 +137,9 @@ int rl_ctx_set_numpy_raise(rl_ctx* ctx, int on);
  *                     (default), 1 = in the arena
  *   "frenet_search"   1 = rl_frenet_batch_* bounds a point from the piece the previous point of its line landed on (default),
  *                     0 = from the table of the pieces alone
+ *   "sweep_bracket"   1 = the sweep's window scan (rings in global memory) brackets the crossing around the edge it was found on
+ *                     last time, where the window's direction cone proves the side values monotone (default), 0 = it always
+ *                     forms the side of all 25 vertices
  * Defaults come from RL_QSS_DF / RL_QSS_V1 / RL_QSS_DF_WAVES / RL_QSS_DF_BAIL_AT, read ONCE in rl_ctx_create. */
 int rl_ctx_set_option(rl_ctx* ctx, const char* name, int value);
 /* test aid: out[n,5] = yaw, cos / sin(yaw + pi/2), cos / sin(yaw - pi/2) of the tangents (dx, dy), as the

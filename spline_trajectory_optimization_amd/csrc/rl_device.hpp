@@ -6,6 +6,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "rl_sep.hpp"   // chunk_separation: the separation pass of the windowed search, shared with the host check
+#include "rl_cone.hpp"  // cone_record, cone_monotone: the direction cone of a window (scan_window's bracket path), shared with the host check
 
 namespace rl {
 
@@ -309,15 +310,17 @@ constexpr int kWinChunks = 3;
 constexpr int kNear = 1;                        // chunks ce-kNear..ce+kNear are checked one by one
 constexpr int kWinEdges = kWinChunks * kChunk;  // 24; rings must be longer than twice this
 constexpr int kRingPad = kWinEdges + 1;         // vertices repeated behind the ring
+static_assert(kConeChunk == kChunk && kConeEdges == kWinEdges, "rl_cone.hpp describes this window");
 constexpr int kWinBatch = 8;
 
 // `lo` addresses the vertices (ring[lo .. lo + kWinEdges]); `lo_edge` numbers the edges (edge q of the window is edge
 // lo_edge + q of the ring, modulo nr).  Scanning the ring itself: lo == lo_edge; scanning a staged stretch: lo = offset
 // of the window inside the stretch.
-template <int BATCH = kWinBatch, bool ST = false, typename RingPtr>
+template <int BATCH = kWinBatch, bool ST = false, bool BRACKET = false, typename RingPtr>
 __device__ __forceinline__ void scan_window(RingPtr ring, int nr, int lo, int lo_edge, double px, double py,
                                             double dx, double dy, Hit& h, const double* cmax_p,
-                                            unsigned long long* counts = nullptr) {   // counts (diagnostic build): [1] exact passes, [2] pass-2 rounds, [3] scans
+                                            unsigned long long* counts = nullptr,   // counts (diagnostic build): [1] exact passes, [2] pass-2 rounds, [3] scans, [4] scans that took the bracket
+                                            bool bracket = false, int bq = -1) {    // BRACKET: the path is on (wave-uniform); the hinted edge's position in the window
   // Pass 1 per vertex: its side value e, then TWO bookkeeping instructions -- the sign bit of e shifted into a 25-bit word
   // (v_alignbit) and a running minimum of |e|.  Edge q is a candidate when the signs of its two vertices differ; a vertex
   // exactly ON the line (e == +-0, seen as a zero minimum) makes every edge of the window a candidate.  That is a superset of
@@ -334,11 +337,52 @@ __device__ __forceinline__ void scan_window(RingPtr ring, int nr, int lo, int lo
   // non-finite vertex) or a vertex closer to the line than that sends the WAVE through the exact pass -- the untouched far
   // end of a support in the first sweep (a width-form ring's vertex i sits on sample i's first normal), hardly ever later.
   // A NaN vertex inside a finite ring gives no crossing on its edges whichever way its sign bit is read.
-  unsigned cand;
-  {
+  // BRACKET (sweep driver, staged windows): the window was centred on the edge `bq` that changed sign when this sample was
+  // re-sampled last, and its record (rl_cone.hpp, in the pad slot behind the window's middle chunk) tells whether the side
+  // values are strictly MONOTONE along the window for this direction: e_{k+1} - e_k = cross(v_{k+1} - v_k, d), one sign for
+  // every edge inside the cone.  A monotone sequence changes sign at most once, so four vertices bq-1 .. bq+2 can stand for
+  // all 25: with the quick e' of the four beyond today's tol and exactly one change of sign among them, the real side values
+  // at the two ends of the four are beyond tol - 4u Mp D - u |e'| > 120 u Mp D on opposite sides, and monotonicity puts
+  // every vertex NOT looked at beyond the end on its side: its real value is further than 120 u Mp D from zero, which is far
+  // outside what the exact arithmetic (fused or not) can do to it, 4u Mp D -- its rounded sign is its side's and it is not
+  // zero.  The full pass -- quick, or exact where a lane of the wave is not sure -- therefore forms the word with exactly this
+  // one bit, and finds every lane sure.  Taken only when EVERY lane in the scan qualifies: otherwise the wave runs the pass
+  // below as it always did.
+  unsigned cand = 0u;
+  bool sure = true, bracketed = false;
+  if constexpr (BRACKET) {
+    if (bracket) {
+      const bool inq = bq >= 1 && bq <= kWinEdges - 2;
+      const int k0 = inq ? bq - 1 : 0;
+      double2 w[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) w[u] = ring[lo + k0 + u];
+      const ConeRec rec = ring.record();
+      const double c0 = fma(px, dy, -(py * dx));
+      const double e0 = fma(w[0].x, dy, fma(-w[0].y, dx, -c0));
+      unsigned sg = (unsigned)__double2hiint(e0) >> 31;
+      double emin = fabs(e0);
+#pragma unroll
+      for (int u = 1; u < 4; ++u) {
+        const double e = fma(w[u].x, dy, fma(-w[u].y, dx, -c0));
+        sg = __builtin_amdgcn_alignbit(sg, (unsigned)__double2hiint(e), 31);
+        emin = fmin(emin, fabs(e));
+      }
+      const double tol = 0x1p-46 * ((cmax_p[opaque_zero()] + fabs(px)) + fabs(py)) * (fabs(dx) + fabs(dy));
+      const unsigned x = (sg ^ (sg >> 1)) & 7u;   // bit 2: edge bq-1 changes sign, bit 1: edge bq, bit 0: edge bq+1
+      // (no short circuit: one straight run of compares instead of nested masked regions)
+      const bool ok = inq & (emin > tol) & (tol > 0x1p-900) & (tol < 0x1p+900) & (x != 0u) & ((x & (x - 1u)) == 0u) &
+                      cone_monotone(rec, dx, dy);
+      bracketed = !__any(!ok);
+      if (bracketed) cand = 1u << (k0 + 2 - (int)(x >> 1));
+#ifdef RL_STAMPS
+      if (counts && bracketed) { counts[3] += 1; counts[4] += 1; }
+#endif
+    }
+  }
+  if (!bracketed) {
     unsigned signs;
     double emin;
-    bool sure;
     {
       const double c0 = fma(px, dy, -(py * dx));
       double2 v = ring[lo];
@@ -388,6 +432,8 @@ __device__ __forceinline__ void scan_window(RingPtr ring, int nr, int lo, int lo
     // sign change across edge q <-> bits 24 - q and 23 - q of `signs` differ <-> bit 23 - q of signs ^ (signs >> 1); reversed: bit q
     cand = __builtin_bitreverse32((signs ^ (signs >> 1)) & 0xFFFFFFu) >> 8;
     if (!sure) cand = 0xFFFFFFu;
+  }
+  {
     // An edge flagged for a CHANGE OF SIGN has its end points on different sides (or one of them is a zero of the other
     // sign bit): edge_hit's two early exits -- product positive; product zero with both factors non-zero and of one sign -- can
     // not fire, so pass 2 goes straight to the crossing, without forming the two side values again.  Only a wave that holds a
@@ -434,7 +480,14 @@ static_assert(kStage >= kWinEdges + 1 + 64 && kStage <= 104, "a stretch holds th
 constexpr int kStageSlots = kStage + kStage / kChunk;   // 108
 __device__ __forceinline__ int stage_slot(int v) { return v + (v >> 3); }
 
-__device__ __forceinline__ void stage_issue(const double2* ring, int nr, int base, double2* stg, int lane) {
+// REC (the sweep driver's bracket path): the pad slot behind chunk j of the stretch receives the cone record (rl_cone.hpp) of the
+// window that chunk is the middle of -- a lane whose window starts at chunk j of the stretch finds its record in the pad behind
+// chunk j + 1, between the vertices it is about to read.  The records lie behind the ring in the same array, rec_off double2 from
+// `ring`: entry m is the record of the window that starts at chunk (m - 1) mod nchunk, for m up to nchunk + kStage / kChunk - 2, so
+// that the pad lanes need no wrap (a stretch that runs over the seam of a ring whose length is no multiple of kChunk serves no
+// window behind the seam, search_ring_windowed: what those pads hold is never read).  Still two DMA instructions, 64 lanes each.
+template <bool REC = false>
+__device__ __forceinline__ void stage_issue(const double2* ring, int nr, int base, double2* stg, int lane, int rec_off = 0) {
   // two DMA instructions, neither predicated: slots 0..63 and slots kStageSlots-64..kStageSlots-1 (the twenty slots both cover
   // receive the same vertex twice).  Exactly two vector-memory operations whatever the lanes do: the wait counts of loads
   // issued BEFORE a stretch request stay exact (a conditional request makes the compiler wait for everything).
@@ -445,6 +498,7 @@ __device__ __forceinline__ void stage_issue(const double2* ring, int nr, int bas
     const int v = t - t / 9;                 // the vertex of slot t (slots 8, 17, 26, ... are the pads: they fetch a neighbour)
     int idx = base + (v < kStage ? v : kStage - 1);
     if (idx >= nr) idx -= nr;                // (base + v) mod nr: base < nr and v < kStage <= nr (the caller checks)
+    if constexpr (REC) { if (t - 9 * (t / 9) == 8) idx = (rec_off + (base >> 3)) + t / 9; }
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ring + idx),
                                      (__attribute__((address_space(3))) void*)(stg + t0), 16, 0, 0);
   }
@@ -453,6 +507,12 @@ __device__ __forceinline__ void stage_issue(const double2* ring, int nr, int bas
 struct StagedWindow {
   const double2* p;   // slot of the window's first vertex
   __device__ __forceinline__ double2 operator[](int k) const { return p[k + (k >> 3)]; }
+  // the cone record of the window (stage_issue<true>): the pad slot behind its middle chunk
+  __device__ __forceinline__ ConeRec record() const {
+    const double2 r = p[2 * kChunk + 1];
+    return ConeRec{__int_as_float(__double2loint(r.x)), __int_as_float(__double2hiint(r.x)),
+                   __int_as_float(__double2loint(r.y)), __int_as_float(__double2hiint(r.y))};
+  }
 };
 // the stretch has landed and is visible to this wave's LDS reads
 __device__ __forceinline__ void stage_wait() {
@@ -470,14 +530,15 @@ __device__ __forceinline__ int window_start(int hint, int nchunk) {
 // returns the base to hand to search_ring_windowed as `staged_base`.  The search waits for the copy (stage_wait) before its
 // first read -- also when no lane had a usable hint and the stretch at 0 was fetched for nothing: the stretches share their
 // LDS with the cost terms of the next step, no copy may still be on its way when the refresh ends.
-__device__ __forceinline__ int stage_prefetch(const double2* ring, int nr, int nchunk, bool active, int hint, double2* stg, int lane) {
+template <bool REC = false>
+__device__ __forceinline__ int stage_prefetch(const double2* ring, int nr, int nchunk, bool active, int hint, double2* stg, int lane, int rec_off = 0) {
   const unsigned long long m = __ballot(active && hint >= 0 && hint < nr);
   // no branch: with no usable hint in the wave the stretch at 0 is fetched for nothing (see stage_issue on the wait counts)
   const int first = m ? __ffsll((long long)m) - 1 : 0;
   const int lo = __builtin_amdgcn_readlane(window_start(hint, nchunk), first);
   const int base = m ? lo : 0;
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // nobody still reads the stretch it replaces
-  stage_issue(ring, nr, base, stg, lane);
+  stage_issue<REC>(ring, nr, base, stg, lane, rec_off);
   return base;
 }
 
@@ -592,13 +653,17 @@ __device__ __forceinline__ double wave_min(double v) { return wave_reduce<OpMin>
 // contains every edge with a crossing not farther than the best one == search_ring_brute, bit for bit.
 // STAGED: the window is scanned from the wave's LDS stretch `stg` (staged_base = first vertex of what it holds now, -1 =
 // nothing yet); `ring` is then the global ring (slow path and re-staging).
-template <bool STAGED = false, bool ST = false, typename RingPtr, typename CirclePtr>
+// BRACKET (STAGED only; `bracket`: on at run time, wave-uniform): the stretches carry the windows' cone records (rec_off, see
+// stage_issue) and scan_window may take its bracket path.
+template <bool STAGED = false, bool ST = false, bool BRACKET = false, typename RingPtr, typename CirclePtr>
 __device__ __forceinline__ Hit search_ring_windowed(RingPtr ring, int nr, CirclePtr circ,
                                                     CirclePtr sep, int nchunk, bool active, int hint,
                                                     double px, double py, double dx, double dy,
                                                     double dlen, const double* cmax, bool skip_guard = false,
                                                     unsigned long long* stamps = nullptr,
-                                                    double2* stg = nullptr, int staged_base = -1) {
+                                                    double2* stg = nullptr, int staged_base = -1,
+                                                    bool bracket = false, int rec_off = 0) {
+  static_assert(!BRACKET || STAGED, "the bracket path reads the record a staged stretch carries");
   const int lane = threadIdx.x & (kWave - 1);
   Hit h{INFINITY, 0.0, kNoEdge};
   const bool windowed = active && hint >= 0 && hint < nr;
@@ -622,7 +687,10 @@ __device__ __forceinline__ Hit search_ring_windowed(RingPtr ring, int nr, Circle
         // bases are multiples of kChunk, so this only fails behind the seam of a ring whose length is not a multiple of
         // kChunk (off = lo - base + nr); such a lane is re-staged from its own window start (off = 0) below.
         if (todo && (off & (kChunk - 1)) == 0 && off + kWinEdges + 1 <= kStage) {
-          scan_window<kStageBatch, ST>(StagedWindow{stg + stage_slot(off)}, nr, 0, lo, px, py, dx, dy, h, cmax, stamps);
+          int bq = hint - lo;   // the hinted edge's position in its window: 8 .. 15, less behind the seam of a ring whose length is no multiple of kChunk
+          if (bq < 0) bq += nr;
+          scan_window<kStageBatch, ST, BRACKET>(StagedWindow{stg + stage_slot(off)}, nr, 0, lo, px, py, dx, dy, h, cmax, stamps,
+                                                bracket, bq);
           todo = false;
         }
       }
@@ -630,7 +698,7 @@ __device__ __forceinline__ Hit search_ring_windowed(RingPtr ring, int nr, Circle
       if (left == 0ull) break;
       base = __builtin_amdgcn_readlane(lo, __ffsll((long long)left) - 1);   // the first unserved lane's window start
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                     // nobody still reads the stretch it replaces
-      stage_issue(reinterpret_cast<const double2*>(ring), nr, base, stg, lane);
+      stage_issue<BRACKET>(reinterpret_cast<const double2*>(ring), nr, base, stg, lane, rec_off);
       stage_wait();
     }
   }

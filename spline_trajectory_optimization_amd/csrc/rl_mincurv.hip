@@ -141,7 +141,8 @@ SweepPlan plan_sweep(const rl_ctx* ctx, int n, int N, int nL, int nR, int B, boo
   // table's X, Y where the sweep keeps them (rl_sweep.hpp: sweep_keeps_table_xy)
   const size_t per_sample_arrays = rl::sweep_keeps_table_xy(joint, strict) ? 3 : 2;
   p.gscratch_doubles = (p.residency != Residency::Global ? 0 : per_sample_arrays * ((N + 1) & ~1) * (strict ? 2 : 1)) +
-                       (p.residency == Residency::Lds ? 0 : (size_t)2 * (nL + rl::kRingPad) + (size_t)2 * (nR + rl::kRingPad));
+                       (p.residency == Residency::Lds ? 0 : (size_t)2 * (nL + rl::kRingPad) + (size_t)2 * (nR + rl::kRingPad) +
+                                                            rl::sweep_cone_doubles(L.ncL, L.ncR));   // rings, and behind them their windows' cone records
   return p;
 }
 
@@ -396,6 +397,7 @@ int rl_ctx_set_option(rl_ctx* ctx, const char* name, int value) {
   else if (k == "qss_df_waves") { if (value != 1 && value != 2 && value != 4) return fail(RL_ERR_ARG, "qss_df_waves: 1, 2 or 4"); ctx->qss_df_waves = value; }
   else if (k == "qss_df_bail_at") { if (value < 0) return fail(RL_ERR_ARG, "qss_df_bail_at >= 0"); ctx->qss_df_bail_at = value; }
   else if (k == "qss_df_redo") { if (value != 0 && value != 1) return fail(RL_ERR_ARG, "qss_df_redo: 0 or 1"); ctx->qss_df_redo = value; }
+  else if (k == "sweep_bracket") { if (value != 0 && value != 1) return fail(RL_ERR_ARG, "sweep_bracket: 0 or 1"); ctx->sweep_bracket = value; }
   else if (k == "tables_search") { if (value < RL_SEARCH_BRUTE || value > RL_SEARCH_WINDOWED) return fail(RL_ERR_ARG, "tables_search: RL_SEARCH_BRUTE, _CULLED or _WINDOWED"); ctx->tables_search = value; }
   else if (k == "tables_rings") { if (value != 0 && value != 1) return fail(RL_ERR_ARG, "tables_rings: 0 (LDS where they fit) or 1 (arena)"); ctx->tables_rings_global = value; }
   else if (k == "frenet_search") { if (value != 0 && value != 1) return fail(RL_ERR_ARG, "frenet_search: 0 (table bound for every point) or 1 (from the previous point's piece)"); ctx->frenet_search = value; }
@@ -658,6 +660,7 @@ static int solve_batch_common(rl_ctx* ctx, const rl_track* trk, int form, const 
   a.max_iter = max_iter;
   for (int j = 0; j < max_iter && !i_start_rows; ++j) a.i_start[j] = i_start[j];
   a.ctrl0 = ctrl0; a.i_start_rows = i_start_rows;
+  a.bracket = ctx->sweep_bracket;
   a.search = search;
   a.max_dist = 100.0;  // race_track.py:104
 #ifdef RL_ABLATION
@@ -673,7 +676,7 @@ static int solve_batch_common(rl_ctx* ctx, const rl_track* trk, int form, const 
     size_t need = joint ? (size_t)max_iter * (size_t)(i_max - i_min) * (48 + 9 * rl::kJointRowsPerThread * 256 + 2 * n)
                         : (size_t)ninst * max_iter * 2 * (size_t)(i_max - i_min) * (rl::kSweepDumpHead + 2 * n);
 #ifdef RL_STAMPS
-    need = std::max(need, (size_t)B * 4 * 17);   // diagnostic build: per-wave phase stamps of every instance, [B][4][16], and behind them [B][4] prologue cycles
+    need = std::max(need, (size_t)B * 4 * 19);   // diagnostic build: per-wave phase stamps of every instance, [B][4][16], and behind them [B][4] prologue cycles, [B][4] window scans, [B][4] bracketed scans
 #endif
     a.dbg_instances = ninst;
     if (g_dbg_len < need) {

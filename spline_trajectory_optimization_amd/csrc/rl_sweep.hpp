@@ -43,6 +43,7 @@ struct SweepArgs {
   // per-instance start lines (SweepConfigFrom instantiations only; rl_mincurv_solve_batch_from_*)
   const double* ctrl0;     // null (the track's initial control points) or [B,n,2]: the line instance b starts from
   const int* i_start_rows; // null (i_start above, shared) or DEVICE [B,max_iter]: instance b's start indices, validated in the kernel
+  int bracket;             // sweep driver, rings in global: the window scan may take its bracket path (context option "sweep_bracket", default 1)
 };
 
 // In-kernel stamps (diagnostic build -DRL_STAMPS only, tools/stamp_sweep.py): where a wave's cycles go, per phase.
@@ -84,6 +85,9 @@ struct SweepLds {
 // alias's support re-sampled in that step.
 __host__ __device__ constexpr bool sweep_keeps_table_xy(bool joint, bool strict) { return strict && !joint; }
 constexpr int kSweepWaves = 4;   // waves of the sweep workgroup (the staged stretches are per wave)
+// cone records per ring in the instance's scratch: one per window start and the repeats that spare the pad lanes of a stretch a wrap
+constexpr int kConeRecExtra = kStage / kChunk;
+__host__ __device__ constexpr size_t sweep_cone_doubles(int ncL, int ncR) { return (size_t)2 * (ncL + kConeRecExtra) + (size_t)2 * (ncR + kConeRecExtra); }
 constexpr int kSweepThreads = kWave * kSweepWaves;
 // reference-order mode: the six cost terms of up to kTermChunk samples wait in LDS for their sequential summation
 // (6 x 256 doubles = 12 KB: inside the staged stretches' 13.8 KB, which are idle between two refreshes), and the
@@ -203,6 +207,11 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
   constexpr bool STRICT = Cfg::arith != Arith::Fast, RAISE = Cfg::arith == Arith::ReferenceRaise, LITE = Cfg::arith == Arith::Branch;
   constexpr bool STAGED = !RINGS_LDS;   // staged windows: rings in global memory
   constexpr bool FROM = Cfg::from;      // per-instance start line and start indices
+  // the stretches carry the windows' cone records (rl_cone.hpp) and scan_window may take its bracket path: the sweep driver's
+  // reference-order, raise and branch instantiations with the rings in global memory.  Not the fast arithmetic: its kernel has
+  // no register to spare (127 VGPRs, no spill -> 128 and 10 spilled with the path) and measured 0.07 ms SLOWER with it
+  // (7.76 -> 7.83 ms, profiles/sweep_monotone/bench_ab.json), where the reference-order kernel gains 0.17 ms.
+  constexpr bool BRACKET = STAGED && !JOINT && STRICT;
   if constexpr (RAISE) { if (!a.raise_flag || a.raise_flag[blockIdx.x] == 0) return; }
 #ifdef RL_STAMPS
   unsigned long long st_entry = 0;
@@ -343,8 +352,27 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
         (left ? sepL : sepR)[cc] = chunk_separation(left ? circL : circR, left ? L.ncL : L.ncR, cc, kNear, rmax);
       }
       __syncthreads();
+      if constexpr (BRACKET) {
+        // the cone records of both rings' windows, behind the rings in the instance's scratch (stage_issue: entry m belongs to
+        // the window that starts at chunk (m - 1) mod nchunk); visible to the DMA reads behind the barriers that follow
+        ConeRec* recs = reinterpret_cast<ConeRec*>(rR + nR + kRingPad);
+        const int mL = L.ncL + kConeRecExtra, mR = L.ncR + kConeRecExtra;
+        for (int m = tid; m < mL + mR; m += BLOCK) {
+          const bool left = m < mL;
+          const int nc = left ? L.ncL : L.ncR;
+          int cs = (left ? m : m - mL) - 1;
+          if (cs < 0) cs += nc;
+          if (cs >= nc) cs -= nc;
+          recs[m] = cone_record(const_cast<const double2*>(left ? rL : rR), left ? nL : nR, cs);
+        }
+        __syncthreads();
+      }
     }
   }
+  // cone records as stage_issue addresses them: double2 offsets from the ring's first vertex
+  const int recoL = BRACKET ? (nL + kRingPad) + (nR + kRingPad) : 0;
+  const int recoR = BRACKET ? (nR + kRingPad) + (L.ncL + kConeRecExtra) : 0;
+  const bool bracket = BRACKET && a.bracket != 0;
 
   // ---- joint (sliding-window) variant only: QP scratch and, per sample, whether the point lies
   // outside its own bound box.  joint_track_constraint (optimizer.py:129-159) has a row for EVERY
@@ -372,7 +400,7 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
   }
 
 #ifdef RL_STAMPS
-  unsigned long long st_cnt[4] = {0, 0, 0, 0};   // reference-order refresh: [0] window-scan cycles, [1] exact sign passes, [2] pass-2 rounds, [3] scans
+  unsigned long long st_cnt[5] = {0, 0, 0, 0, 0};   // reference-order refresh: [0] window-scan cycles, [1] exact sign passes, [2] pass-2 rounds, [3] scans, [4] scans that took the bracket
   unsigned long long st_fine[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sf0 = 0, sf1 = 0;   // inside the refresh: evaluation, left ring, right ring, stores
 #endif
   // refresh(i0,i1,j0,j1): new p, normal and closest ring crossings for the samples of two ranges
@@ -456,8 +484,8 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
           int baseL = -1, baseR = -1;
           auto prefetch = [&]() {
             if constexpr (STAGED) {
-              baseL = stage_prefetch(reinterpret_cast<const double2*>(rL), nL, L.ncL, active, (int)hints[i], stgL, lane);
-              baseR = stage_prefetch(reinterpret_cast<const double2*>(rR), nR, L.ncR, active, (int)hints[Npad + i], stgR, lane);
+              baseL = stage_prefetch<BRACKET>(reinterpret_cast<const double2*>(rL), nL, L.ncL, active, (int)hints[i], stgL, lane, recoL);
+              baseR = stage_prefetch<BRACKET>(reinterpret_cast<const double2*>(rR), nR, L.ncR, active, (int)hints[Npad + i], stgR, lane, recoR);
             }
           };
           if (from_base) {
@@ -473,11 +501,11 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
           RL_FSTAMP(0);
           const double dLx = a.max_dist * hd.cl, dLy = a.max_dist * hd.sl;   // trajectory.py:87-88, norm = +pi/2
           const double dRx = a.max_dist * hd.cr, dRy = a.max_dist * hd.sr;   //                      norm = -pi/2
-          const Hit hl = search_ring_windowed<STAGED, true>(rL, nL, circL, sepL, L.ncL, active, (int)hints[i], px, py,
-                                                            dLx, dLy, a.max_dist, cmax, false, RL_STRICT_COUNTS, stgL, baseL);
+          const Hit hl = search_ring_windowed<STAGED, true, BRACKET>(rL, nL, circL, sepL, L.ncL, active, (int)hints[i], px, py,
+                                                            dLx, dLy, a.max_dist, cmax, false, RL_STRICT_COUNTS, stgL, baseL, bracket, recoL);
           RL_FSTAMP(1);
-          const Hit hr = search_ring_windowed<STAGED, true>(rR, nR, circR, sepR, L.ncR, active, (int)hints[Npad + i], px, py,
-                                                            dRx, dRy, a.max_dist, cmax, false, RL_STRICT_COUNTS, stgR, baseR);
+          const Hit hr = search_ring_windowed<STAGED, true, BRACKET>(rR, nR, circR, sepR, L.ncR, active, (int)hints[Npad + i], px, py,
+                                                            dRx, dRy, a.max_dist, cmax, false, RL_STRICT_COUNTS, stgR, baseR, bracket, recoR);
           RL_FSTAMP(2);
           if (active) {   // no crossing: best_s = 0, the waypoint itself (trajectory.py:127)
             const double2 Lp = make_double2(uf_madd(px, hl.best_s, dLx), uf_madd(py, hl.best_s, dLy));
@@ -538,8 +566,8 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
 #endif
         int baseL = -1, baseR = -1;
         if constexpr (STAGED) {   // both stretches are on their way while the point is evaluated
-          baseL = stage_prefetch(reinterpret_cast<const double2*>(rL), nL, L.ncL, active, (int)hints[i], stgL, lane);
-          baseR = stage_prefetch(reinterpret_cast<const double2*>(rR), nR, L.ncR, active, (int)hints[Npad + i], stgR, lane);
+          baseL = stage_prefetch<BRACKET>(reinterpret_cast<const double2*>(rL), nL, L.ncL, active, (int)hints[i], stgL, lane, recoL);
+          baseR = stage_prefetch<BRACKET>(reinterpret_cast<const double2*>(rR), nR, L.ncR, active, (int)hints[Npad + i], stgR, lane, recoR);
         }
         CurvePoint<K, 1> c;
         eval_sample<K, 1>(tr, cx, cy, i, l, c);
@@ -548,19 +576,19 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
         RL_FSTAMP(0);
         const bool skip = RL_ABLATE(a, 2);
 #ifdef RL_STAMPS
-        unsigned long long ws[2] = {0, 0};
-        const Hit hl = search_ring_windowed<STAGED>(rL, nL, circL, sepL, L.ncL, active, (int)hints[i], c.x, c.y,
-                                                    dx, dy, a.max_dist, cmax, skip, ws, stgL, baseL);
+        unsigned long long ws[5] = {0, 0, 0, 0, 0};   // [0] window-scan cycles; scan_window counts in [1..4]
+        const Hit hl = search_ring_windowed<STAGED, false, BRACKET>(rL, nL, circL, sepL, L.ncL, active, (int)hints[i], c.x, c.y,
+                                                    dx, dy, a.max_dist, cmax, skip, ws, stgL, baseL, bracket, recoL);
         RL_FSTAMP(1);
-        const Hit hr = search_ring_windowed<STAGED>(rR, nR, circR, sepR, L.ncR, active, (int)hints[Npad + i], c.x,
-                                                    c.y, -dx, -dy, a.max_dist, cmax, skip, ws, stgR, baseR);  // yaw - pi/2
+        const Hit hr = search_ring_windowed<STAGED, false, BRACKET>(rR, nR, circR, sepR, L.ncR, active, (int)hints[Npad + i], c.x,
+                                                    c.y, -dx, -dy, a.max_dist, cmax, skip, ws, stgR, baseR, bracket, recoR);  // yaw - pi/2
         RL_FSTAMP(2);
-        st_fine[4] += ws[0];
+        st_fine[4] += ws[0]; st_cnt[3] += ws[3]; st_cnt[4] += ws[4];
 #else
-        const Hit hl = search_ring_windowed<STAGED>(rL, nL, circL, sepL, L.ncL, active, (int)hints[i], c.x, c.y,
-                                                    dx, dy, a.max_dist, cmax, skip, nullptr, stgL, baseL);
-        const Hit hr = search_ring_windowed<STAGED>(rR, nR, circR, sepR, L.ncR, active, (int)hints[Npad + i], c.x,
-                                                    c.y, -dx, -dy, a.max_dist, cmax, skip, nullptr, stgR, baseR);  // yaw - pi/2
+        const Hit hl = search_ring_windowed<STAGED, false, BRACKET>(rL, nL, circL, sepL, L.ncL, active, (int)hints[i], c.x, c.y,
+                                                    dx, dy, a.max_dist, cmax, skip, nullptr, stgL, baseL, bracket, recoL);
+        const Hit hr = search_ring_windowed<STAGED, false, BRACKET>(rR, nR, circR, sepR, L.ncR, active, (int)hints[Npad + i], c.x,
+                                                    c.y, -dx, -dy, a.max_dist, cmax, skip, nullptr, stgR, baseR, bracket, recoR);  // yaw - pi/2
 #endif
         if (active) {
           sL[i] = hl.best_s;
@@ -1824,6 +1852,8 @@ __global__ __launch_bounds__(kSweepThreads, Cfg::workgroups_per_cu) void k_sweep
     if constexpr (STRICT) { o[11] = (double)st_cnt[3]; o[12] = (double)st_cnt[2]; o[14] = (double)st_cnt[1]; }   // scans, pass-2 rounds, exact sign passes (slot 14 otherwise: tiles that took the full heading)
     o[6] = (double)(st_t1 - st_begin);
     a.dbg[(size_t)a.B * NW * 16 + (size_t)b * NW + wave] = (double)(st_begin - st_entry);   // the prologue: entry -> first step
+    a.dbg[(size_t)a.B * NW * 17 + (size_t)b * NW + wave] = (double)st_cnt[3];               // window scans, and those that took the bracket
+    a.dbg[(size_t)a.B * NW * 18 + (size_t)b * NW + wave] = (double)st_cnt[4];
     {   // where the wave ran: HW_ID (wave slot, SIMD, CU, shader array, shader engine) and the XCC
       unsigned hw, xcc;
       asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));

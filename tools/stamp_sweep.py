@@ -22,10 +22,13 @@ lib = _lib.load()
 _lib.check(lib.rl_debug_dump_enable(1))
 for _ in range(2):
     out = ops.solve_batch_host(trk, _lib.BOUNDS_WIDTHS, W, ist, arith=ARITH)
-buf = np.zeros(B * 4 * 17)
-_lib.check(lib.rl_debug_read(buf.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(buf)))
+buf = np.zeros(B * 4 * 19)   # [B][4][16] stamps, [B][4] prologue cycles, [B][4] window scans, [B][4] scans that took the bracket
+have_scans = lib.rl_debug_read(buf.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(buf)) == 0
+if not have_scans:   # a library from before the bracket path: 17 values per wave
+    buf = np.zeros(B * 4 * 17)
+    _lib.check(lib.rl_debug_read(buf.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(buf)))
 s = buf[:B * 4 * 16].reshape(B, 4, 16)
-pro = buf[B * 4 * 16:].reshape(B, 4)   # kernel entry -> first step: rings, chunk circles, separation pass, first fill
+pro = buf[B * 4 * 16:B * 4 * 17].reshape(B, 4)   # kernel entry -> first step: rings, chunk circles, separation pass, first fill
 tot = s[:, :, 6]
 names = ["phase 1 (cost + constraints + reductions)", "barrier A", "phase 2 (QP, wave 0)", "barrier B", "phase 3 (refresh)", "barrier C"]
 res = {"kernel_ms": out[4].kernel_ms, "B": B, "arith": ARITH, "cycles_per_wave_mean": float(tot.mean())}
@@ -44,4 +47,8 @@ if ARITH == 1:   # reference-order loop: slots 0 terms, 1 barrier, 2 in-order su
     res["note"] = "reference-order loop: phase 1 = cost terms and rows; phase 2 = the six in-order sums (wave 0) + QP + derivative window"
     res["refresh: heading (inside evaluation)"] = {"share_wave0": float((s[:, 0, 13] / tot[:, 0]).mean()), "cycles_per_step_wave0": float(s[:, 0, 13].mean() / 610)}
     res["tiles that took the full heading, per instance (all waves)"] = float(s[:, :, 14].sum(axis=1).mean())
+if have_scans:
+    scans, brk = buf[B * 4 * 17:B * 4 * 18].sum(), buf[B * 4 * 18:].sum()
+    res["window scans (wave level), whole batch"] = float(scans)
+    res["  of those: took the bracket (four vertices instead of 25)"] = {"count": float(brk), "share": float(brk / max(scans, 1.0))}
 print(json.dumps(res, indent=1))

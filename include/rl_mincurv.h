@@ -206,6 +206,14 @@ int rl_track_set_length(rl_track* trk, double length);
 int rl_mincurv_cost(rl_ctx* ctx, const rl_track* trk, const int* idx, int n_idx, const double* z,
                     double* H, double* g, int* M);
 
+/* The same with a weight per SAMPLE in the cost: the reference's `v` (optimization/optimizer.py:71-76 with line 71 active --
+ * the reference itself runs with v = 1), which multiplies the numerators of Pxx, Pxy and Pyy.  weights is HOST [N], one per
+ * sample index as SPEED is in the table; every weight finite and within [2^-30, 2^30], else RL_ERR_ARG (as for a NULL).
+ * In the context's arithmetic: reference-order = the reference's expression in numpy's order, (dTy*dTy)*v, ((-2*dTx)*dTy)*v,
+ * (dTx*dTx)*v, each divided by denom, summed in sample order; weights of 1 give the bits of rl_mincurv_cost. */
+int rl_mincurv_cost_weighted(rl_ctx* ctx, const rl_track* trk, const int* idx, int n_idx, const double* z,
+                             const double* weights, double* H, double* g, int* M);
+
 /* ---- a8: TrajectoryOptimizer.track_constraint  (optimization/optimizer.py:222-254)
  * points [N,19] supplies X,Y and the four bound columns.  Outputs for ONE control point:
  * b[M] (the non-zero of A rows 2i and 2i+1: A[2i,0] = A[2i+1,1] = b_i), lba[2M], uba[2M]. */

@@ -13,6 +13,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RL_LIB_PATH") or os.path.join(_PKG, "librl_mincurv.so")  # RL_LIB_PATH: dev hook for A/B builds
 
 NCOL = 19
+WEIGHT_MIN, WEIGHT_MAX = 2.0 ** -30, 2.0 ** 30   # include/rl_mincurv.h: rl_mincurv_cost_weighted's allowed weights
 MAX_ITER = 32
 BOUNDS_SHARED_RINGS, BOUNDS_WIDTHS, BOUNDS_POINTS = 0, 1, 2
 SEARCH_BRUTE, SEARCH_CULLED, SEARCH_WINDOWED = 0, 1, 2
@@ -64,6 +65,7 @@ _SIGNATURES = {
     "rl_track_set_control_points": (ctypes.c_int, [_vp, _dp, _dp]),
     "rl_track_set_length": (ctypes.c_int, [_vp, ctypes.c_double]),
     "rl_mincurv_cost": (ctypes.c_int, [_vp, _vp, _ip, ctypes.c_int, _dp, _dp, _dp, _ip]),
+    "rl_mincurv_cost_weighted": (ctypes.c_int, [_vp, _vp, _ip, ctypes.c_int, _dp, _dp, _dp, _dp, _ip]),
     "rl_track_constraint": (ctypes.c_int, [_vp, _vp, _dp, ctypes.c_int, _dp, _dp, _dp, _ip]),
     "rl_mincurv_sweep": (ctypes.c_int, [_vp, _vp, _ip, ctypes.c_int, _dp, _dp, _dp, _ip,
                                         ctypes.POINTER(Stats)]),

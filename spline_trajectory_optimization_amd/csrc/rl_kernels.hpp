@@ -333,15 +333,19 @@ __global__ void k_fill_bounds(double* __restrict__ points, int N, const double2*
 struct CostAcc {
   double hxx, hyy, fx_pxx_b, fy_pxy_b, fy_pyy_b, b_pxy_fx;
 };
+// WEIGHTED: v of optimizer.py:71-76 multiplies the three numerators (v = 1: the bits of the unweighted terms)
+template <bool WEIGHTED = false>
 __device__ __forceinline__ void cost_terms(double dx, double dy, double d2x, double d2y, double B,
-                                           double zx, double zy, CostAcc& a) {
+                                           double zx, double zy, CostAcc& a, double v = 1.0) {
   const double Fx = d2x - B * zx;
   const double Fy = d2y - B * zy;
   const double s2 = dx * dx + dy * dy;
   const double denom = s2 * s2 * s2;
-  const double Pxx = (dy * dy) / denom;
-  const double Pxy = (-2.0 * dx * dy) / denom;
-  const double Pyy = (dx * dx) / denom;
+  double nxx = dy * dy, nxy = -2.0 * dx * dy, nyy = dx * dx;
+  if constexpr (WEIGHTED) { nxx *= v; nxy *= v; nyy *= v; }
+  const double Pxx = nxx / denom;
+  const double Pxy = nxy / denom;
+  const double Pyy = nyy / denom;
   a.hxx += B * Pxx * B;
   a.hyy += B * Pyy * B;
   a.fx_pxx_b += Fx * Pxx * B;
@@ -351,14 +355,14 @@ __device__ __forceinline__ void cost_terms(double dx, double dy, double d2x, dou
 }
 
 // a7: one workgroup (256 threads) per requested control point
-template <int K>
-__global__ __launch_bounds__(256) void k_cost(TrackDev tr, const double* __restrict__ cx,
-                                              const double* __restrict__ cy,
-                                              const int* __restrict__ idxs,
-                                              const double* __restrict__ z,
-                                              double* __restrict__ H, double* __restrict__ g,
-                                              int* __restrict__ Mout) {
-  __shared__ double red[6][4];
+template <int K, bool WEIGHTED>
+__device__ __forceinline__ void cost_body(const TrackDev& tr, const double* __restrict__ cx,
+                                          const double* __restrict__ cy,
+                                          const int* __restrict__ idxs,
+                                          const double* __restrict__ z,
+                                          const double* __restrict__ weights,   // WEIGHTED: [N], per sample
+                                          double* __restrict__ H, double* __restrict__ g,
+                                          int* __restrict__ Mout, double (*red)[4]) {
   const int q = blockIdx.x;
   const int idx = idxs[q];
   const int s0 = tr.sup[2 * idx], s1 = tr.sup[2 * idx + 1];
@@ -371,7 +375,8 @@ __global__ __launch_bounds__(256) void k_cost(TrackDev tr, const double* __restr
     CurvePoint<K, 2> c;
     eval_sample<K, 2>(tr, cx, cy, i, l, c);
     const double B = D2[(size_t)(idx - l + K) * tr.N + i];
-    cost_terms(c.dx, c.dy, c.d2x, c.d2y, B, zx, zy, acc);
+    if constexpr (WEIGHTED) cost_terms<true>(c.dx, c.dy, c.d2x, c.d2y, B, zx, zy, acc, weights[i]);
+    else cost_terms(c.dx, c.dy, c.d2x, c.d2y, B, zx, zy, acc);
   }
   double v[6] = {acc.hxx, acc.hyy, acc.fx_pxx_b, acc.fy_pxy_b, acc.fy_pyy_b, acc.b_pxy_fx};
   const int w = threadIdx.x / kWave, lane = threadIdx.x % kWave;
@@ -389,6 +394,28 @@ __global__ __launch_bounds__(256) void k_cost(TrackDev tr, const double* __restr
     g[2 * q + 1] = (s[3] + s[4]) + (s[5] + s[4]);
     if (Mout) Mout[q] = s1 - s0;
   }
+}
+template <int K>
+__global__ __launch_bounds__(256) void k_cost(TrackDev tr, const double* __restrict__ cx,
+                                              const double* __restrict__ cy,
+                                              const int* __restrict__ idxs,
+                                              const double* __restrict__ z,
+                                              double* __restrict__ H, double* __restrict__ g,
+                                              int* __restrict__ Mout) {
+  __shared__ double red[6][4];
+  cost_body<K, false>(tr, cx, cy, idxs, z, nullptr, H, g, Mout, red);
+}
+// the same with a weight per sample (rl_mincurv_cost_weighted)
+template <int K>
+__global__ __launch_bounds__(256) void k_cost_weighted(TrackDev tr, const double* __restrict__ cx,
+                                                       const double* __restrict__ cy,
+                                                       const int* __restrict__ idxs,
+                                                       const double* __restrict__ z,
+                                                       const double* __restrict__ weights,
+                                                       double* __restrict__ H, double* __restrict__ g,
+                                                       int* __restrict__ Mout) {
+  __shared__ double red[6][4];
+  cost_body<K, true>(tr, cx, cy, idxs, z, weights, H, g, Mout, red);
 }
 
 // a8: one workgroup for one control point; reads X,Y and the bound columns from `points`
@@ -435,11 +462,16 @@ __device__ __forceinline__ double quotient_by_chain(double n, double d, double r
 }
 __device__ __forceinline__ bool plain_operand(double v) { return fabs(v) >= 0x1p-300 && fabs(v) <= 0x1p+300; }
 
+constexpr double kWeightMin = 0x1p-30, kWeightMax = 0x1p+30;   // allowed per-sample cost weights (rl_mincurv_cost_weighted)
 __device__ __forceinline__ void cost_quotients(double dTx, double dTy, double s2, double denom, double nxx, double nxy,
                                                double nyy, double& Pxx, double& Pxy, double& Pyy) {
 #pragma clang fp contract(off)
   // plain range: 2^-90 <= s2 <= 2^90  =>  denom = s2^3 within 2^+-270, numerators <= 2 s2; both tangent components >= 2^-100
-  // in magnitude  =>  numerators >= 2^-200: no operand near an end of the exponent range, no zero
+  // in magnitude  =>  numerators >= 2^-200: no operand near an end of the exponent range, no zero.
+  // Weighted callers pass numerators scaled by a weight in [kWeightMin, kWeightMax] = [2^-30, 2^30] (checked on the host before
+  // the launch): numerators within [2^-230, 2^121], quotients within [2^-500, 2^391], the reciprocal within 2^+-270 --
+  // v_div_scale stays idle (no operand below 2^-969, exponents of numerator and denominator less than 768 apart, no quotient or
+  // reciprocal near the denormals) and v_div_fixup has nothing to fix: the predicate below holds for them unchanged.
   const bool plain = s2 >= 0x1p-90 && s2 <= 0x1p+90 && fmin(fabs(dTx), fabs(dTy)) >= 0x1p-100;
   if (__all(plain)) {
     double r = __builtin_amdgcn_rcp(denom);
@@ -507,6 +539,87 @@ __global__ __launch_bounds__(256) void k_cost_strict(TrackDev tr, const double* 
       const double denom = s2 * s2 * s2;
       double Pxx, Pxy, Pyy;
       cost_quotients(dTx, dTy, s2, denom, dTy * dTy, -2.0 * dTx * dTy, dTx * dTx, Pxx, Pxy, Pyy);
+      double* tp = terms + tid;
+      tp[0] = B2 * Pxx * B2;
+      tp[kTermStrideA] = B2 * Pyy * B2;
+      tp[2 * kTermStrideA] = Fx * Pxx * B2;
+      tp[3 * kTermStrideA] = Fy * Pxy * B2;
+      tp[4 * kTermStrideA] = Fy * Pyy * B2;
+      tp[5 * kTermStrideA] = B2 * Pxy * Fx;
+    }
+    __syncthreads();
+    if (wave == 0 && lane < 6) {
+      const int cnt = min(kTermChunkA, M - ch * kTermChunkA);
+      const double* tp = terms + lane * kTermStrideA;
+      for (int u = 0; u < cnt; ++u) sacc += tp[u];
+    }
+    __syncthreads();
+  }
+  if (wave == 0) {
+    auto lane_val = [&](int src) {
+      return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(sacc), src), __builtin_amdgcn_readlane(__double2loint(sacc), src));
+    };
+    const double t0 = lane_val(0), t1 = lane_val(1), t2 = lane_val(2), t3 = lane_val(3), t4 = lane_val(4), t5 = lane_val(5);
+    if (tid == 0) {
+      H[4 * q + 0] = 2.0 * t0; H[4 * q + 1] = 0.0; H[4 * q + 2] = 0.0; H[4 * q + 3] = 2.0 * t1;
+      g[2 * q + 0] = t2 + t2;
+      g[2 * q + 1] = (t3 + t4) + (t5 + t4);
+      if (Mout) Mout[q] = M;
+    }
+  }
+}
+
+// The same with a weight per sample (rl_mincurv_cost_weighted in the reference-order arithmetic).  A kernel of its own, written
+// out: k_cost_strict above keeps the code, and so the registers, it always had (sharing one inlined body moved its SGPR count).
+template <int K>
+__global__ __launch_bounds__(256) void k_cost_strict_weighted(TrackDev tr, const double* __restrict__ cx,
+                                                     const double* __restrict__ cy, const int* __restrict__ idxs,
+                                                     const double* __restrict__ z, const double* __restrict__ weights,
+                                                     double* __restrict__ H, double* __restrict__ g, int* __restrict__ Mout) {
+  __shared__ double terms[6 * kTermStrideA];
+  __shared__ double c12[8 * K];
+  using SR = StrictRows<K>;
+  const int q = blockIdx.x, tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  const int idx = idxs[q], n = tr.n, N = tr.N;
+  const int s0 = tr.sup[2 * idx], s1 = tr.sup[2 * idx + 1];
+  const double zx = z ? z[2 * q] : cx[idx], zy = z ? z[2 * q + 1] : cy[idx];
+  const double* __restrict__ Ds = tr.Ds;
+  if (wave == 0) {   // splder coefficients c1[j], c2[j] for j = idx-K .. idx+K-1 (x: lanes 0.., y: lanes 32..)
+    const int w = lane & 31;
+    const double* cc = lane < 32 ? cx : cy;
+    const int j = idx - K + w;
+    double c1 = 0.0, c2 = 0.0;
+    if (w < 2 * K && j >= 0 && j + 1 <= n - 1) {
+#pragma clang fp contract(off)
+      c1 = (cc[j + 1] - cc[j]) * (double)K / (tr.t[j + K + 1] - tr.t[j + 1]);
+    }
+    const double c1n = __shfl_down(c1, 1, kWave);
+    if (w < 2 * K - 1 && j >= 0 && j + 2 <= n - 1) {
+#pragma clang fp contract(off)
+      c2 = (c1n - c1) * (double)(K - 1) / (tr.t[j + K + 1] - tr.t[j + 2]);
+    }
+    if (w < 2 * K) { c12[(lane < 32 ? 0 : 2 * K) + w] = c1; c12[4 * K + (lane < 32 ? 0 : 2 * K) + w] = c2; }
+  }
+  __syncthreads();
+  const int M = s1 - s0, nchunks = (M + kTermChunkA - 1) / kTermChunkA;
+  double sacc = 0.0;
+  for (int ch = 0; ch < nchunks; ++ch) {
+    const int i = s0 + ch * kTermChunkA + tid;
+    if (i < s1) {
+#pragma clang fp contract(off)
+      const int l = tr.ell[i];
+      const int wofs = l - idx;
+      const double dTx = seq_dot<K>(c12 + wofs, Ds + (size_t)SR::E1 * N, N, i);
+      const double dTy = seq_dot<K>(c12 + 2 * K + wofs, Ds + (size_t)SR::E1 * N, N, i);
+      const double d2Tx = seq_dot<K - 1>(c12 + 4 * K + wofs, Ds + (size_t)SR::E2 * N, N, i);
+      const double d2Ty = seq_dot<K - 1>(c12 + 6 * K + wofs, Ds + (size_t)SR::E2 * N, N, i);
+      const double B2 = Ds[(size_t)(SR::D2 + idx - l + K) * N + i];
+      const double Fx = d2Tx - B2 * zx, Fy = d2Ty - B2 * zy;
+      const double s2 = dTx * dTx + dTy * dTy;
+      const double denom = s2 * s2 * s2;
+      double Pxx, Pxy, Pyy;
+      const double w = weights[i];   // optimizer.py:71-76, numpy's order: (numerator * v) / denom
+      cost_quotients(dTx, dTy, s2, denom, (dTy * dTy) * w, ((-2.0 * dTx) * dTy) * w, (dTx * dTx) * w, Pxx, Pxy, Pyy);
       double* tp = terms + tid;
       tp[0] = B2 * Pxx * B2;
       tp[kTermStrideA] = B2 * Pyy * B2;

@@ -579,6 +579,38 @@ int rl_mincurv_cost(rl_ctx* ctx, const rl_track* trk, const int* idx, int n_idx,
   return sg.finish();
 }
 
+// host weights of the weighted cost: finite, positive, within [2^-30, 2^30] (rl_kernels.hpp: kWeightMin / kWeightMax)
+static bool weights_ok(const double* w, size_t count) {
+  for (size_t i = 0; i < count; ++i)
+    if (!(w[i] >= rl::kWeightMin && w[i] <= rl::kWeightMax)) return false;   // NaN fails both comparisons
+  return true;
+}
+
+int rl_mincurv_cost_weighted(rl_ctx* ctx, const rl_track* trk, const int* idx, int n_idx, const double* z, const double* weights,
+                             double* H, double* g, int* M) {
+  if (!ctx || !trk || !idx || !weights || !H || !g) return fail(RL_ERR_ARG, "null argument");
+  if (n_idx <= 0) return fail(RL_ERR_ARG, "n_idx <= 0");
+  for (int q = 0; q < n_idx; ++q)
+    if (idx[q] < 0 || idx[q] >= trk->n) return fail(RL_ERR_ARG, "control point index out of range");
+  if (!weights_ok(weights, trk->N)) return fail(RL_ERR_ARG, "weights must be finite and within [2^-30, 2^30]");
+  const bool strict = ctx->arith == RL_ARITH_REFERENCE && trk->k == 5;
+  Staging sg(ctx);
+  const int* didx = sg.in(idx, n_idx);
+  const double* dz = sg.in(z, (size_t)2 * n_idx);
+  const double* dw = sg.in(weights, trk->N);
+  double *dH = sg.out(H, (size_t)4 * n_idx), *dg = sg.out(g, (size_t)2 * n_idx);
+  int* dM = sg.out_optional(M, n_idx);
+  sg.run([&] {
+    if (strict) if (int rc = ensure_strict_tables(ctx, trk)) return rc;
+    const rl::TrackDev td = trk->dev();
+    const double *cx = trk->c0.p, *cy = trk->c0.p + trk->n;
+    const dim3 grid(n_idx), block(256);
+    if (strict) return launch(ctx, rl::k_cost_strict_weighted<5>, grid, block, 0, td, cx, cy, didx, dz, dw, dH, dg, dM);
+    return by_degree(trk->k, [&](auto kc) { return launch(ctx, rl::k_cost_weighted<RL_DEGREE(kc)>, grid, block, 0, td, cx, cy, didx, dz, dw, dH, dg, dM); });
+  });
+  return sg.finish();
+}
+
 int rl_track_constraint(rl_ctx* ctx, const rl_track* trk, const double* points, int idx,
                         double* b, double* lba, double* uba, int* M) {
   if (!ctx || !trk || !points || !b || !lba || !uba || !M) return fail(RL_ERR_ARG, "null argument");

@@ -97,9 +97,22 @@ def region_index_torch(xy, regions, out=None):
     return out
 
 
-def mincurv_cost(track, idx, z=None):
+def _check_weights(weights, N):
+    """Host weights of the weighted cost: float64 [N], finite and within [_lib.WEIGHT_MIN, _lib.WEIGHT_MAX]."""
+    weights = np.ascontiguousarray(weights, dtype=np.float64)
+    if weights.shape != (N,):
+        raise ValueError(f"weights: expected shape [{N}], got {list(weights.shape)}")
+    if not np.all((weights >= _lib.WEIGHT_MIN) & (weights <= _lib.WEIGHT_MAX)):   # NaN fails both
+        raise ValueError("weights: every weight must be finite and within [2**-30, 2**30]")
+    return weights
+
+
+def mincurv_cost(track, idx, z=None, weights=None):
     """TrajectoryOptimizer.min_curvature_cost for several control points at once
-    (optimization/optimizer.py:24-86).  Returns H [n_idx,2,2], g [n_idx,2], M [n_idx]."""
+    (optimization/optimizer.py:24-86).  weights: None, or [N] per-sample weights, the reference's `v` of optimizer.py:71-76
+    (rl_mincurv_cost_weighted).  Returns H [n_idx,2,2], g [n_idx,2], M [n_idx]."""
+    if weights is not None:
+        weights = _check_weights(weights, track.N)
     ctx = track.ctx
     idx, ip = as_i(np.atleast_1d(idx))
     n_idx = len(idx)
@@ -108,6 +121,10 @@ def mincurv_cost(track, idx, z=None):
         z, zp = as_d(np.asarray(z).reshape(n_idx, 2))
     else:
         zp = None
+    if weights is not None:
+        check(ctx.lib.rl_mincurv_cost_weighted(ctx.h, track.h, ip, n_idx, zp, weights.ctypes.data_as(_dp),
+                                               H.ctypes.data_as(_dp), g.ctypes.data_as(_dp), M.ctypes.data_as(_ip)))
+        return H.reshape(n_idx, 2, 2), g, M
     check(ctx.lib.rl_mincurv_cost(ctx.h, track.h, ip, n_idx, zp, H.ctypes.data_as(_dp),
                                   g.ctypes.data_as(_dp), M.ctypes.data_as(_ip)))
     return H.reshape(n_idx, 2, 2), g, M

@@ -10,6 +10,9 @@ Differences from the reference, all additive and keyword-only:
   * the per-iteration `Simulator.run_simulation` calls (optimizer.py:333-339) never feed back
     into the returned spline (they only rewrite SPEED/ACC/TIME columns of a table that is
     discarded); they are skipped unless `simulate=True`.
+  * `min_curvature_cost(..., weights=)` activates the per-sample weight the reference carries but never uses
+    (optimizer.py:71-72: `# v = 1/traj_d[t_mask, Trajectory.SPEED]`, `v = np.ones(M)`); `speed_weights(traj_d)` forms
+    1 / SPEED of a simulated table.  The sweep itself still runs with v = 1, as the reference does.
   * the matplotlib visualiser (optimizer.py:261, 331-340) is not constructed.
   * ARITHMETIC.  This class is the drop-in for the reference's, so by default it answers in the REFERENCE-ORDER arithmetic
     (`TrajectoryOptimizer.arith = _lib.ARITH_REFERENCE`: the reference's operations in numpy's / scipy's order, the CPU oracle's
@@ -63,12 +66,22 @@ class TrajectoryOptimizer:
             trk.set_control_points(cx, cy)
         return trk
 
-    def min_curvature_cost(self, z: np.ndarray, idx: int, traj_s: BSplineTrajectory, traj_d: Trajectory):
-        """optimizer.py:24-86 -> k_cost.  Returns H (2x2), g (2)."""
+    def min_curvature_cost(self, z: np.ndarray, idx: int, traj_s: BSplineTrajectory, traj_d: Trajectory, *, weights=None):
+        """optimizer.py:24-86 -> k_cost.  Returns H (2x2), g (2).  weights: None (v = 1, the reference) or one weight per
+        sample of traj_d, the `v` of optimizer.py:71-76 (line 71 active: weights = 1 / traj_d[:, Trajectory.SPEED])."""
         trk = self._device_track(traj_s, len(traj_d))
         with self._scope(traj_s._spl_x.k):
-            H, g, _ = ops.mincurv_cost(trk, [idx], z=np.asarray(z, dtype=np.float64).reshape(1, 2))
+            H, g, _ = ops.mincurv_cost(trk, [idx], z=np.asarray(z, dtype=np.float64).reshape(1, 2), weights=weights)
         return H[0], g[0]
+
+    @staticmethod
+    def speed_weights(traj_d: Trajectory):
+        """w = 1 / traj_d[:, SPEED] (optimizer.py:71), ValueError unless every speed is finite and positive (a table fresh from
+        sample_along holds zeros: simulate it first)."""
+        v = np.asarray(traj_d[:, Trajectory.SPEED], dtype=np.float64)
+        if not (np.all(np.isfinite(v)) and np.all(v > 0.0)):
+            raise ValueError("speed_weighted: the SPEED column must be finite and positive (run the simulator on the table first)")
+        return 1.0 / v
 
     def joint_min_curvature_cost(self, traj_s: BSplineTrajectory, traj_d: Trajectory, start_idx=None, span=None):
         """optimizer.py:88-110: the 2x2 blocks of the window's control points on the diagonal."""

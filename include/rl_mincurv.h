@@ -469,6 +469,23 @@ int rl_mintime_solve_batch_dev(rl_ctx* ctx, const double* model, int B, int N, c
                                const double* left, const double* right, int bounds_per_instance, double margin,
                                double track_length, double average_track_width, double speed_cap, double* X, double* U,
                                double* T, int max_iter, double tol, double* stats);
+/* One VEHICLE per instance: the two entries above with `model` replaced by
+ *   models [B, RL_DT_NPARAM], a HOST array in both (as `model` is), row b = the model of instance b
+ * -- lap time against mass, grip, power, brake force or steering limit as ONE batched solve.  Every row is checked
+ * (finite; Fd_max, |Fb_max|, delta_max, mass, Pmax, mu, Td, Tb, Tdelta > 0; RL_ERR_ARG names the first bad instance,
+ * nothing is launched); the variable scaling of instance b uses ITS Fd_max, |Fb_max|, delta_max and mass, with the
+ * expressions of the shared-model entries, so B equal rows give the bits of the shared-model call.  margin,
+ * average_track_width, speed_cap, s and kappa stay shared (vehicles of different widths: fold each margin into
+ * left / right and pass margin = 0); bounds_per_instance, the sub-batches and the polling of the host entry are
+ * unchanged.  The models reach the kernels as one table row per instance in the context's scratch. */
+int rl_mintime_solve_vehicles(rl_ctx* ctx, const double* models, int B, int N, const double* s, const double* kappa,
+                              const double* left, const double* right, int bounds_per_instance, double margin,
+                              double track_length, double average_track_width, double speed_cap, double* X, double* U,
+                              double* T, int max_iter, double tol, double* stats);
+int rl_mintime_solve_vehicles_dev(rl_ctx* ctx, const double* models, int B, int N, const double* s, const double* kappa,
+                                  const double* left, const double* right, int bounds_per_instance, double margin,
+                                  double track_length, double average_track_width, double speed_cap, double* X, double* U,
+                                  double* T, int max_iter, double tol, double* stats);
 
 /* ---- the bicycle min-time NLP of set_up_bicycle_problem (min_time_optm/min_time_optimizer.py:14-90; models/
  * dynamic_bicycle.py, utils/integrator.py:13-19, utils/utils.py:3-13): kinematic bicycle, RK4 defects, closed lap,

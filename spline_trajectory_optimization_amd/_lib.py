@@ -99,6 +99,12 @@ _SIGNATURES = {
     "rl_mintime_solve_batch_dev": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int,
                                                   ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp, _vp,
                                                   _vp, ctypes.c_int, ctypes.c_double, _vp]),
+    "rl_mintime_solve_vehicles": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int,
+                                                 ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _dp, _dp,
+                                                 _dp, ctypes.c_int, ctypes.c_double, _dp]),
+    "rl_mintime_solve_vehicles_dev": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int,
+                                                     ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp,
+                                                     _vp, _vp, ctypes.c_int, ctypes.c_double, _vp]),
     "rl_bicycle_eval_nodes": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "rl_bicycle_solve_batch": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int, _dp, _dp,
                                               _dp, ctypes.c_int, ctypes.c_double, _dp]),

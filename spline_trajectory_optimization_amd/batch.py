@@ -305,14 +305,17 @@ MIN_TIME_U0 = (1.0, -1.0, 0.001, 0.0)   # the reference's constant controls of a
 
 def min_time_centerline_guess_torch(s_nodes, base, B):
     """The guess optimise_track_batch hands the NLP without start lines: on the centre line with the QSS table's speeds and
-    times.  s_nodes [N], base [N,19] (simulated centre-line table), cuda tensors.  Returns (X0 [B,N,6], U0 [B,N,4], T0 [B,N])."""
+    times.  s_nodes [N], base [N,19] (simulated centre-line table) or [B,N,19] (one per instance: vehicle sweeps), cuda
+    tensors.  Returns (X0 [B,N,6], U0 [B,N,4], T0 [B,N])."""
     import torch
     N = int(s_nodes.shape[0])
+    if base.ndim == 3 and int(base.shape[0]) != B:
+        raise ValueError(f"base: {int(base.shape[0])} tables for {B} instances")
     X = torch.zeros((B, N, 6), dtype=torch.float64, device=s_nodes.device)
     X[:, :, 0] = s_nodes
-    X[:, :, 5] = base[:, 4]
+    X[:, :, 5] = base[..., 4]
     U = torch.tensor(MIN_TIME_U0, dtype=torch.float64, device=s_nodes.device).repeat(B, N, 1).contiguous()
-    T = base[:, 16].repeat(B, 1).contiguous()
+    T = base[:, :, 16].contiguous() if base.ndim == 3 else base[:, 16].repeat(B, 1).contiguous()
     return X, U, T
 
 

@@ -162,8 +162,9 @@ RL_DT Dual<ND, T> m_max(const Dual<ND, T>& a, const Dual<ND, T>& b) { return m_v
 template <typename S>
 struct DtTyres { S fx[4], fy[4], fz[4]; };  // fl, fr, rl, rr
 
-template <typename S>
-__device__ __forceinline__ void dt_dynamics(const double* p, const S (&x)[6], const S (&u)[4], double k,
+// PP: `const double*`, or the pointer to a row of the min-time solver's vehicle table (rl_mintime.hpp: MtTab)
+template <typename S, typename PP>
+__device__ __forceinline__ void dt_dynamics(PP p, const S (&x)[6], const S (&u)[4], double k,
                                             S (&f)[6], DtTyres<S>& ty) {
   const S n = x[1], phi = x[2], omega = x[3], beta = x[4], v = x[5];
   const S fd = u[0] * (m_tanh(u[0]) * 0.5 + 0.5);    // :17

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <type_traits>
 
 #include "rl_kernels.hpp"
@@ -1668,10 +1669,29 @@ int rl_dt_eval_jac(rl_ctx* ctx, const double* model, int B, int N, const double*
 // ---- the min-time double-track NLP (rl_mintime.hpp)
 namespace {
 // A sub-batch: its stream, its views of the problem, the state and the caller's arrays, the grids most kernels share (y: the instance).
-struct MtGroup { hipStream_t q; rl::MtProblem P; rl::MtState st; double *X, *U, *T, *stats; dim3 rows, per_node, per_inst; };
+// veh: one vehicle per instance -- V carries the group's slice of the vehicle table and the kernels that read the model are
+// launched as their <MtProblemV> instance (rl_mintime.hpp); P.p / sw / se are then NaN, so that a kernel that read the model
+// from its arguments in such a call could not go unnoticed.
+struct MtGroup { hipStream_t q; rl::MtProblem P; rl::MtProblemV V; bool veh; rl::MtState st; double *X, *U, *T, *stats; dim3 rows, per_node, per_inst; };
 using MtKernel = void (*)(rl::MtProblem, rl::MtState);
-int mt_run(const rl_ctx* ctx, const MtGroup& G, MtKernel kernel, dim3 grid, int threads) {
+using MtKernelV = void (*)(rl::MtProblemV, rl::MtState);
+struct MtKernels { MtKernel shared; MtKernelV vehicles; };   // the two forms of a kernel that reads the model
+#define MT_K(name) MtKernels{rl::name<rl::MtProblem>, rl::name<rl::MtProblemV>}
+#define MT_KT(name, arg) MtKernels{rl::name<arg, rl::MtProblem>, rl::name<arg, rl::MtProblemV>}
+int mt_run(const rl_ctx* ctx, const MtGroup& G, MtKernel kernel, dim3 grid, int threads) {   // a kernel that never reads the model
   return launch(ctx, G.q, kernel, grid, dim3(threads), 0, G.P, G.st);
+}
+int mt_run_model(const rl_ctx* ctx, const MtGroup& G, MtKernels k, dim3 grid, int threads) {
+  return G.veh ? launch(ctx, G.q, k.vehicles, grid, dim3(threads), 0, G.V, G.st)
+               : launch(ctx, G.q, k.shared, grid, dim3(threads), 0, G.P, G.st);
+}
+int mt_pack(const rl_ctx* ctx, const MtGroup& G) {
+  return G.veh ? launch(ctx, G.q, rl::k_mt_pack<rl::MtProblemV>, G.rows, dim3(64), 0, G.V, G.st, G.X, G.U, G.T)
+               : launch(ctx, G.q, rl::k_mt_pack<rl::MtProblem>, G.rows, dim3(64), 0, G.P, G.st, G.X, G.U, G.T);
+}
+int mt_unpack(const rl_ctx* ctx, const MtGroup& G) {
+  return G.veh ? launch(ctx, G.q, rl::k_mt_unpack<rl::MtProblemV>, G.rows, dim3(64), 0, G.V, G.st, G.X, G.U, G.T)
+               : launch(ctx, G.q, rl::k_mt_unpack<rl::MtProblem>, G.rows, dim3(64), 0, G.P, G.st, G.X, G.U, G.T);
 }
 
 // One iteration of one group on its stream; finished instances return at once from every kernel.  Three pipelines: the
@@ -1679,77 +1699,122 @@ int mt_run(const rl_ctx* ctx, const MtGroup& G, MtKernel kernel, dim3 grid, int 
 int mt_enqueue_iteration(const rl_ctx* ctx, const MtGroup& G) {
   const int N = G.P.N, nb = G.st.B;
   if (ctx->mt_hes_sweep) {   // cross-check: forward (over forward) duals through the whole pair function
-    RL_TRY(mt_run(ctx, G, rl::k_mt_derivs<0>, G.rows, 64));
-    RL_TRY(mt_run(ctx, G, rl::k_mt_derivs<1>, dim3(G.rows.x, nb, rl::kMtJacSlices), 64));
-    RL_TRY(mt_run(ctx, G, rl::k_mt_derivs<2>, dim3(G.rows.x, nb, rl::kMtHesSlices), 64));
+    RL_TRY(mt_run_model(ctx, G, MT_KT(k_mt_derivs, 0), G.rows, 64));
+    RL_TRY(mt_run_model(ctx, G, MT_KT(k_mt_derivs, 1), dim3(G.rows.x, nb, rl::kMtJacSlices), 64));
+    RL_TRY(mt_run_model(ctx, G, MT_KT(k_mt_derivs, 2), dim3(G.rows.x, nb, rl::kMtHesSlices), 64));
   } else {
-    RL_TRY(mt_run(ctx, G, rl::k_mt_values, G.rows, 64));   // functions; values of the dynamics at the two ends -> midpoint
-    RL_TRY(mt_run(ctx, G, rl::k_mt_jac_dirs, dim3(rl::mt_jac_blocks(N), nb, 3), 64));
-    if (ctx->mt_unfused) RL_TRY(mt_run(ctx, G, rl::k_mt_jac_assemble, G.per_node, 64));
-    RL_TRY(mt_run(ctx, G, rl::k_mt_hes_point<0>, dim3(rl::mt_hes_blocks(N), nb, 1), 64));
-    RL_TRY(mt_run(ctx, G, rl::k_mt_hes_point<1>, dim3(rl::mt_hes_blocks(N), nb, 2), 64));
+    RL_TRY(mt_run_model(ctx, G, MT_K(k_mt_values), G.rows, 64));   // functions; values of the dynamics at the two ends -> midpoint
+    RL_TRY(mt_run_model(ctx, G, MT_K(k_mt_jac_dirs), dim3(rl::mt_jac_blocks(N), nb, 3), 64));
+    if (ctx->mt_unfused) RL_TRY(mt_run_model(ctx, G, MT_K(k_mt_jac_assemble), G.per_node, 64));
+    RL_TRY(mt_run_model(ctx, G, MT_KT(k_mt_hes_point, 0), dim3(rl::mt_hes_blocks(N), nb, 1), 64));
+    RL_TRY(mt_run_model(ctx, G, MT_KT(k_mt_hes_point, 1), dim3(rl::mt_hes_blocks(N), nb, 2), 64));
     if (ctx->mt_unfused) {
-      RL_TRY(mt_run(ctx, G, rl::k_mt_hes_assemble, G.per_node, 64));
+      RL_TRY(mt_run_model(ctx, G, MT_K(k_mt_hes_assemble), G.per_node, 64));
     } else {   // Jacobian, Hessian, blocks and right-hand side in one pass over the pairs
-      RL_TRY(mt_run(ctx, G, rl::k_mt_node, dim3(rl::mt_node_blocks(N), nb), 64));
-      RL_TRY(mt_run(ctx, G, rl::k_mt_prepare2, G.per_inst, 256));
+      RL_TRY(mt_run_model(ctx, G, MT_K(k_mt_node), dim3(rl::mt_node_blocks(N), nb), 64));
+      RL_TRY(mt_run_model(ctx, G, MT_K(k_mt_prepare2), G.per_inst, 256));
     }
   }
   if (ctx->mt_hes_sweep || ctx->mt_unfused) {
-    RL_TRY(mt_run(ctx, G, rl::k_mt_prepare, G.per_inst, 64));
+    RL_TRY(mt_run_model(ctx, G, MT_K(k_mt_prepare), G.per_inst, 64));
     RL_TRY(mt_run(ctx, G, rl::k_mt_assemble, G.per_node, 64));
     RL_TRY(mt_run(ctx, G, rl::k_mt_gc_pack, G.per_node, 64));
   }
   if (ctx->mt_kkt4 && N >= 64) RL_TRY(mt_run(ctx, G, rl::k_mt_kkt4, G.per_inst, 256));
   else RL_TRY(mt_run(ctx, G, rl::k_mt_kkt, G.per_inst, 128));
   RL_TRY(mt_run(ctx, G, rl::k_mt_dir, dim3(rl::kMtDirBlocks(N), nb), 64));
-  RL_TRY(mt_run(ctx, G, rl::k_mt_trial, G.rows, 64));
+  RL_TRY(mt_run_model(ctx, G, MT_K(k_mt_trial), G.rows, 64));
   RL_TRY(mt_run(ctx, G, rl::k_mt_step, G.per_inst, 256));
-  RL_TRY(mt_run(ctx, G, rl::k_mt_trial_b, G.rows, 64));        // halvings of the instances whose first trial point was rejected
-  return mt_run(ctx, G, rl::k_mt_step_b, G.per_inst, 256);
+  RL_TRY(mt_run_model(ctx, G, MT_K(k_mt_trial_b), G.rows, 64));        // halvings of the instances whose first trial point was rejected
+  return mt_run_model(ctx, G, MT_K(k_mt_step_b), G.per_inst, 256);
 }
 
 // the closing pass of one group: final residuals of the instances still running (status 0 = iteration limit), the caller's arrays, the report
 int mt_enqueue_closing(const rl_ctx* ctx, const MtGroup& G) {
   const int N = G.P.N, nb = G.st.B;
-  RL_TRY(mt_run(ctx, G, rl::k_mt_derivs<0>, G.rows, 64));
+  RL_TRY(mt_run_model(ctx, G, MT_KT(k_mt_derivs, 0), G.rows, 64));
   if (ctx->mt_hes_sweep) {
-    RL_TRY(mt_run(ctx, G, rl::k_mt_derivs<1>, dim3(G.rows.x, nb, rl::kMtJacSlices), 64));
+    RL_TRY(mt_run_model(ctx, G, MT_KT(k_mt_derivs, 1), dim3(G.rows.x, nb, rl::kMtJacSlices), 64));
   } else {
-    RL_TRY(mt_run(ctx, G, rl::k_mt_hes_values, G.rows, 64));
-    RL_TRY(mt_run(ctx, G, rl::k_mt_jac_dirs, dim3(rl::mt_jac_blocks(N), nb, 3), 64));
-    RL_TRY(mt_run(ctx, G, rl::k_mt_jac_assemble, G.per_node, 64));
+    RL_TRY(mt_run_model(ctx, G, MT_K(k_mt_hes_values), G.rows, 64));
+    RL_TRY(mt_run_model(ctx, G, MT_K(k_mt_jac_dirs), dim3(rl::mt_jac_blocks(N), nb, 3), 64));
+    RL_TRY(mt_run_model(ctx, G, MT_K(k_mt_jac_assemble), G.per_node, 64));
   }
-  RL_TRY(mt_run(ctx, G, rl::k_mt_residuals, G.per_inst, 64));
-  RL_TRY(launch(ctx, G.q, rl::k_mt_unpack, G.rows, dim3(64), 0, G.P, G.st, G.X, G.U, G.T));
+  RL_TRY(mt_run_model(ctx, G, MT_K(k_mt_residuals), G.per_inst, 64));
+  RL_TRY(mt_unpack(ctx, G));
   return launch(ctx, G.q, rl::k_mt_stats, dim3((nb + 63) / 64), dim3(64), 0, G.st, G.stats);
+}
+
+// min_time_optimizer.py:109-113: scale_x = (1, average_track_width, 1, 1, 0.5, speed_cap),
+// scale_u = (Fd_max, |Fb_max|, delta_max, 50 mass), scale_t = 1  ->  sw [9], se [7] of one model (MtProblem).  The one
+// statement of the scales: the shared-model call and every row of a vehicles call go through it.
+void mt_scales(const double* model, double average_track_width, double speed_cap, double* sw, double* se) {
+  const double sx[6] = {1.0, average_track_width, 1.0, 1.0, 0.5, speed_cap};
+  const double su[4] = {model[RL_DT_FD_MAX], std::fabs(model[RL_DT_FB_MAX]), model[RL_DT_DELTA_MAX], model[RL_DT_MASS] * 50.0};
+  for (int c = 0; c < 5; ++c) sw[c] = sx[1 + c];
+  sw[5] = su[0]; sw[6] = su[2]; sw[7] = su[3]; sw[8] = 1.0;
+  for (int c = 0; c < 6; ++c) se[c] = 1.0 / sx[c];
+  se[6] = 1.0 / su[3];
+}
+
+// a vehicles call checks every row before anything is enqueued: what the scales divide by and what the rows of the NLP divide by
+int mt_check_models(const double* models, int B) {
+  static const struct { int slot; const char* name; } positive[] = {
+      {RL_DT_FD_MAX, "Fd_max"}, {RL_DT_DELTA_MAX, "delta_max"}, {RL_DT_MASS, "mass"}, {RL_DT_PMAX, "Pmax"}, {RL_DT_MU, "mu"},
+      {RL_DT_TD, "Td"}, {RL_DT_TB, "Tb"}, {RL_DT_TDELTA, "Tdelta"}};
+  for (int b = 0; b < B; ++b) {
+    const double* m = models + (size_t)b * RL_DT_NPARAM;
+    for (int i = 0; i < RL_DT_NPARAM; ++i)
+      if (!std::isfinite(m[i])) return fail(RL_ERR_ARG, "models: instance " + std::to_string(b) + ": parameter " + std::to_string(i) + " is not finite");
+    if (!(std::fabs(m[RL_DT_FB_MAX]) > 0.0)) return fail(RL_ERR_ARG, "models: instance " + std::to_string(b) + ": |Fb_max| must be > 0");
+    for (const auto& q : positive)
+      if (!(m[q.slot] > 0.0)) return fail(RL_ERR_ARG, "models: instance " + std::to_string(b) + ": " + q.name + " must be > 0");
+  }
+  return RL_OK;
 }
 
 // Both entry points of the solve, on device pointers.  poll: stop enqueueing once every instance has finished (the host
 // entry point, which synchronises anyway); without it all max_iter iterations are enqueued and the call does not wait.
-int mintime_solve_common(rl_ctx* ctx, const double* model, int B, int N, const double* s, const double* kappa, const double* left,
+// vehicles: `model` is [B, RL_DT_NPARAM], one row per instance (rl_mintime_solve_vehicles*).
+int mintime_solve_common(rl_ctx* ctx, const double* model, bool vehicles, int B, int N, const double* s, const double* kappa, const double* left,
                          const double* right, int bounds_per_instance, double margin, double track_length, double average_track_width,
                          double speed_cap, double* X, double* U, double* T, int max_iter, double tol, double* stats, bool poll) {
   if (!ctx || !model || !s || !kappa || !left || !right || !X || !U || !T || !stats) return fail(RL_ERR_ARG, "null argument");
   if (B <= 0 || N < 8 || !(track_length > 0.0) || max_iter < 1 || !(tol > 0.0)) return fail(RL_ERR_ARG, "bad sizes (N >= 8 nodes)");
   if (!(average_track_width > 0.0) || !(speed_cap > 0.0)) return fail(RL_ERR_ARG, "bad scales");
+  if (vehicles) RL_TRY(mt_check_models(model, B));
   RL_HIP(hipSetDevice(ctx->device));
   rl::MtProblem P;
-  for (int i = 0; i < rl::DT_NPARAM; ++i) P.p[i] = model[i];
   P.N = N; P.bounds_per_instance = bounds_per_instance ? 1 : 0;
   P.margin = margin; P.track_length = track_length;
-  // min_time_optimizer.py:109-113: scale_x = (1, average_track_width, 1, 1, 0.5, speed_cap),
-  // scale_u = (Fd_max, |Fb_max|, delta_max, 50 mass), scale_t = 1
-  const double sx[6] = {1.0, average_track_width, 1.0, 1.0, 0.5, speed_cap};
-  const double su[4] = {model[RL_DT_FD_MAX], std::fabs(model[RL_DT_FB_MAX]), model[RL_DT_DELTA_MAX], model[RL_DT_MASS] * 50.0};
-  for (int c = 0; c < 5; ++c) P.sw[c] = sx[1 + c];
-  P.sw[5] = su[0]; P.sw[6] = su[2]; P.sw[7] = su[3]; P.sw[8] = 1.0;
-  for (int c = 0; c < 6; ++c) P.se[c] = 1.0 / sx[c];
-  P.se[6] = 1.0 / su[3];
   P.s = s; P.kappa = kappa; P.left = left; P.right = right;
+  std::vector<double> rows;   // vehicles: the table p | sw | se, kMtRow doubles per instance
+  if (vehicles) {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (double& v : P.p) v = nan;
+    for (double& v : P.sw) v = nan;
+    for (double& v : P.se) v = nan;
+    rows.assign((size_t)B * rl::kMtRow, 0.0);
+    for (int b = 0; b < B; ++b) {
+      const double* m = model + (size_t)b * RL_DT_NPARAM;
+      double* r = rows.data() + (size_t)b * rl::kMtRow;
+      for (int i = 0; i < rl::DT_NPARAM; ++i) r[i] = m[i];
+      mt_scales(m, average_track_width, speed_cap, r + rl::kMtRowSw, r + rl::kMtRowSe);
+    }
+  } else {
+    for (int i = 0; i < rl::DT_NPARAM; ++i) P.p[i] = model[i];
+    mt_scales(model, average_track_width, speed_cap, P.sw, P.se);
+  }
   Arena ar(ctx);
   rl::MtState st;
-  RL_HIP(ar.carve([&](Arena& x) { rl::carve(x, st, rl::kMtArrays, B, N); }));
+  double* table = nullptr;
+  RL_HIP(ar.carve([&](Arena& x) {
+    rl::carve(x, st, rl::kMtArrays, B, N);
+    if (vehicles) table = x.take<double>(rows.size());
+  }));
+  // a pageable copy on the context's stream (the runtime has read `rows` when it returns, as for the long tables of
+  // qss_sim_enqueue); the sub-batch streams fork behind it
+  if (vehicles) RL_HIP(hipMemcpyAsync(table, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   st.tol = tol;
   // Strategy constants of the line search / barrier update.  Measured on 1024 width-perturbed MGKT tracks:
   // (d_up, a_lo, mu_kappa) = (5, 0.3, 10) 96.5 iterations on average, (3, 0.2, 30) 77.8 (round 2).  Round 4: the damping
@@ -1806,6 +1871,11 @@ int mintime_solve_common(rl_ctx* ctx, const double* model, int B, int N, const d
     MtGroup& G = grp[g];
     G.q = fork_stream(ctx, g); G.P = P; G.st = rl::slice(st, rl::kMtArrays, b0, nb);
     if (P.bounds_per_instance) { G.P.left = left + o; G.P.right = right + o; }
+    G.veh = vehicles;
+    const double* row0 = table + (vehicles ? (size_t)b0 * rl::kMtRow : 0);   // the group's slice of the table, as of left / right
+    G.V.p = (rl::MtTab)row0; G.V.sw = (rl::MtTab)(row0 + rl::kMtRowSw); G.V.se = (rl::MtTab)(row0 + rl::kMtRowSe);
+    G.V.N = N; G.V.s = s; G.V.kappa = kappa; G.V.left = G.P.left; G.V.right = G.P.right;
+    G.V.bounds_per_instance = P.bounds_per_instance; G.V.margin = margin; G.V.track_length = track_length;
     G.X = X + o * 6; G.U = U + o * 4; G.T = T + o; G.stats = stats + (size_t)b0 * rl::kMtStats;
     G.rows = dim3(rl::mt_row_blocks(N), nb); G.per_node = dim3(N, nb); G.per_inst = dim3(nb);
   }
@@ -1813,8 +1883,8 @@ int mintime_solve_common(rl_ctx* ctx, const double* model, int B, int N, const d
   for (int g = 1; g < ngrp; ++g) RL_HIP(hipStreamWaitEvent(grp[g].q, ctx->ev_fork, 0));
   for (int g = 0; g < ngrp; ++g) {
     const MtGroup& G = grp[g];
-    RL_TRY(launch(ctx, G.q, rl::k_mt_pack, G.rows, dim3(64), 0, G.P, G.st, G.X, G.U, G.T));
-    RL_TRY(mt_run(ctx, G, rl::k_mt_derivs<0>, G.rows, 64));
+    RL_TRY(mt_pack(ctx, G));
+    RL_TRY(mt_run_model(ctx, G, MT_KT(k_mt_derivs, 0), G.rows, 64));
     RL_TRY(launch(ctx, G.q, rl::k_mt_init, dim3(rl::mt_init_blocks(N), G.st.B), dim3(256), 0, G.P, G.st, mt_mu0, mt_delta0));
   }
   for (int it = 0; it < max_iter; ++it) {
@@ -1848,20 +1918,31 @@ int mintime_solve_common(rl_ctx* ctx, const double* model, int B, int N, const d
   RL_HIP(ar.end());
   return RL_OK;
 }
+#undef MT_K
+#undef MT_KT
 }  // namespace
 
 int rl_mintime_solve_batch_dev(rl_ctx* ctx, const double* model, int B, int N, const double* s, const double* kappa,
                                const double* left, const double* right, int bounds_per_instance, double margin,
                                double track_length, double average_track_width, double speed_cap, double* X, double* U,
                                double* T, int max_iter, double tol, double* stats) {
-  return mintime_solve_common(ctx, model, B, N, s, kappa, left, right, bounds_per_instance, margin, track_length,
+  return mintime_solve_common(ctx, model, false, B, N, s, kappa, left, right, bounds_per_instance, margin, track_length,
                               average_track_width, speed_cap, X, U, T, max_iter, tol, stats, false);
 }
 
-int rl_mintime_solve_batch(rl_ctx* ctx, const double* model, int B, int N, const double* s, const double* kappa,
-                           const double* left, const double* right, int bounds_per_instance, double margin,
-                           double track_length, double average_track_width, double speed_cap, double* X, double* U,
-                           double* T, int max_iter, double tol, double* stats) {
+int rl_mintime_solve_vehicles_dev(rl_ctx* ctx, const double* models, int B, int N, const double* s, const double* kappa,
+                                  const double* left, const double* right, int bounds_per_instance, double margin,
+                                  double track_length, double average_track_width, double speed_cap, double* X, double* U,
+                                  double* T, int max_iter, double tol, double* stats) {
+  return mintime_solve_common(ctx, models, true, B, N, s, kappa, left, right, bounds_per_instance, margin, track_length,
+                              average_track_width, speed_cap, X, U, T, max_iter, tol, stats, false);
+}
+
+// the host entries: stage the arrays, run the shared function with the poll, bring the results down
+static int mintime_solve_host(rl_ctx* ctx, const double* model, bool vehicles, int B, int N, const double* s, const double* kappa,
+                              const double* left, const double* right, int bounds_per_instance, double margin,
+                              double track_length, double average_track_width, double speed_cap, double* X, double* U,
+                              double* T, int max_iter, double tol, double* stats) {
   if (!ctx || !left || !right) return fail(RL_ERR_ARG, "null argument");   // what is read here; the shared function checks the rest
   if (B <= 0 || N < 8) return fail(RL_ERR_ARG, "bad sizes (N >= 8 nodes)");
   const size_t bn = (size_t)B * N, nb_ = bounds_per_instance ? bn : (size_t)N;
@@ -1872,10 +1953,28 @@ int rl_mintime_solve_batch(rl_ctx* ctx, const double* model, int B, int N, const
   double *dX = sg.inout(X, bn * 6), *dU = sg.inout(U, bn * 4), *dT = sg.inout(T, bn);
   double* dst = sg.out(stats, (size_t)B * rl::kMtStats);
   sg.run([&] {
-    return mintime_solve_common(ctx, model, B, N, ds, dk, dl, dr, bounds_per_instance, margin, track_length,
+    return mintime_solve_common(ctx, model, vehicles, B, N, ds, dk, dl, dr, bounds_per_instance, margin, track_length,
                                 average_track_width, speed_cap, dX, dU, dT, max_iter, tol, dst, true);
   });
   return sg.finish();
+}
+
+int rl_mintime_solve_batch(rl_ctx* ctx, const double* model, int B, int N, const double* s, const double* kappa,
+                           const double* left, const double* right, int bounds_per_instance, double margin,
+                           double track_length, double average_track_width, double speed_cap, double* X, double* U,
+                           double* T, int max_iter, double tol, double* stats) {
+  return mintime_solve_host(ctx, model, false, B, N, s, kappa, left, right, bounds_per_instance, margin, track_length,
+                            average_track_width, speed_cap, X, U, T, max_iter, tol, stats);
+}
+
+int rl_mintime_solve_vehicles(rl_ctx* ctx, const double* models, int B, int N, const double* s, const double* kappa,
+                              const double* left, const double* right, int bounds_per_instance, double margin,
+                              double track_length, double average_track_width, double speed_cap, double* X, double* U,
+                              double* T, int max_iter, double tol, double* stats) {
+  if (!models) return fail(RL_ERR_ARG, "null argument");
+  if (B > 0) RL_TRY(mt_check_models(models, B));   // before anything is staged
+  return mintime_solve_host(ctx, models, true, B, N, s, kappa, left, right, bounds_per_instance, margin, track_length,
+                            average_track_width, speed_cap, X, U, T, max_iter, tol, stats);
 }
 
 // ---- the bicycle min-time NLP (rl_bicycle.hpp)

@@ -80,6 +80,32 @@ struct MtProblem {
   double se[kMtNe];   // row scale of the equalities: 1 / scale_x (6), 1 / scale_u[3]
 };
 
+// One vehicle per instance (rl_mintime_solve_vehicles*): p | sw | se of instance b are row b of a table in device memory,
+// kMtRow doubles apart, instead of kernel arguments.  Every kernel takes its instance from blockIdx, so a row's address
+// is the same in all lanes; the pointers are in the constant address space (the table is written by a copy that is
+// complete before the first kernel of the solve starts, and by nothing else), which makes every read of a value a scalar
+// load whatever the kernel stores in between -- the registers a value occupies are the ones the kernel argument
+// occupied.  The pair functions and the kernels that read the model are templates over the problem type -- <MtProblem> with
+// the model in the kernel arguments (what the shared-model entries launch), <MtProblemV> with the table -- and read P.p[],
+// P.sw[], P.se[] from either; the expressions on the values are the same text in the same order.  The other kernels
+// (k_mt_assemble, k_mt_gc_pack, k_mt_kkt, k_mt_kkt4, k_mt_dir, k_mt_step, k_mt_init) never look at the model and take
+// MtProblem in both cases.
+typedef const double __attribute__((address_space(4))) * MtTab;
+constexpr int kMtRowSw = DT_NPARAM, kMtRowSe = kMtRowSw + kMtNv, kMtRow = 48;   // 28 + 9 + 7 = 44 doubles, padded to 384 B
+static_assert(kMtRowSe + kMtNe <= kMtRow, "a table row holds p | sw | se");
+struct MtProblemV {
+  MtTab p, sw, se;    // row 0 of the (sub-)batch; mt_model moves them to the instance's row
+  int N;
+  const double* s; const double* kappa; const double* left; const double* right;
+  int bounds_per_instance;
+  double margin, track_length;
+};
+__device__ __forceinline__ void mt_model(MtProblem&, int) {}
+__device__ __forceinline__ void mt_model(MtProblemV& P, int b) {
+  const size_t o = (size_t)b * kMtRow;
+  P.p += o; P.sw += o; P.se += o;
+}
+
 template <typename S> struct MtLift;
 template <> struct MtLift<double> { static __device__ __forceinline__ double make(double v) { return v; } };
 template <int ND, typename T> struct MtLift<Dual<ND, T>> {
@@ -95,9 +121,9 @@ template <int ND, typename T> struct MtLift<Dual<ND, T>> {
 // rows are handed to a SINK as soon as they exist -- sink.eq(c, v) / sink.g(c, v) ADD v to row c; the defect
 // rows arrive in two pieces -- so that a caller that only needs a weighted sum of the rows (the Lagrangian of
 // the Hessian kernel) never holds the 24 of them at once.
-template <typename S, typename Sink>
-__device__ __forceinline__ void mt_pair_emit(const MtProblem& P, int j, const S (&wo)[kMtNv], const S (&wn)[kMtNv], Sink& sink) {
-  const double* p = P.p;
+template <typename S, typename Sink, typename PT>
+__device__ __forceinline__ void mt_pair_emit(const PT& P, int j, const S (&wo)[kMtNv], const S (&wn)[kMtNv], Sink& sink) {
+  const auto p = P.p;
   const int jn = j + 1 == P.N ? 0 : j + 1;
   S x[6], xn[6], u[4];
   x[0] = MtLift<S>::make(P.s[j]); xn[0] = MtLift<S>::make(P.s[jn]);
@@ -170,8 +196,8 @@ struct MtRowSink {     // all 24 rows (function values, Jacobian slices)
   __device__ __forceinline__ void g(int c, const S& v) { g_[c] = g_[c] + v; }
 };
 
-template <typename S>
-__device__ __forceinline__ void mt_pair(const MtProblem& P, int j, const S (&wo)[kMtNv], const S (&wn)[kMtNv],
+template <typename S, typename PT>
+__device__ __forceinline__ void mt_pair(const PT& P, int j, const S (&wo)[kMtNv], const S (&wn)[kMtNv],
                                         S (&eq)[kMtNe], S (&g)[kMtNi]) {
 #pragma unroll
   for (int c = 0; c < kMtNe; ++c) eq[c] = MtLift<S>::make(0.0);
@@ -215,17 +241,19 @@ constexpr StateArray<MtState> kMtArrays[] = {
 static_assert(sizeof(kMtArrays) / sizeof(kMtArrays[0]) == (offsetof(MtState, tol) - offsetof(MtState, w)) / sizeof(double*), "every array of MtState has its row");
 
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void mt_instance(MtProblem& P, int b) {
+template <typename PT>
+__device__ __forceinline__ void mt_instance(PT& P, int b) {
   if (P.bounds_per_instance) { P.left += (size_t)b * P.N; P.right += (size_t)b * P.N; }
 }
 
 // k_mt_derivs<KIND>: one thread per (node, instance, slice).  KIND 0: functions (1 slice), 1: Jacobian (6 slices
 // of three directions), 2: Hessian (kMtHesSlices pairs of direction groups) -- three kernels, so that the cheap
 // ones do not inherit the register budget of the forward-over-forward one.
-template <int KIND>
-__global__ void __launch_bounds__(64) k_mt_derivs(MtProblem P, MtState st) {
+template <int KIND, typename PT>
+__global__ void __launch_bounds__(64) k_mt_derivs(PT P, MtState st) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   const int b = blockIdx.y;
+  mt_model(P, b);
   const int slice = KIND == 0 ? 0 : (KIND == 1 ? 1 + (int)blockIdx.z : 1 + kMtJacSlices + (int)blockIdx.z);
   if (j >= P.N) return;
   if (st.scal[(size_t)b * kMtScal + kMtStatus] != 0.0) return;   // instance finished
@@ -354,7 +382,8 @@ __device__ __forceinline__ int mt_tri8(int a, int b) {               // index of
 }
 
 // physical unknowns of the pair; the next state is brought next to this one (utils/utils.py:10-18: locally the identity)
-__device__ __forceinline__ void mt_phys(const MtProblem& P, const double* wo, const double* wn, double (&Y)[5], double (&Yn)[5],
+template <typename PT>
+__device__ __forceinline__ void mt_phys(const PT& P, const double* wo, const double* wn, double (&Y)[5], double (&Yn)[5],
                                         double (&U)[3], double& t) {
 #pragma unroll
   for (int c = 0; c < 5; ++c) { Y[c] = wo[c] * P.sw[c]; Yn[c] = wn[c] * P.sw[c]; }
@@ -366,8 +395,8 @@ __device__ __forceinline__ void mt_phys(const MtProblem& P, const double* wo, co
   Yn[1] = m_atan2(sd, cd) + Y[1];
 }
 
-template <typename S>
-__device__ __forceinline__ void mt_dyn(const MtProblem& P, int j, const S (&Y)[5], const S (&U)[3], S (&f)[6], DtTyres<S>& ty) {
+template <typename S, typename PT>
+__device__ __forceinline__ void mt_dyn(const PT& P, int j, const S (&Y)[5], const S (&U)[3], S (&f)[6], DtTyres<S>& ty) {
   S x[6], u[4];
   x[0] = MtLift<S>::make(P.s[j]);
 #pragma unroll
@@ -377,10 +406,10 @@ __device__ __forceinline__ void mt_dyn(const MtProblem& P, int j, const S (&Y)[5
 }
 
 // the rows of this node that are curved and depend on (Y, U) only, weighted with their multipliers
-template <typename S>
-__device__ __forceinline__ S mt_own_rows(const MtProblem& P, const S (&Y)[5], const S (&U)[3], const DtTyres<S>& ty,
+template <typename S, typename PT>
+__device__ __forceinline__ S mt_own_rows(const PT& P, const S (&Y)[5], const S (&U)[3], const DtTyres<S>& ty,
                                          const double* y, const double* z) {
-  const double* p = P.p;
+  const auto p = P.p;
   S sd, cd_;
   m_sincos(U[1], sd, cd_);
   S L = (U[2] - p[DT_HCOG] / (0.5 * (p[DT_TWF] + p[DT_TWR])) *
@@ -396,7 +425,8 @@ __device__ __forceinline__ S mt_own_rows(const MtProblem& P, const S (&Y)[5], co
 }
 
 // values of the two end evaluations -> midpoint and F1 - F2
-__device__ __forceinline__ void mt_hes_values_body(const MtProblem& P, const MtState& st, int b, int j) {
+template <typename PT>
+__device__ __forceinline__ void mt_hes_values_body(const PT& P, const MtState& st, int b, int j) {
   const int N = P.N;
   const int jn = j + 1 == N ? 0 : j + 1;
   double Y[5], Yn[5], U[3], t;
@@ -418,7 +448,8 @@ __device__ __forceinline__ void mt_hes_values_body(const MtProblem& P, const MtS
   for (int c = 0; c < 6; ++c) { hw[kMtHwF + c] = f1[c]; hw[kMtHwF + 6 + c] = f2[c]; }
 }
 // functions eq, g of the pair at the current point -> st.fun
-__device__ __forceinline__ void mt_fun_body(MtProblem P, const MtState& st, int b, int j) {
+template <typename PT>
+__device__ __forceinline__ void mt_fun_body(PT P, const MtState& st, int b, int j) {
   mt_instance(P, b);
   const int N = P.N, jn = j + 1 == N ? 0 : j + 1;
   const double* wo_ = st.w + ((size_t)b * N + j) * kMtNv;
@@ -434,24 +465,28 @@ __device__ __forceinline__ void mt_fun_body(MtProblem P, const MtState& st, int 
   for (int c = 0; c < kMtNi; ++c) st.fun[o * kMtNf + kMtNe + c] = g[c];
 }
 // grid (node blocks, B): values of the two end evaluations -> midpoint and F1 - F2
-__global__ void __launch_bounds__(64) k_mt_hes_values(MtProblem P, MtState st) {
+template <typename PT>
+__global__ void __launch_bounds__(64) k_mt_hes_values(PT P, MtState st) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+  mt_model(P, b);
   if (j >= P.N || st.scal[(size_t)b * kMtScal + kMtStatus] != 0.0) return;
   mt_hes_values_body(P, st, b, j);
 }
 // grid (node blocks, B): both of the above in one launch (the first kernel of an iteration of the default path)
-__global__ void __launch_bounds__(64) k_mt_values(MtProblem P, MtState st) {
+template <typename PT>
+__global__ void __launch_bounds__(64) k_mt_values(PT P, MtState st) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+  mt_model(P, b);
   if (j >= P.N || st.scal[(size_t)b * kMtScal + kMtStatus] != 0.0) return;
   mt_fun_body(P, st, b, j);
   mt_hes_values_body(P, st, b, j);
 }
 
 // the curved rows of this node that depend on (Y, U) only, one by one (row order: eq 6, g 0..3, g 4)
-template <typename S>
-__device__ __forceinline__ void mt_own_rows_each(const MtProblem& P, const S (&Y)[5], const S (&U)[3], const DtTyres<S>& ty,
+template <typename S, typename PT>
+__device__ __forceinline__ void mt_own_rows_each(const PT& P, const S (&Y)[5], const S (&U)[3], const DtTyres<S>& ty,
                                                  S (&r)[6]) {
-  const double* p = P.p;
+  const auto p = P.p;
   S sd, cd_;
   m_sincos(U[1], sd, cd_);
   r[0] = (U[2] - p[DT_HCOG] / (0.5 * (p[DT_TWF] + p[DT_TWR])) *
@@ -473,9 +508,11 @@ __device__ __forceinline__ void mt_own_rows_each(const MtProblem& P, const S (&Y
 // n' = v sin(xi + beta), xi' = omega - kappa s' only (see k_mt_hes_point): their two columns are closed forms, written by
 // the first two lanes of the node.
 constexpr int kMtJacNodes = 10, kMtJacDirs = 6;
-__global__ void __launch_bounds__(64) k_mt_jac_dirs(MtProblem P, MtState st) {
+template <typename PT>
+__global__ void __launch_bounds__(64) k_mt_jac_dirs(PT P, MtState st) {
   const int nl = (int)threadIdx.x / kMtJacDirs, dl = (int)threadIdx.x - kMtJacDirs * nl;
   const int j = blockIdx.x * kMtJacNodes + nl, b = blockIdx.y, N = P.N;
+  mt_model(P, b);
   const int pt = blockIdx.z, d = 2 + dl;
   if (nl >= kMtJacNodes || j >= N || st.scal[(size_t)b * kMtScal + kMtStatus] != 0.0) return;
   const int jn = j + 1 == N ? 0 : j + 1;
@@ -522,9 +559,11 @@ __global__ void __launch_bounds__(64) k_mt_jac_dirs(MtProblem P, MtState st) {
 
 // grid (N, B), one wave per node: the 24 x 18 Jacobian of the pair rows in the scaled unknowns, from J1, J2, Jm by
 // the chain rule (defect rows), the own-row gradients, and the closed forms of the linear and the rate rows
-__global__ void __launch_bounds__(64) k_mt_jac_assemble(MtProblem P, MtState st) {
+template <typename PT>
+__global__ void __launch_bounds__(64) k_mt_jac_assemble(PT P, MtState st) {
   __shared__ double M[kMtPv][14], JM[6][14];
   const int j = blockIdx.x, b = blockIdx.y, lane = threadIdx.x, N = P.N;
+  mt_model(P, b);
   if (st.scal[(size_t)b * kMtScal + kMtStatus] != 0.0) return;
   const int jn = j + 1 == N ? 0 : j + 1;
   const size_t o = (size_t)b * N + j;
@@ -611,10 +650,11 @@ __global__ void __launch_bounds__(64) k_mt_jac_assemble(MtProblem P, MtState st)
 // A = m0 - kappa m2, theta = xi + beta, D = 1 / (1 - n kappa),  and the other 8 are zero (written: the work array is not cleared).
 constexpr int kMtHesNodes = 3, kMtDynVars = 6, kMtDynPairs = 21;
 __host__ __device__ constexpr int mt_hes_blocks(int N) { return (N + kMtHesNodes - 1) / kMtHesNodes; }
-template <int ENDS>
-__global__ void __launch_bounds__(64, 2) k_mt_hes_point(MtProblem P, MtState st) {
+template <int ENDS, typename PT>
+__global__ void __launch_bounds__(64, 2) k_mt_hes_point(PT P, MtState st) {
   const int nl = (int)threadIdx.x / kMtDynPairs, q = (int)threadIdx.x - kMtDynPairs * nl;
   const int j = blockIdx.x * kMtHesNodes + nl, b = blockIdx.y, N = P.N;
+  mt_model(P, b);
   const int pt = ENDS ? (int)blockIdx.z : 0;
   if (nl >= kMtHesNodes || j >= N || st.scal[(size_t)b * kMtScal + kMtStatus] != 0.0) return;
   const int jn = j + 1 == N ? 0 : j + 1;
@@ -678,9 +718,11 @@ __global__ void __launch_bounds__(64, 2) k_mt_hes_point(MtProblem P, MtState st)
 }
 
 // grid (N, B), one wave per node: the 18 x 18 Hessian of the scaled unknowns from the pieces
-__global__ void __launch_bounds__(64) k_mt_hes_assemble(MtProblem P, MtState st) {
+template <typename PT>
+__global__ void __launch_bounds__(64) k_mt_hes_assemble(PT P, MtState st) {
   __shared__ double M[kMtPv][14], T[kMtPv][14], Hm[kMtPv][kMtPv], g[kMtPv], gpsi[14], gphi[2][kMtPv], gF[2][kMtPv];
   const int j = blockIdx.x, b = blockIdx.y, lane = threadIdx.x, N = P.N;
+  mt_model(P, b);
   if (st.scal[(size_t)b * kMtScal + kMtStatus] != 0.0) return;
   const int jn = j + 1 == N ? 0 : j + 1;
   const size_t o = (size_t)b * N + j;
@@ -873,7 +915,8 @@ __device__ __forceinline__ double mt_cost_grad(const double* w, int N, int j, in
 
 // max |r_d|, max constraint violation, max s z, max |s z - mu|, lap time [s] of one instance (one wave)
 //   r_d[j][a] = gc + Ao(j)' y_j + An(j-1)' y_{j-1} + Go(j)' z_j + Gn(j-1)' z_{j-1}
-__device__ __forceinline__ void mt_residuals(const MtProblem& P, const double* w, const double* sv, const double* yv,
+template <typename PT>
+__device__ __forceinline__ void mt_residuals(const PT& P, const double* w, const double* sv, const double* yv,
                                              const double* zv, const double* fun, const double* jac, double mu, int lane,
                                              double& kkt, double& viol, double& compl_, double& errmu, double& lap) {
   const int N = P.N;
@@ -905,8 +948,10 @@ __device__ __forceinline__ void mt_residuals(const MtProblem& P, const double* w
 
 // k_mt_prepare: one wave per instance: residuals r_d, r_c, r_g at the current point -> kkt / viol / compl,
 // convergence test, barrier update (everything the assembly of the right-hand side needs to know)
-__global__ void __launch_bounds__(64) k_mt_prepare(MtProblem P, MtState st) {
+template <typename PT>
+__global__ void __launch_bounds__(64) k_mt_prepare(PT P, MtState st) {
   const int b = blockIdx.x, lane = threadIdx.x, N = P.N;
+  mt_model(P, b);
   double* scal = st.scal + (size_t)b * kMtScal;
   if (scal[kMtStatus] != 0.0) return;
   mt_instance(P, b);
@@ -1069,9 +1114,11 @@ __global__ void __launch_bounds__(64) k_mt_gc_pack(MtProblem P, MtState st) {
 static_assert(kMtHw == 21 * 16, "k_mt_node fetches the work array as 21 rows of 16 lanes");
 static_assert(kMtNv == 9 && kMtNe == 7 && kMtNi == 17 && kMtLoc == 18, "k_mt_node's lane = column layout is written for 9 + 7 unknowns per node");
 static_assert(kMtHesNodes * kMtDynPairs <= 64 && kMtJacNodes * kMtJacDirs <= 64, "(node, direction) lanes of the derivative kernels fit one wave");
-__global__ void __launch_bounds__(64) k_mt_node(MtProblem P, MtState st) {
+template <typename PT>
+__global__ void __launch_bounds__(64) k_mt_node(PT P, MtState st) {
   __shared__ MtNodeGrp LG[kMtNodeGroups];
   const int b = blockIdx.y, lane = threadIdx.x, N = P.N;
+  mt_model(P, b);
   if (st.scal[(size_t)b * kMtScal + kMtStatus] != 0.0) return;
   const int c = lane & 15;
   MtNodeGrp& L = LG[lane >> 4];
@@ -1379,8 +1426,8 @@ __device__ __forceinline__ void mt_block_reduce_n(double (&v)[NV], const int (&o
 // k_mt_prepare2 (one workgroup per instance, after k_mt_node): convergence test and barrier update as k_mt_prepare (the stationarity
 // residual comes per node from k_mt_node), then the right-hand side rhs = rhs0 - mu r1.  (Measured: as a prologue of the elimination
 // kernel instead of a kernel of its own it is 1.5 % faster for 1024 instances and 13 % slower for 256: a kernel of its own.)
-template <int BLOCK>
-__device__ __forceinline__ bool mt_prepare2(const MtProblem& P, const MtState& st, int b, int tid, double* red) {
+template <int BLOCK, typename PT>
+__device__ __forceinline__ bool mt_prepare2(const PT& P, const MtState& st, int b, int tid, double* red) {
   const int N = P.N;
   double* scal = st.scal + (size_t)b * kMtScal;
   const double* w = st.w + (size_t)b * N * kMtNv;
@@ -1432,8 +1479,10 @@ __device__ __forceinline__ bool mt_prepare2(const MtProblem& P, const MtState& s
 }
 
 
-__global__ void __launch_bounds__(256) k_mt_prepare2(MtProblem P, MtState st) {
+template <typename PT>
+__global__ void __launch_bounds__(256) k_mt_prepare2(PT P, MtState st) {
   __shared__ double red[5 * 4];
+  mt_model(P, blockIdx.x);
   if (st.scal[(size_t)blockIdx.x * kMtScal + kMtStatus] != 0.0) return;
   (void)mt_prepare2<256>(P, st, blockIdx.x, threadIdx.x, red);
 }
@@ -1969,8 +2018,10 @@ __global__ void __launch_bounds__(256, 2) k_mt_kkt4(MtProblem P, MtState st) {
 }
 
 // residuals only (final report of the instances that ran into the iteration limit)
-__global__ void __launch_bounds__(64) k_mt_residuals(MtProblem P, MtState st) {
+template <typename PT>
+__global__ void __launch_bounds__(64) k_mt_residuals(PT P, MtState st) {
   const int b = blockIdx.x, lane = threadIdx.x, N = P.N;
+  mt_model(P, b);
   double* scal = st.scal + (size_t)b * kMtScal;
   if (scal[kMtStatus] == 1.0) return;
   mt_instance(P, b);
@@ -2107,7 +2158,8 @@ __global__ void __launch_bounds__(64) k_mt_dir(MtProblem P, MtState st) {
 }
 
 // (theta, phi) share of the pair j at the trial point w + a dw, s + a ds
-__device__ __forceinline__ void mt_trial_node(const MtProblem& P, const MtStepPtrs& q, int N, int j, double a, double mu,
+template <typename PT>
+__device__ __forceinline__ void mt_trial_node(const PT& P, const MtStepPtrs& q, int N, int j, double a, double mu,
                                               double& theta, double& phi) {
   const int jn = j + 1 == N ? 0 : j + 1;
   double wo[kMtNv], wn[kMtNv], eq[kMtNe], g[kMtNi];
@@ -2139,8 +2191,10 @@ __device__ __forceinline__ void mt_trial_node(const MtProblem& P, const MtStepPt
 #define RL_MT_TRIALS 1
 #endif
 constexpr int kMtTrials = RL_MT_TRIALS;
-__global__ void __launch_bounds__(64) k_mt_trial(MtProblem P, MtState st) {
+template <typename PT>
+__global__ void __launch_bounds__(64) k_mt_trial(PT P, MtState st) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y, N = P.N;
+  mt_model(P, b);
   const MtStepPtrs q = mt_step_ptrs(st, b, N);
   if (q.scal[kMtStatus] != 0.0) return;
   // the primal step length: every workgroup takes the minimum over the shares of k_mt_dir itself (220 values; a minimum does not depend on the order)
@@ -2222,8 +2276,10 @@ __global__ void __launch_bounds__(256, 2) k_mt_step(MtProblem P, MtState st) {
 }
 
 // grid as k_mt_trial: for the instances k_mt_step has marked, the trial points ap / 2 and ap / 4 per node -> vec[b][j][2 .. 5]
-__global__ void __launch_bounds__(64) k_mt_trial_b(MtProblem P, MtState st) {
+template <typename PT>
+__global__ void __launch_bounds__(64) k_mt_trial_b(PT P, MtState st) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y, N = P.N;
+  mt_model(P, b);
   const MtStepPtrs q = mt_step_ptrs(st, b, N);
   if (q.scal[kMtStatus] != 0.0 || q.scal[15] == 0.0) return;
   if (j >= N) return;
@@ -2240,9 +2296,11 @@ __global__ void __launch_bounds__(64) k_mt_trial_b(MtProblem P, MtState st) {
   }
 }
 
-__global__ void __launch_bounds__(256, 2) k_mt_step_b(MtProblem P, MtState st) {
+template <typename PT>
+__global__ void __launch_bounds__(256, 2) k_mt_step_b(PT P, MtState st) {
   __shared__ double red[4 * 4];
   const int b = blockIdx.x, tid = threadIdx.x, N = P.N;
+  mt_model(P, b);
   const MtStepPtrs q = mt_step_ptrs(st, b, N);
   if (q.scal[kMtStatus] != 0.0 || q.scal[15] == 0.0) return;
   mt_instance(P, b);
@@ -2302,8 +2360,10 @@ __global__ void __launch_bounds__(256, 2) k_mt_step_b(MtProblem P, MtState st) {
 }
 
 // physical X [B,N,6], U [B,N,4], T [B,N]  <->  scaled unknowns w [B,N,9]
-__global__ void k_mt_pack(MtProblem P, MtState st, const double* X, const double* U, const double* T) {
+template <typename PT>
+__global__ void k_mt_pack(PT P, MtState st, const double* X, const double* U, const double* T) {
   const int b = blockIdx.y, j = blockIdx.x * blockDim.x + threadIdx.x, N = P.N;
+  mt_model(P, b);
   if (j >= N) return;
   const size_t o = (size_t)b * N + j;
   double* w = st.w + o * kMtNv;
@@ -2311,8 +2371,10 @@ __global__ void k_mt_pack(MtProblem P, MtState st, const double* X, const double
   w[5] = U[o * 4 + 0] / P.sw[5]; w[6] = U[o * 4 + 2] / P.sw[6]; w[7] = U[o * 4 + 3] / P.sw[7];
   w[8] = T[o] / P.sw[8];
 }
-__global__ void k_mt_unpack(MtProblem P, MtState st, double* X, double* U, double* T) {
+template <typename PT>
+__global__ void k_mt_unpack(PT P, MtState st, double* X, double* U, double* T) {
   const int b = blockIdx.y, j = blockIdx.x * blockDim.x + threadIdx.x, N = P.N;
+  mt_model(P, b);
   if (j >= N) return;
   const size_t o = (size_t)b * N + j;
   const double* w = st.w + o * kMtNv;

@@ -49,6 +49,45 @@ from .. import ops
 from ..models.trajectory import Trajectory
 
 
+def vehicle_margins(models, default=None):
+    """margin_b = vehicle_width / 2 + safety_margin (:134) of B model dicts -> float64 [B].  Rows of an array carry no
+    such keys: `default` (the margin of the problem's own model) for every instance then."""
+    if len(models) > 0 and isinstance(models[0], dict):
+        return np.array([m["vehicle_width"] / 2.0 + m["safety_margin"] for m in models], dtype=np.float64)
+    if default is None:
+        raise ValueError("models: an array has no vehicle_width / safety_margin; pass dicts or a margin")
+    return np.full(len(models), float(default))
+
+
+def fold_margins(left, right, margins):
+    """The solver takes ONE margin per call; vehicles of different widths get theirs folded into their boundary distances:
+    (left - m_b, right + m_b) [B,N], to be passed with margin = 0.  These are the sums the kernels form themselves
+    (left - margin, right + margin), so the folded call sees the same doubles.  left / right [N] or [B,N], numpy arrays
+    or torch tensors; margins [B] (numpy)."""
+    m = np.asarray(margins, dtype=np.float64)
+    if isinstance(left, np.ndarray):
+        col = m[:, None]
+    else:
+        import torch
+        col = torch.from_numpy(m).to(left.device)[:, None]
+    if left.ndim == 1:
+        left, right = left[None], right[None]
+    if left.shape[0] not in (1, len(m)):
+        raise ValueError(f"left / right: {left.shape[0]} instances for {len(m)} vehicles")
+    return left - col, right + col
+
+
+def _solver_margin(models, B, left, right, default):
+    """(table [B,28], left, right, margin) of a vehicles call: one shared margin when all vehicles have the same, folded
+    margins and 0 otherwise."""
+    table = ops.dt_models_table(models, B)
+    m = vehicle_margins(models, default)
+    if np.all(m == m[0]):
+        return table, left, right, float(m[0])
+    left, right = fold_margins(left, right, m)
+    return table, left, right, 0.0
+
+
 class DoubleTrackProblem:
     def __init__(self, params):
         self.params = params
@@ -97,15 +136,24 @@ class DoubleTrackProblem:
         X, U, T, st = self.solve_batch(self.left[None], self.right[None], max_iter=max_iter, tol=tol)
         return X[0], U[0], T[0], st[0]
 
-    def solve_batch(self, left, right, X0=None, U0=None, T0=None, max_iter=None, tol=None):
+    def solve_batch(self, left, right, X0=None, U0=None, T0=None, max_iter=None, tol=None, models=None):
         """B instances that differ in their boundary distances left/right [B,N] (and optionally in their initial
-        guesses).  The reference's IPOPT tolerance `tol` (yaml :8) is a loose 0.1; the default here is 1e-6."""
+        guesses).  The reference's IPOPT tolerance `tol` (yaml :8) is a loose 0.1; the default here is 1e-6.
+        models: None, or B model dicts (or an array [B, len(ops.DT_PARAMS)]): instance b is then solved for vehicle b
+        (ops.mintime_solve_vehicles) instead of for the problem's own model; vehicles of different vehicle_width /
+        safety_margin get their margins folded into left / right (fold_margins).  The initial guesses stay the problem's."""
         left = np.ascontiguousarray(left, dtype=np.float64); right = np.ascontiguousarray(right, dtype=np.float64)
         B = left.shape[0]
         rep = lambda a: np.repeat(np.asarray(a)[None], B, axis=0)  # noqa: E731
         X0 = rep(self.X0) if X0 is None else X0
         U0 = rep(self.U0) if U0 is None else U0
         T0 = rep(self.T0) if T0 is None else T0
+        if models is not None:
+            table, left, right, margin = _solver_margin(models, B, left, right, self.margin)
+            return ops.mintime_solve_vehicles(table, self.s, self.kappa, np.ascontiguousarray(left), np.ascontiguousarray(right),
+                                              margin, self.track_length, X0, U0, T0, self.average_track_width, self.speed_cap,
+                                              max_iter=int(max_iter or self.params.get("max_iter", 200)),
+                                              tol=float(tol if tol is not None else 1e-6))
         return ops.mintime_solve_batch(self.model, self.s, self.kappa, left, right, self.margin, self.track_length,
                                        X0, U0, T0, self.average_track_width, self.speed_cap,
                                        max_iter=int(max_iter or self.params.get("max_iter", 200)),
@@ -328,7 +376,7 @@ def pose_table(race_track, traj_d, X):
 
 
 def optimise_track_batch(race_track, vehicle, model, left=None, right=None, average_track_width=7.0, speed_cap=30.0,
-                         max_iter=200, tol=1e-6, device=None, track=None, start_points=None):
+                         max_iter=200, tol=1e-6, device=None, track=None, start_points=None, models=None, vehicles=None):
     """optimise_track for B instances of one track that differ in their boundary distances, as ONE chain on torch's current
     stream with device tensors throughout: QSS warm start (k_qss_sim) -> initial guess -> NLP solve (k_mt_*) -> tables of
     the batch (k_pose_tables) -> their summary (k_table_summary).  No result travels to the host in between; the host set-up is
@@ -345,12 +393,24 @@ def optimise_track_batch(race_track, vehicle, model, left=None, right=None, aver
     batch.lap_times_torch(...)["points"] of a min-curvature batch on the same track: instance b then starts from line b
     projected onto the centre line (batch.min_time_guess_from_lines_torch) instead of from the centre line, and the result
     gains "start_status" (int32 [B]: 0 = started from its line, otherwise from the centre line, see that function).
+    models: None, or B model dicts: instance b is solved for vehicle b (ops.mintime_solve_vehicles_torch) and `model` is not
+    read.  B must agree with left / right when those are given; otherwise the track's own distances are repeated B times.
+    Vehicles of different vehicle_width / safety_margin get their margins folded into the distances the solver sees
+    (fold_margins); the tables keep the distances as given.
+    vehicles: None, or B QSS vehicles (Vehicles or 5-tuples, batch.vehicle_tables_batch), with `models` only: the warm start is
+    then one QSS run per instance (ops.qss_sim_vehicles_torch), `base` is [B,N,19] and `vehicle` is not read.
     Returns dict(points [B,N,19], X [B,N,6], U [B,N,4], T [B,N], stats [B,12], summary [B,8]) of cuda tensors plus "track":
     stats as include/rl_mincurv.h: rl_mintime_solve_batch, summary in the order of ops.SUMMARY_COLUMNS (summary[:, 0] is the
     lap time)."""
     import torch
     from .. import _lib, batch
     from ..models.trajectory import _ring_coords
+    if vehicles is not None and models is None:
+        raise ValueError("vehicles: one QSS vehicle per instance goes with models=, one NLP model per instance")
+    if vehicles is not None and start_points is not None:
+        raise ValueError("start_points with vehicles=: the guess from lines takes one centre-line table, not one per instance")
+    if models is not None:
+        ops.dt_models_table(models)   # a bad row is refused before anything is set up
     dev = torch.device("cuda", _lib.Context.get(device).device)
     up = lambda a: a.to(dev).contiguous() if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)  # noqa: E731
     if (left is None) != (right is None):
@@ -359,18 +419,31 @@ def optimise_track_batch(race_track, vehicle, model, left=None, right=None, aver
     race_track.fill_trajectory_boundaries(traj_d)
     N = len(traj_d)
     s = np.ascontiguousarray(race_track.abscissa, dtype=np.float64)
-    margin = model["vehicle_width"] / 2.0 + model["safety_margin"]
     if left is None:
         left_d, right_d = up(np.asarray(race_track.left_intp(s))[None]), up(np.asarray(race_track.right_intp(s))[None])
+        if models is not None:
+            left_d, right_d = left_d.repeat(len(models), 1), right_d.repeat(len(models), 1)
     else:
         left_d, right_d = up(left), up(right)
     B = int(left_d.shape[0])
     if tuple(left_d.shape) != (B, N) or tuple(right_d.shape) != (B, N):
         raise ValueError(f"left / right: expected [B,{N}]")
-    # QSS warm start: the simulated centre-line table is the same for every instance
-    base = up(traj_d.points)[None].contiguous()
-    ops.qss_sim_torch(base, *batch.vehicle_tables(vehicle))
-    base = base[0]
+    if models is None:
+        margin = model["vehicle_width"] / 2.0 + model["safety_margin"]
+    else:
+        if len(models) != B:
+            raise ValueError(f"models: {len(models)} vehicles for {B} instances of left / right")
+        table, left_s, right_s, margin = _solver_margin(models, B, left_d, right_d, None)
+        left_s, right_s = left_s.contiguous(), right_s.contiguous()
+    if vehicles is None:
+        # QSS warm start: the simulated centre-line table is the same for every instance
+        base = up(traj_d.points)[None].contiguous()
+        ops.qss_sim_torch(base, *batch.vehicle_tables(vehicle))
+        base = base[0]
+    else:
+        veh = batch._vehicles_stacked(vehicles, B, dev)
+        base = up(traj_d.points)[None].repeat(B, 1, 1).contiguous()
+        ops.qss_sim_vehicles_torch(base, *veh)
     # initial guess (min_time_optimizer.py:146-151 as written; DoubleTrackProblem's "reference" mode)
     s_d = up(s)
     kappa_d = up(race_track.curvature_intp(s))
@@ -383,9 +456,14 @@ def optimise_track_batch(race_track, vehicle, model, left=None, right=None, aver
         if start_d.ndim != 3 or int(start_d.shape[0]) != B or int(start_d.shape[2]) != 19:
             raise ValueError(f"start_points: expected [{B},P,19]")
         X, U, T, start_status = batch.min_time_guess_from_lines_torch(race_track, start_d, s_d, kappa_d, base, pieces=pieces)
-    stats = ops.mintime_solve_torch(dict(model), s_d, kappa_d, left_d, right_d, margin,
-                                    float(race_track.center_s.get_length()), X, U, T, float(average_track_width),
-                                    float(speed_cap), max_iter=int(max_iter), tol=float(tol))
+    if models is None:
+        stats = ops.mintime_solve_torch(dict(model), s_d, kappa_d, left_d, right_d, margin,
+                                        float(race_track.center_s.get_length()), X, U, T, float(average_track_width),
+                                        float(speed_cap), max_iter=int(max_iter), tol=float(tol))
+    else:
+        stats = ops.mintime_solve_vehicles_torch(table, s_d, kappa_d, left_s, right_s, margin,
+                                                 float(race_track.center_s.get_length()), X, U, T, float(average_track_width),
+                                                 float(speed_cap), max_iter=int(max_iter), tol=float(tol))
     if track is None:
         track = batch.make_track(race_track.center_s, N, device=dev.index)
     elif track.N != N:

@@ -1001,6 +1001,78 @@ def mintime_solve_torch(model, s, kappa, left, right, margin, track_length, X, U
     return stats
 
 
+_DT_POSITIVE = ("Fd_max", "delta_max", "mass", "Pmax", "mu", "Td", "Tb", "Tdelta")   # and |Fb_max|: what the library checks per row
+
+
+def dt_models_table(models, B=None):
+    """B vehicle models -> the [B, len(DT_PARAMS)] float64 array rl_mintime_solve_vehicles* takes.  `models`: a sequence
+    of B model dicts (the reference's keys) or an array of that shape.  Checks what the library checks, before anything
+    reaches it: B (when given), every row finite, and Fd_max, |Fb_max|, delta_max, mass, Pmax, mu, Td, Tb, Tdelta > 0 --
+    a ValueError names the first bad instance."""
+    if len(models) > 0 and isinstance(models[0], dict):
+        tab = np.array([[float(m[k]) for k in DT_PARAMS] for m in models], dtype=np.float64)
+    else:
+        tab = np.array(models, dtype=np.float64, order="C")
+    if tab.ndim != 2 or tab.shape[1] != len(DT_PARAMS) or tab.shape[0] == 0:
+        raise ValueError(f"models: expected B dicts or an array [B, {len(DT_PARAMS)}], got shape {tab.shape}")
+    if B is not None and tab.shape[0] != B:
+        raise ValueError(f"models: {tab.shape[0]} vehicles for a batch of {B} instances")
+    for b, row in enumerate(tab):
+        if not np.all(np.isfinite(row)):
+            raise ValueError(f"models: instance {b}: parameter {DT_PARAMS[int(np.flatnonzero(~np.isfinite(row))[0])]} is not finite")
+        if not abs(row[DT_PARAMS.index("Fb_max")]) > 0.0:
+            raise ValueError(f"models: instance {b}: |Fb_max| must be > 0")
+        for k in _DT_POSITIVE:
+            if not row[DT_PARAMS.index(k)] > 0.0:
+                raise ValueError(f"models: instance {b}: {k} must be > 0")
+    return np.ascontiguousarray(tab)
+
+
+def mintime_solve_vehicles(models, s, kappa, left, right, margin, track_length, X0, U0, T0, average_track_width=7.0,
+                           speed_cap=30.0, max_iter=120, tol=1e-6, device=None):
+    """mintime_solve_batch with ONE VEHICLE PER INSTANCE (include/rl_mincurv.h: rl_mintime_solve_vehicles): `models` is a
+    sequence of B model dicts or an array [B, len(DT_PARAMS)]; the variable scaling of instance b uses its own model;
+    margin, average_track_width and speed_cap stay shared.  Everything else, and the result, as mintime_solve_batch."""
+    X = np.array(X0, dtype=np.float64, copy=True, order="C"); U = np.array(U0, dtype=np.float64, copy=True, order="C")
+    T = np.array(T0, dtype=np.float64, copy=True, order="C")
+    B, N = T.shape
+    tab = dt_models_table(models, B)
+    assert X.shape == (B, N, 6) and U.shape == (B, N, 4)
+    s, sp = as_d(s); kappa, kp = as_d(kappa); left, lp = as_d(left); right, rp = as_d(right)
+    per = left.ndim == 2
+    assert left.shape == right.shape == ((B, N) if per else (N,)) and len(s) == len(kappa) == N
+    ctx = Context.get(device)
+    stats = np.zeros((B, 12))
+    check(ctx.lib.rl_mintime_solve_vehicles(ctx.h, tab.ctypes.data_as(_dp), B, N, sp, kp, lp, rp, int(per), float(margin),
+                                            float(track_length), float(average_track_width), float(speed_cap),
+                                            X.ctypes.data_as(_dp), U.ctypes.data_as(_dp), T.ctypes.data_as(_dp),
+                                            int(max_iter), float(tol), stats.ctypes.data_as(_dp)))
+    return X, U, T, stats
+
+
+def mintime_solve_vehicles_torch(models, s, kappa, left, right, margin, track_length, X, U, T, average_track_width=7.0,
+                                 speed_cap=30.0, max_iter=120, tol=1e-6):
+    """mintime_solve_torch with one vehicle per instance (rl_mintime_solve_vehicles_dev): `models` as in
+    mintime_solve_vehicles -- a HOST table, read before the call returns; the tensors as in mintime_solve_torch."""
+    import torch
+    dev = X.device
+    B, N = T.shape
+    tab = dt_models_table(models, B)
+    for t_ in (s, kappa, left, right, X, U, T):
+        assert t_.is_cuda and t_.dtype == torch.float64 and t_.is_contiguous()
+    assert tuple(X.shape) == (B, N, 6) and tuple(U.shape) == (B, N, 4) and s.shape[0] == kappa.shape[0] == N
+    per = left.dim() == 2
+    assert tuple(left.shape) == tuple(right.shape) == ((B, N) if per else (N,))
+    ctx = Context.get(dev.index)
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    stats = torch.empty((B, 12), dtype=torch.float64, device=dev)
+    p = lambda t_: ctypes.c_void_p(t_.data_ptr())  # noqa: E731
+    check(ctx.lib.rl_mintime_solve_vehicles_dev(ctx.h, tab.ctypes.data_as(_dp), B, N, p(s), p(kappa), p(left), p(right),
+                                                int(per), float(margin), float(track_length), float(average_track_width),
+                                                float(speed_cap), p(X), p(U), p(T), int(max_iter), float(tol), p(stats)))
+    return stats
+
+
 BK_PARAMS = ("lr", "L", "delta_max", "v_max", "a_lon_max", "a_lon_min", "delta_dot_max", "acc_max")   # rl_bk_param order
 
 

@@ -30,8 +30,29 @@ def parse(path):
     return {d: out[n] for n, d in zip(names, dem)}
 
 
+def renamed(before, after):
+    """A kernel that became a template over the type of one of its parameters has another demangled name with the same body:
+    `k(T, S)` -> `void k<T>(T, S)`, `void k<1>(T, S)` -> `void k<1, T>(T, S)`.  Such an instance is compared with the parent's
+    kernel of the old name when that name is gone from the new listing.  Returns {old name: new name}."""
+    out = {}
+    for name in after:
+        m = re.match(r"^void ([\w:]+)<(.*)>\((.*)\)$", name)
+        if name in before or not m:
+            continue
+        fn, targs, params = m.group(1), [a.strip() for a in m.group(2).split(",")], m.group(3)
+        first = params.split(",")[0].strip()
+        if targs[-1] != first:
+            continue
+        old = f"{fn}({params})" if len(targs) == 1 else f"void {fn}<{', '.join(targs[:-1])}>({params})"
+        if old in before and old not in after:
+            out[old] = name
+    return out
+
+
 def main():
     before, after = parse(sys.argv[1]), parse(sys.argv[2])
+    same_body = renamed(before, after)
+    after = {k: v for k, v in after.items() if k not in same_body.values()} | {old: after[new] for old, new in same_body.items()}
     changed = [k for k in before if k not in after or after[k] != before[k]]
     new = [k for k in after if k not in before]
     res = {
@@ -42,6 +63,7 @@ def main():
         "flags": "-O3 -std=c++17 --offload-arch=gfx950 --cuda-device-only -S",
         "kernels_before": len(before), "kernels_after": len(after),
         "existing_kernels_unchanged": not changed, "existing_kernels_changed": changed,
+        "kernels_now_templates": same_body,   # listed under their old names in "after"
         "new_kernels": new, "new_kernels_resources": {k: after[k] for k in new},
         "before": before, "after": after,
     }

@@ -3,6 +3,7 @@
 The HIP library is the product; there is no CPU fallback anywhere in this package.  If the shared
 object is missing, or no MI355X/HIP device is usable, every compute entry point raises.
 """
+import contextlib
 import ctypes
 import os
 import threading
@@ -35,115 +36,103 @@ class RlError(RuntimeError):
     pass
 
 
+_i, _d = ctypes.c_int, ctypes.c_double
+_st = ctypes.POINTER(Stats)
+_D, _I = object(), object()   # an argument in the entry's memory space: double* / int* of a _host entry, void* of its _dev twin
+
+
+def _host(args):
+    return _i, [_dp if a is _D else _ip if a is _I else a for a in args]
+
+
+def _dev(args):
+    return _i, [_vp if a is _D or a is _I else a for a in args]
+
+
+# the argument list of each _host / _dev pair, once; plain _dp / _ip is a host pointer in both (model vector, models table,
+# shared i_start, region tables, the QSS lookup tables of rl_qss_sim_dev)
+_SOLVE_BATCH = [_vp, _vp, _i, _D, _i, _ip, _i, _i, _D, _D, _I, _I, _st]
+_SOLVE_BATCH_FROM = [_vp, _vp, _i, _D, _i, _D, _I, _i, _i, _i, _D, _D, _I, _I, _st]   # and _joint_
+_SPLINE_FIT = [_vp, _vp, _D, _i, _i, _i, _D, _i, _D, _D]
+_DT_EVAL = [_vp, _dp, _i, _i, _dp, _dp, _dp, _dp, _d, _d, _dp, _dp, _dp, _dp, _dp, _dp]
+_MINTIME_SOLVE = [_vp, _dp, _i, _i, _D, _D, _D, _D, _i, _d, _d, _d, _d, _D, _D, _D, _i, _d, _D]   # and _vehicles
+_BICYCLE_SOLVE = [_vp, _dp, _i, _i, _D, _D, _D, _D, _i, _D, _D, _D, _i, _d, _D]
+_QSS_SIM = [_vp, _D, _i, _i, _dp, _dp, _i, _dp, _dp, _i, _dp, _I]
+_QSS_SIM_VEHICLES = [_vp, _D, _i, _i, _D, _D, _i, _D, _D, _i, _D, _I]
+_GLOBAL = [_vp, _vp, _D, _i, _d, _i, _D, _D, _D, _D, _st]
+_GLOBAL_XY = [_vp, _vp, _D, _i, _d, _d, _i, _D, _D, _D, _D, _st]
+_TABLES = [_vp, _vp, _D, _i, _i, _D, _d, _D, _i, _D]
+_POSE_TABLES = [_vp, _vp, _i, _D, _i, _i, _D, _D, _D, _i, _i, _D, _D, _i, _D, _D]
+_FRENET = [_vp, _D, _i, _i, _i, _D, _D, _D, _D, _i, _D, _I, _D]
+_FRENET_RESAMPLE = [_vp, _D, _D, _i, _i, _i, _D, _i, _d, _D, _I]
+_TABLE_SUMMARY = [_vp, _D, _i, _i, _I, _D]
+_SWEEP = [_vp, _vp, _ip, _i, _dp, _dp, _dp, _ip, _st]
+
 # every symbol include/rl_mincurv.h declares: (restype, argtypes)
 _SIGNATURES = {
-    "rl_version": (ctypes.c_int, []),
+    "rl_version": (_i, []),
     "rl_last_error": (ctypes.c_char_p, []),
-    "rl_debug_dump_enable": (ctypes.c_int, [ctypes.c_int]),
-    "rl_debug_read": (ctypes.c_int, [_dp, ctypes.c_longlong]),
-    "rl_ctx_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(_vp)]),
+    "rl_debug_dump_enable": (_i, [_i]),
+    "rl_debug_read": (_i, [_dp, ctypes.c_longlong]),
+    "rl_ctx_create": (_i, [_i, ctypes.POINTER(_vp)]),
     "rl_ctx_destroy": (None, [_vp]),
-    "rl_ctx_set_stream": (ctypes.c_int, [_vp, _vp]),
-    "rl_ctx_synchronize": (ctypes.c_int, [_vp]),
-    "rl_ctx_set_arith": (ctypes.c_int, [_vp, ctypes.c_int]),
-    "rl_ctx_get_arith": (ctypes.c_int, [_vp]),
-    "rl_ctx_set_numpy_raise": (ctypes.c_int, [_vp, ctypes.c_int]),
-    "rl_ctx_set_option": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_int]),
-    "rl_debug_cr_heading": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int, _dp]),
-    "rl_spline_eval": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _dp, ctypes.c_int, _dp,
-                                      ctypes.c_int, ctypes.c_int, _dp]),
-    "rl_sample_along": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _dp, ctypes.c_int,
-                                       ctypes.c_double, _dp, ctypes.c_int, _dp]),
-    "rl_fill_bounds": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, ctypes.c_int, _dp, ctypes.c_int,
-                                      ctypes.c_double]),
-    "rl_fill_region": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _dp, _ip, ctypes.c_int, _ip]),
-    "rl_region_index_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _ip, ctypes.c_int, _vp]),
-    "rl_track_create": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _dp, ctypes.c_int, ctypes.c_int,
-                                       ctypes.POINTER(_vp)]),
+    "rl_ctx_set_stream": (_i, [_vp, _vp]),
+    "rl_ctx_synchronize": (_i, [_vp]),
+    "rl_ctx_set_arith": (_i, [_vp, _i]),
+    "rl_ctx_get_arith": (_i, [_vp]),
+    "rl_ctx_set_numpy_raise": (_i, [_vp, _i]),
+    "rl_ctx_set_option": (_i, [_vp, ctypes.c_char_p, _i]),
+    "rl_debug_cr_heading": (_i, [_vp, _dp, _dp, _i, _dp]),
+    "rl_spline_eval": (_i, [_vp, _dp, _i, _dp, _dp, _i, _dp, _i, _i, _dp]),
+    "rl_sample_along": (_i, [_vp, _dp, _i, _dp, _dp, _i, _d, _dp, _i, _dp]),
+    "rl_fill_bounds": (_i, [_vp, _dp, _i, _dp, _i, _dp, _i, _d]),
+    "rl_fill_region": (_i, [_vp, _dp, _i, _i, _dp, _ip, _i, _ip]),
+    "rl_region_index_dev": (_i, [_vp, _vp, _i, _i, _i, _dp, _ip, _i, _vp]),
+    "rl_track_create": (_i, [_vp, _dp, _i, _dp, _dp, _i, _i, ctypes.POINTER(_vp)]),
     "rl_track_destroy": (None, [_vp]),
-    "rl_track_set_rings": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, ctypes.c_int]),
-    "rl_track_set_control_points": (ctypes.c_int, [_vp, _dp, _dp]),
-    "rl_track_set_length": (ctypes.c_int, [_vp, ctypes.c_double]),
-    "rl_mincurv_cost": (ctypes.c_int, [_vp, _vp, _ip, ctypes.c_int, _dp, _dp, _dp, _ip]),
-    "rl_mincurv_cost_weighted": (ctypes.c_int, [_vp, _vp, _ip, ctypes.c_int, _dp, _dp, _dp, _dp, _ip]),
-    "rl_track_constraint": (ctypes.c_int, [_vp, _vp, _dp, ctypes.c_int, _dp, _dp, _dp, _ip]),
-    "rl_mincurv_sweep": (ctypes.c_int, [_vp, _vp, _ip, ctypes.c_int, _dp, _dp, _dp, _ip,
-                                        ctypes.POINTER(Stats)]),
-    "rl_mincurv_sweep_joint": (ctypes.c_int, [_vp, _vp, _ip, ctypes.c_int, _dp, _dp, _dp, _ip,
-                                              ctypes.POINTER(Stats)]),
-    "rl_mincurv_solve_batch_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, _ip,
-                                                  ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp,
-                                                  ctypes.POINTER(Stats)]),
-    "rl_mincurv_solve_batch_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, ctypes.c_int, _ip,
-                                                   ctypes.c_int, ctypes.c_int, _dp, _dp, _ip, _ip,
-                                                   ctypes.POINTER(Stats)]),
-    "rl_mincurv_solve_batch_from_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int,
-                                                       ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.POINTER(Stats)]),
-    "rl_mincurv_solve_batch_from_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, ctypes.c_int, _dp, _ip, ctypes.c_int,
-                                                        ctypes.c_int, ctypes.c_int, _dp, _dp, _ip, _ip, ctypes.POINTER(Stats)]),
-    "rl_mincurv_solve_batch_joint_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int,
-                                                        ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.POINTER(Stats)]),
-    "rl_mincurv_solve_batch_joint_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, ctypes.c_int, _dp, _ip, ctypes.c_int,
-                                                         ctypes.c_int, ctypes.c_int, _dp, _dp, _ip, _ip, ctypes.POINTER(Stats)]),
-    "rl_spline_fit_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
-                                               _vp, _vp]),
-    "rl_spline_fit_batch_host": (ctypes.c_int, [_vp, _vp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_int,
-                                                _dp, _dp]),
-    "rl_dt_eval_nodes": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_double,
-                                        ctypes.c_double, _dp, _dp, _dp, _dp, _dp, _dp]),
-    "rl_dt_eval_jac": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_double,
-                                      ctypes.c_double, _dp, _dp, _dp, _dp, _dp, _dp]),
-    "rl_mintime_solve_batch": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int,
-                                              ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _dp, _dp,
-                                              _dp, ctypes.c_int, ctypes.c_double, _dp]),
-    "rl_mintime_solve_batch_dev": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int,
-                                                  ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp, _vp,
-                                                  _vp, ctypes.c_int, ctypes.c_double, _vp]),
-    "rl_mintime_solve_vehicles": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int,
-                                                 ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _dp, _dp,
-                                                 _dp, ctypes.c_int, ctypes.c_double, _dp]),
-    "rl_mintime_solve_vehicles_dev": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int,
-                                                     ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp,
-                                                     _vp, _vp, ctypes.c_int, ctypes.c_double, _vp]),
-    "rl_bicycle_eval_nodes": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
-    "rl_bicycle_solve_batch": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int, _dp, _dp,
-                                              _dp, ctypes.c_int, ctypes.c_double, _dp]),
-    "rl_bicycle_solve_batch_dev": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int, _vp,
-                                                  _vp, _vp, ctypes.c_int, ctypes.c_double, _vp]),
-    "rl_qss_sim_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_int, _dp, _dp,
-                                      ctypes.c_int, _dp, _vp]),
-    "rl_mincurv_global_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_int,
-                                                   _vp, _vp, _vp, _vp, ctypes.POINTER(Stats)]),
-    "rl_mincurv_global_batch_host": (ctypes.c_int, [_vp, _vp, _dp, ctypes.c_int, ctypes.c_double,
-                                                    ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.POINTER(Stats)]),
-    "rl_qss_sim": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_int, _dp, _dp,
-                                  ctypes.c_int, _dp, _ip]),
-    "rl_qss_sim_vehicles_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp,
-                                               ctypes.c_int, _vp, _vp]),
-    "rl_qss_sim_vehicles_host": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_int, _dp, _dp,
-                                                ctypes.c_int, _dp, _ip]),
-    "rl_mincurv_global_xy_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int,
-                                                      _vp, _vp, _vp, _vp, ctypes.POINTER(Stats)]),
-    "rl_mincurv_global_xy_batch_host": (ctypes.c_int, [_vp, _vp, _dp, ctypes.c_int, ctypes.c_double, ctypes.c_double,
-                                                       ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.POINTER(Stats)]),
-    "rl_tables_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_double, _vp,
-                                           ctypes.c_int, _vp]),
-    "rl_tables_batch_host": (ctypes.c_int, [_vp, _vp, _dp, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_double, _dp,
-                                            ctypes.c_int, _dp]),
-    "rl_pose_tables_batch_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp,
-                                                ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp]),
-    "rl_pose_tables_batch_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp,
-                                                 ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_int, _dp, _dp]),
-    "rl_frenet_batch_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int,
-                                           _vp, _vp, _vp]),
-    "rl_frenet_batch_host": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int,
-                                            _dp, _ip, _dp]),
-    "rl_frenet_resample_dev": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
-                                              ctypes.c_double, _vp, _vp]),
-    "rl_frenet_resample_host": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_int,
-                                               ctypes.c_double, _dp, _ip]),
-    "rl_table_summary_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp]),
-    "rl_table_summary_host": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _ip, _dp]),
+    "rl_track_set_rings": (_i, [_vp, _dp, _i, _dp, _i]),
+    "rl_track_set_control_points": (_i, [_vp, _dp, _dp]),
+    "rl_track_set_length": (_i, [_vp, _d]),
+    "rl_mincurv_cost": (_i, [_vp, _vp, _ip, _i, _dp, _dp, _dp, _ip]),
+    "rl_mincurv_cost_weighted": (_i, [_vp, _vp, _ip, _i, _dp, _dp, _dp, _dp, _ip]),
+    "rl_track_constraint": (_i, [_vp, _vp, _dp, _i, _dp, _dp, _dp, _ip]),
+    "rl_mincurv_sweep": (_i, _SWEEP),
+    "rl_mincurv_sweep_joint": (_i, _SWEEP),
+    "rl_mincurv_solve_batch_dev": _dev(_SOLVE_BATCH),
+    "rl_mincurv_solve_batch_host": _host(_SOLVE_BATCH),
+    "rl_mincurv_solve_batch_from_dev": _dev(_SOLVE_BATCH_FROM),
+    "rl_mincurv_solve_batch_from_host": _host(_SOLVE_BATCH_FROM),
+    "rl_mincurv_solve_batch_joint_dev": _dev(_SOLVE_BATCH_FROM),
+    "rl_mincurv_solve_batch_joint_host": _host(_SOLVE_BATCH_FROM),
+    "rl_spline_fit_batch_dev": _dev(_SPLINE_FIT),
+    "rl_spline_fit_batch_host": _host(_SPLINE_FIT),
+    "rl_dt_eval_nodes": (_i, _DT_EVAL),
+    "rl_dt_eval_jac": (_i, _DT_EVAL),
+    "rl_mintime_solve_batch": _host(_MINTIME_SOLVE),
+    "rl_mintime_solve_batch_dev": _dev(_MINTIME_SOLVE),
+    "rl_mintime_solve_vehicles": _host(_MINTIME_SOLVE),
+    "rl_mintime_solve_vehicles_dev": _dev(_MINTIME_SOLVE),
+    "rl_bicycle_eval_nodes": (_i, [_vp, _dp, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "rl_bicycle_solve_batch": _host(_BICYCLE_SOLVE),
+    "rl_bicycle_solve_batch_dev": _dev(_BICYCLE_SOLVE),
+    "rl_qss_sim_dev": _dev(_QSS_SIM),
+    "rl_mincurv_global_batch_dev": _dev(_GLOBAL),
+    "rl_mincurv_global_batch_host": _host(_GLOBAL),
+    "rl_qss_sim": _host(_QSS_SIM),
+    "rl_qss_sim_vehicles_dev": _dev(_QSS_SIM_VEHICLES),
+    "rl_qss_sim_vehicles_host": _host(_QSS_SIM_VEHICLES),
+    "rl_mincurv_global_xy_batch_dev": _dev(_GLOBAL_XY),
+    "rl_mincurv_global_xy_batch_host": _host(_GLOBAL_XY),
+    "rl_tables_batch_dev": _dev(_TABLES),
+    "rl_tables_batch_host": _host(_TABLES),
+    "rl_pose_tables_batch_dev": _dev(_POSE_TABLES),
+    "rl_pose_tables_batch_host": _host(_POSE_TABLES),
+    "rl_frenet_batch_dev": _dev(_FRENET),
+    "rl_frenet_batch_host": _host(_FRENET),
+    "rl_frenet_resample_dev": _dev(_FRENET_RESAMPLE),
+    "rl_frenet_resample_host": _host(_FRENET_RESAMPLE),
+    "rl_table_summary_dev": _dev(_TABLE_SUMMARY),
+    "rl_table_summary_host": _host(_TABLE_SUMMARY),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -245,19 +234,14 @@ class Context:
         (include/rl_mincurv.h: rl_ctx_set_numpy_raise)."""
         check(self.lib.rl_ctx_set_numpy_raise(self.h, 1 if on else 0))
 
+    @contextlib.contextmanager
     def arith(self, arith):
         """with ctx.arith(ARITH_REFERENCE): ...  -- the sweep calls inside run in that arithmetic."""
-        ctx = self
-
-        class _Scope:
-            def __enter__(self_):
-                self_.old = ctx.set_arith(arith)
-                return ctx
-
-            def __exit__(self_, *exc):
-                ctx.set_arith(self_.old)
-                return False
-        return _Scope()
+        old = self.set_arith(arith)
+        try:
+            yield self
+        finally:
+            self.set_arith(old)
 
 
 class Track:

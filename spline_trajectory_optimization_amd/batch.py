@@ -252,12 +252,7 @@ def lap_times_host(track, ctrl, bounds_form, bounds, length, vehicle=None, bank=
     import torch
     _one_of(vehicle, vehicles)
     veh = vehicle_tables(vehicle) if vehicles is None else None
-    B, bshape, kshape, _ = ops._tables_shapes(track, ctrl, bounds_form, bounds, bank)
-    ops._check_np(ctrl, "ctrl", (B, track.n, 2))
-    if bshape:
-        ops._check_np(bounds, "bounds", bshape)
-    if kshape:
-        ops._check_np(bank, "bank", kshape)
+    B = ops.check_tables_host(track, ctrl, bounds_form, bounds, bank)
     dev = torch.device("cuda", track.ctx.device)
     up = lambda a: None if a is None else torch.from_numpy(a).to(dev)  # noqa: E731
     if vehicles is not None:

@@ -375,6 +375,31 @@ int rl_mincurv_global_batch_host(rl_ctx* ctx, const rl_track* trk, const double*
                                  double margin, int n_outer, double* out_ctrl, double* out_xy,
                                  double* out_a, double* out_stats, rl_stats* stats);
 
+/* The same QP with a SPEED-WEIGHTED cost, one weight row per instance: sum_i w[b,i] kappa_i^2 -- the per-sample weight
+ * v = 1 / SPEED that the reference's cost carries and never switches on (optimization/optimizer.py:71-76), so that every
+ * vehicle of a batch gets its own line.  The weight enters the Gauss-Newton partials alone: P = 2 G'WG (then scaled to trace
+ * n-k, plus 1e-9 I, as above) and q = 2 G'W(kappa - G a); rows, bounds, interior point and exit rule are those of the entry above.
+ *   weights   [B,N], sample i of instance b as column SPEED of that instance's table; every weight finite and within
+ *             [2^-30, 2^30].  NULL = the entry above, bit for bit.
+ *             w = 1 everywhere returns the bits of the unweighted entry; a constant power of two returns the same out_ctrl,
+ *             out_xy, out_a (the trace scaling cancels it) and stats [1], [2] multiplied by it exactly.
+ *   out_stats [B,8] as above with [1], [2] = sum_i w_i kappa_i^2 before / after, and
+ *             [6] = number of weights of the instance outside the limits (NaN included); 0 for an accepted instance.
+ *   *_host checks every weight before anything is staged or enqueued: RL_ERR_ARG, the message names the first bad instance.
+ *   *_dev cannot read device memory on the host: the kernel checks the weights.  An instance with a refused weight runs as
+ *   n_outer = 0 -- out_ctrl / out_xy are the track's own line, out_a is zero, [0] = [4] = 0 -- reports the count in [6] and
+ *   leaves [1] and [2] UNSPECIFIED (they may be NaN); the other instances of the batch are not touched and the call
+ *   returns RL_OK.
+ * Dispatch and limits are those of the unweighted entry (the wave-specialised kernel, the generic one under RL_GLOBAL_V1=1 or
+ * where the fast path does not fit).  The two-coordinate formulation below (rl_mincurv_global_xy_batch_*) has NO weighted
+ * form.  CPU twin for tests: tests/weighted_global_twin.py. */
+int rl_mincurv_global_weighted_batch_dev(rl_ctx* ctx, const rl_track* trk, const double* widths, const double* weights, int B,
+                                         double margin, int n_outer, double* out_ctrl, double* out_xy, double* out_a,
+                                         double* out_stats, rl_stats* stats);
+int rl_mincurv_global_weighted_batch_host(rl_ctx* ctx, const rl_track* trk, const double* widths, const double* weights, int B,
+                                          double margin, int n_outer, double* out_ctrl, double* out_xy, double* out_a,
+                                          double* out_stats, rl_stats* stats);
+
 /* The same global problem with BOTH coordinates of every control point free -- the choice of unknowns and rows of the
  * reference's Julia prototype (julia/spline_traj_opt.ipynb L247-281: A = R blockdiag(B, B), one lateral and one longitudinal
  * row per sample; L410-412: Z = [c_x; c_y]; L276-279: bounds from the widths and +-1 m), with the corrections of SURVEY.md

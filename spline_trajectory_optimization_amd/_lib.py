@@ -14,7 +14,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RL_LIB_PATH") or os.path.join(_PKG, "librl_mincurv.so")  # RL_LIB_PATH: dev hook for A/B builds
 
 NCOL = 19
-WEIGHT_MIN, WEIGHT_MAX = 2.0 ** -30, 2.0 ** 30   # include/rl_mincurv.h: rl_mincurv_cost_weighted's allowed weights
+WEIGHT_MIN, WEIGHT_MAX = 2.0 ** -30, 2.0 ** 30   # include/rl_mincurv.h: the allowed weights of the weighted entries
 MAX_ITER = 32
 BOUNDS_SHARED_RINGS, BOUNDS_WIDTHS, BOUNDS_POINTS = 0, 1, 2
 SEARCH_BRUTE, SEARCH_CULLED, SEARCH_WINDOWED = 0, 1, 2
@@ -60,6 +60,7 @@ _BICYCLE_SOLVE = [_vp, _dp, _i, _i, _D, _D, _D, _D, _i, _D, _D, _D, _i, _d, _D]
 _QSS_SIM = [_vp, _D, _i, _i, _dp, _dp, _i, _dp, _dp, _i, _dp, _I]
 _QSS_SIM_VEHICLES = [_vp, _D, _i, _i, _D, _D, _i, _D, _D, _i, _D, _I]
 _GLOBAL = [_vp, _vp, _D, _i, _d, _i, _D, _D, _D, _D, _st]
+_GLOBAL_WEIGHTED = [_vp, _vp, _D, _D, _i, _d, _i, _D, _D, _D, _D, _st]
 _GLOBAL_XY = [_vp, _vp, _D, _i, _d, _d, _i, _D, _D, _D, _D, _st]
 _TABLES = [_vp, _vp, _D, _i, _i, _D, _d, _D, _i, _D]
 _POSE_TABLES = [_vp, _vp, _i, _D, _i, _i, _D, _D, _D, _i, _i, _D, _D, _i, _D, _D]
@@ -118,6 +119,8 @@ _SIGNATURES = {
     "rl_qss_sim_dev": _dev(_QSS_SIM),
     "rl_mincurv_global_batch_dev": _dev(_GLOBAL),
     "rl_mincurv_global_batch_host": _host(_GLOBAL),
+    "rl_mincurv_global_weighted_batch_dev": _dev(_GLOBAL_WEIGHTED),
+    "rl_mincurv_global_weighted_batch_host": _host(_GLOBAL_WEIGHTED),
     "rl_qss_sim": _host(_QSS_SIM),
     "rl_qss_sim_vehicles_dev": _dev(_QSS_SIM_VEHICLES),
     "rl_qss_sim_vehicles_host": _host(_QSS_SIM_VEHICLES),

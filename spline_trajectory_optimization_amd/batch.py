@@ -261,6 +261,60 @@ def lap_times_host(track, ctrl, bounds_form, bounds, length, vehicle=None, bank=
     return {k_: v.cpu().numpy() for k_, v in out.items()}
 
 
+SPEED_COLUMN = 4   # Trajectory.SPEED
+
+
+def vehicle_lines_torch(track, widths, length, vehicles, rounds=2, margin=0.0, n_outer=6, bank=None):
+    """One racing line per vehicle: the speed-weighted global min-curvature QP iterated with the QSS simulator, all enqueued
+    on torch's current stream with no host round trip.  Round 0 is the unweighted global QP (ops.global_batch_torch); each of
+    the `rounds` further rounds simulates every vehicle on its current line (lap_times_torch(..., vehicles=vehicles)), takes
+    w = 1 / SPEED of its table with a torch op on the device, and solves the QP again under those weights
+    (ops.global_batch_torch(weights=w)): the line spends the track's width where THAT vehicle is slow.  Every QP starts from
+    the track's own line.  widths [1,N,2] (one track for every vehicle) or [B,N,2], float64 cuda; vehicles: B Vehicles /
+    5-tuples or the stacked 5-tuple of vehicle_tables_batch (numpy or cuda); B is the number of vehicles; bank as for
+    ops.tables_torch.  A failed simulation whose speed is zero gives an infinite weight: the kernel refuses that instance (it
+    comes back as the track's line) and reports it in stats[r, b, 6].
+    Returns dict(ctrl [B,n,2], summary [rounds+1,B,8] (ops.SUMMARY_COLUMNS of every round's lines), stats [rounds+1,B,8] (the
+    QP's), weights [B,N] (those of the last round; ones for rounds=0), points [B,N,19] (the simulated tables of ctrl))."""
+    import torch
+    if getattr(widths, "ndim", None) != 3 or tuple(widths.shape[1:]) != (track.N, 2):
+        raise ValueError(f"widths: expected [1,{track.N},2] or [B,{track.N},2]")
+    if int(rounds) < 0:
+        raise ValueError("rounds: must be >= 0")
+    stacked = isinstance(vehicles, (tuple, list)) and len(vehicles) == 5 and all(hasattr(a, "ndim") for a in vehicles)
+    B = int(vehicles[4].shape[0]) if stacked else len(vehicles)
+    if int(widths.shape[0]) not in (1, B):
+        raise ValueError(f"widths: {int(widths.shape[0])} instances for {B} vehicles")
+    ops._check_torch(widths, "widths", tuple(widths.shape))
+    veh = _vehicles_stacked(vehicles, B, widths.device)
+    widths = widths.expand(B, track.N, 2).contiguous()
+    weights = torch.ones((B, track.N), dtype=torch.float64, device=widths.device)
+    summary, stats = [], []
+    for r in range(int(rounds) + 1):
+        sol = ops.global_batch_torch(track, widths, margin, n_outer, weights=None if r == 0 else weights)
+        lap = lap_times_torch(track, sol["ctrl"], _lib.BOUNDS_WIDTHS, widths, length, bank=bank, vehicles=veh)
+        summary.append(lap["summary"]); stats.append(sol["stats"])
+        if r < int(rounds):
+            weights = (1.0 / lap["points"][:, :, SPEED_COLUMN]).contiguous()
+    return {"ctrl": sol["ctrl"], "summary": torch.stack(summary), "stats": torch.stack(stats), "weights": weights,
+            "points": lap["points"]}
+
+
+def vehicle_lines_host(track, widths, length, vehicles, rounds=2, margin=0.0, n_outer=6, bank=None):
+    """vehicle_lines_torch for numpy input (float64, C-contiguous): copies in, runs the same chain on the track's device,
+    copies out.  Returns the same dict of numpy arrays."""
+    import torch
+    if not isinstance(widths, np.ndarray) or widths.ndim != 3:
+        raise ValueError(f"widths: expected a numpy array [1,{track.N},2] or [B,{track.N},2]")
+    ops._check_np(widths, "widths", (widths.shape[0], track.N, 2))
+    if bank is not None:
+        ops._check_np(bank, "bank", tuple(bank.shape))
+    dev = torch.device("cuda", track.ctx.device)
+    out = vehicle_lines_torch(track, torch.from_numpy(widths).to(dev), length, vehicles, rounds, margin, n_outer,
+                              bank=None if bank is None else torch.from_numpy(bank).to(dev))
+    return {k_: v.cpu().numpy() for k_, v in out.items()}
+
+
 def min_time_tables_torch(race_track, track, X, T, bounds_form, bounds, base=None, pieces=None):
     """Tables of a batch the min-time solve returned (ops.mintime_solve_torch): X [B,N,6] in race_track's curvilinear frame, T
     [B,N] -> points [B,N,19] with X, Y, YAW, SPEED, the bounds, the distances and TIME filled (ops.pose_tables_torch, form

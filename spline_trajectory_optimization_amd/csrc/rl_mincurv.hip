@@ -965,7 +965,9 @@ int global_tables(const rl_ctx* ctx, const rl_track* trk) {
   return RL_OK;
 }
 
-int global_common(rl_ctx* ctx, const rl_track* trk, const double* widths, int B, double margin, int n_outer,
+// weights: null = the unweighted kernels (the bits they always returned); else [B][N] on the device, the weighted kernels of
+// the same dispatch (they validate the weights themselves)
+int global_common(rl_ctx* ctx, const rl_track* trk, const double* widths, const double* weights, int B, double margin, int n_outer,
                   double* out_ctrl, double* out_xy, double* out_a, double* out_stats, rl_stats* stats) {
   if (!ctx || !trk || !widths || !out_ctrl || !out_stats) return fail(RL_ERR_ARG, "null argument");
   if (B <= 0) return fail(RL_ERR_ARG, "B <= 0");
@@ -993,6 +995,11 @@ int global_common(rl_ctx* ctx, const rl_track* trk, const double* widths, int B,
         return by_degree(trk->k, [&](auto kc) {
           constexpr int K = RL_DEGREE(kc);
           const dim3 grid(B), blk(block2);
+          if (weights) {
+            if (R == 5) return groups == 1 ? launch(ctx, rl::k_global_qp2_weighted<K, 5, 1, true>, grid, blk, lds2, a, weights) : launch(ctx, rl::k_global_qp2_weighted<K, 5, 3, true>, grid, blk, lds2, a, weights);
+            if (R == 6) return groups == 1 ? launch(ctx, rl::k_global_qp2_weighted<K, 6, 1, true>, grid, blk, lds2, a, weights) : launch(ctx, rl::k_global_qp2_weighted<K, 6, 3, true>, grid, blk, lds2, a, weights);
+            return launch(ctx, rl::k_global_qp2_weighted<K, 10, 1, false>, grid, blk, lds2, a, weights);
+          }
           if (R == 5) return groups == 1 ? launch(ctx, rl::k_global_qp2<K, 5, 1, true>, grid, blk, lds2, a) : launch(ctx, rl::k_global_qp2<K, 5, 3, true>, grid, blk, lds2, a);
           if (R == 6) return groups == 1 ? launch(ctx, rl::k_global_qp2<K, 6, 1, true>, grid, blk, lds2, a) : launch(ctx, rl::k_global_qp2<K, 6, 3, true>, grid, blk, lds2, a);
           return launch(ctx, rl::k_global_qp2<K, 10, 1, false>, grid, blk, lds2, a);
@@ -1006,6 +1013,11 @@ int global_common(rl_ctx* ctx, const rl_track* trk, const double* widths, int B,
   if (stats) { stats->lds_bytes = (int)lds; stats->block_threads = block; stats->rings_in_lds = 0; }
   return by_degree(trk->k, [&](auto kc) {
     constexpr int K = RL_DEGREE(kc);
+    if (weights) {
+      if (block <= 384) return launch(ctx, rl::k_global_qp_weighted<K, 384>, dim3(B), dim3(block), lds, a, weights);
+      if (block <= 640) return launch(ctx, rl::k_global_qp_weighted<K, 640>, dim3(B), dim3(block), lds, a, weights);
+      return launch(ctx, rl::k_global_qp_weighted<K, 1024>, dim3(B), dim3(block), lds, a, weights);
+    }
     if (block <= 384) return launch(ctx, rl::k_global_qp<K, 384>, dim3(B), dim3(block), lds, a);
     if (block <= 640) return launch(ctx, rl::k_global_qp<K, 640>, dim3(B), dim3(block), lds, a);
     return launch(ctx, rl::k_global_qp<K, 1024>, dim3(B), dim3(block), lds, a);
@@ -1124,7 +1136,7 @@ int rl_mincurv_global_xy_batch_host(rl_ctx* ctx, const rl_track* trk, const doub
 int rl_mincurv_global_batch_dev(rl_ctx* ctx, const rl_track* trk, const double* widths, int B,
                                 double margin, int n_outer, double* out_ctrl, double* out_xy,
                                 double* out_a, double* out_stats, rl_stats* stats) {
-  return global_common(ctx, trk, widths, B, margin, n_outer, out_ctrl, out_xy, out_a, out_stats, stats);
+  return global_common(ctx, trk, widths, nullptr, B, margin, n_outer, out_ctrl, out_xy, out_a, out_stats, stats);
 }
 
 int rl_mincurv_global_batch_host(rl_ctx* ctx, const rl_track* trk, const double* widths, int B,
@@ -1132,8 +1144,36 @@ int rl_mincurv_global_batch_host(rl_ctx* ctx, const rl_track* trk, const double*
                                  double* out_a, double* out_stats, rl_stats* stats) {
   return global_batch_host(ctx, trk, widths, B, 1, out_ctrl, out_xy, out_a, out_stats, stats, global_tables,
                            [&](const double* w, double* c, double* xy, double* a, double* st) {
-                             return global_common(ctx, trk, w, B, margin, n_outer, c, xy, a, st, stats);
+                             return global_common(ctx, trk, w, nullptr, B, margin, n_outer, c, xy, a, st, stats);
                            });
+}
+
+int rl_mincurv_global_weighted_batch_dev(rl_ctx* ctx, const rl_track* trk, const double* widths, const double* weights, int B,
+                                         double margin, int n_outer, double* out_ctrl, double* out_xy, double* out_a,
+                                         double* out_stats, rl_stats* stats) {
+  return global_common(ctx, trk, widths, weights, B, margin, n_outer, out_ctrl, out_xy, out_a, out_stats, stats);
+}
+
+int rl_mincurv_global_weighted_batch_host(rl_ctx* ctx, const rl_track* trk, const double* widths, const double* weights, int B,
+                                          double margin, int n_outer, double* out_ctrl, double* out_xy, double* out_a,
+                                          double* out_stats, rl_stats* stats) {
+  if (!weights) return rl_mincurv_global_batch_host(ctx, trk, widths, B, margin, n_outer, out_ctrl, out_xy, out_a, out_stats, stats);
+  if (!ctx || !trk || !widths || !out_ctrl || !out_stats) return fail(RL_ERR_ARG, "null argument");
+  if (B <= 0) return fail(RL_ERR_ARG, "B <= 0");
+  for (int b = 0; b < B; ++b)   // before anything is staged or enqueued
+    if (!weights_ok(weights + (size_t)b * trk->N, trk->N)) {
+      char msg[96];
+      snprintf(msg, sizeof msg, "weights of instance %d must be finite and within [2^-30, 2^30]", b);
+      return fail(RL_ERR_ARG, msg);
+    }
+  const int n = trk->n, N = trk->N;
+  Staging sg(ctx);   // global_batch_host's staging with one more input
+  const double *dw = sg.in(widths, (size_t)B * N * 2), *dwt = sg.in(weights, (size_t)B * N);
+  double *dctrl = sg.out(out_ctrl, (size_t)B * n * 2), *dxy = sg.out(out_xy, (size_t)B * N * 2);
+  double *da = sg.out(out_a, (size_t)B * (n - trk->k)), *dst = sg.out(out_stats, (size_t)B * 8);
+  sg.run([&] { return global_tables(ctx, trk); });
+  sg.run_timed([&] { return global_common(ctx, trk, dw, dwt, B, margin, n_outer, dctrl, dxy, da, dst, stats); });
+  return sg.finish(stats);
 }
 
 int rl_mincurv_sweep(rl_ctx* ctx, rl_track* trk, const int* i_start, int max_iter,

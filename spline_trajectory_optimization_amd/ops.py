@@ -479,40 +479,73 @@ _GLOBAL_ENTRIES = {1: ("rl_mincurv_global_batch_host", "rl_mincurv_global_batch_
                    2: ("rl_mincurv_global_xy_batch_host", "rl_mincurv_global_xy_batch_dev", "z")}
 
 
-def _global_batch(A, track, widths, margin, n_outer, want_xy, out, dof, lon):
+_GLOBAL_WEIGHTED_ENTRIES = ("rl_mincurv_global_weighted_batch_host", "rl_mincurv_global_weighted_batch_dev")
+
+
+def _global_weights(A, weights, B, N, like):
+    """The weights of the weighted global QP in A's memory space: [N] (every instance) or [B,N] -> contiguous [B,N];
+    ValueError before any device call.  Host weights are range-checked here (as _check_weights does for the cost entry); device
+    weights are checked by the kernel, which reports a refused instance in stats[:, 6]."""
+    if A is _Host:
+        weights = np.asarray(weights, dtype=np.float64)
+    elif not (hasattr(weights, "is_cuda") and weights.is_cuda and weights.dtype == like.dtype):
+        raise ValueError("weights: expected a float64 cuda tensor")
+    if tuple(weights.shape) not in ((N,), (B, N)):
+        raise ValueError(f"weights: expected shape [{N}] or [{B},{N}], got {list(weights.shape)}")
+    if A is _Host:
+        if not np.all((weights >= _lib.WEIGHT_MIN) & (weights <= _lib.WEIGHT_MAX)):   # NaN fails both
+            raise ValueError("weights: every weight must be finite and within [2**-30, 2**30]")
+        return np.ascontiguousarray(np.broadcast_to(weights, (B, N)))
+    A.same_device(like, "widths", [("weights", weights)])
+    return weights.expand(B, N).contiguous()
+
+
+def _global_batch(A, track, widths, margin, n_outer, want_xy, out, dof, lon, weights=None):
     """The global QP in A's memory space -> dict(ctrl, xy, a | z, stats, rl_stats); dof picks the entry, the third output
-    (a [B,n-k] / z [B,n-k,2]) and the extra `lon` argument."""
+    (a [B,n-k] / z [B,n-k,2]) and the extra `lon` argument.  weights (dof 1 only): None, or the [N] / [B,N] per-sample weights
+    of the speed-weighted cost (rl_mincurv_global_weighted_batch_*)."""
     B = widths.shape[0]
     assert tuple(widths.shape) == (B, track.N, 2), widths.shape
     assert dof in _GLOBAL_ENTRIES, dof
     host, dev, third = _GLOBAL_ENTRIES[dof]
+    wargs = ()
+    if weights is not None:
+        if dof != 1:
+            raise ValueError("weights: the weighted cost exists for dof=1 only (the two-coordinate QP has no weighted form)")
+        host, dev = _GLOBAL_WEIGHTED_ENTRIES
+        weights = _global_weights(A, weights, B, track.N, widths)
+        wargs = (A.ptr(weights),)
     if out is None:
         new = lambda *shape: A.new(widths, shape, zero=True)  # noqa: E731
         out = {"ctrl": new(B, track.n, 2), "xy": new(B, track.N, 2) if want_xy else None,
                third: new(B, track.n - track.k, *((2,) if dof == 2 else ())), "stats": new(B, 8)}
     ctx = A.bind(track.ctx, widths)
     st = Stats()
-    check(A.entry(ctx, host, dev)(ctx.h, track.h, A.ptr(widths), int(B), float(margin), *((float(lon),) if dof == 2 else ()),
+    check(A.entry(ctx, host, dev)(ctx.h, track.h, A.ptr(widths), *wargs, int(B), float(margin), *((float(lon),) if dof == 2 else ()),
                                   int(n_outer), A.ptr(out["ctrl"]), A.ptr(out["xy"]), A.ptr(out[third]), A.ptr(out["stats"]),
                                   ctypes.byref(st)))
     out["rl_stats"] = st
     return out
 
 
-def global_batch_host(track, widths, margin=0.0, n_outer=6, want_xy=True, dof=1, lon=1.0):
+def global_batch_host(track, widths, margin=0.0, n_outer=6, want_xy=True, dof=1, lon=1.0, weights=None):
     """Global min-curvature QP (include/rl_mincurv.h: rl_mincurv_global_batch_host) for B width
     instances [B,N,2] = (w_left, w_right).  Returns (ctrl [B,n,2], xy [B,N,2] | None, a [B,n-k],
     stats [B,8], rl_stats).  dof=2: both coordinates of every control point free, lateral and +-`lon` m longitudinal rows
-    (rl_mincurv_global_xy_batch_host; the third result is then z [B,n-k,2])."""
-    o = _global_batch(_Host, track, _f64(widths), margin, n_outer, want_xy, None, dof, lon)
+    (rl_mincurv_global_xy_batch_host; the third result is then z [B,n-k,2]).  weights (dof=1): [N] (every instance) or [B,N]
+    per-sample weights of the cost sum w kappa^2, e.g. 1 / SPEED of each instance's simulated table, finite and within
+    [2**-30, 2**30] (rl_mincurv_global_weighted_batch_host); stats[:, 1:3] are then the weighted sums."""
+    o = _global_batch(_Host, track, _f64(widths), margin, n_outer, want_xy, None, dof, lon, weights)
     return o["ctrl"], o["xy"], o[_GLOBAL_ENTRIES[dof][2]], o["stats"], o["rl_stats"]
 
 
-def global_batch_torch(track, widths, margin=0.0, n_outer=6, out=None, dof=1, lon=1.0):
+def global_batch_torch(track, widths, margin=0.0, n_outer=6, out=None, dof=1, lon=1.0, weights=None):
     """Same on DEVICE tensors: widths float64 cuda [B,N,2]; enqueues on torch's current stream, no
-    sync.  Returns dict(ctrl, xy, a, stats) of cuda tensors (dof=2: `z` [B,n-k,2] instead of `a`)."""
+    sync.  Returns dict(ctrl, xy, a, stats) of cuda tensors (dof=2: `z` [B,n-k,2] instead of `a`).  weights (dof=1): a float64
+    cuda tensor [N] or [B,N]; the kernel checks it (rl_mincurv_global_weighted_batch_dev): an instance with a weight that is
+    not finite or outside [2**-30, 2**30] comes back as the input line with the number of such weights in stats[b, 6]."""
     _assert_cuda_f64(widths)
-    return _global_batch(_Torch, track, widths, margin, n_outer, True, out, dof, lon)
+    return _global_batch(_Torch, track, widths, margin, n_outer, True, out, dof, lon, weights)
 
 
 def _qss_sim(A, points, acc_x, acc_c, dcc_x, dcc_c, params, device):

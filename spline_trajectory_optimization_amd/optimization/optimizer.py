@@ -237,19 +237,21 @@ class TrajectoryOptimizer:
         return traj_out_s
 
     def run_global_min_curvature_qp(self, traj_in_s: BSplineTrajectory, traj_in_d: Trajectory, margin=0.0,
-                                    n_outer=6):
+                                    n_outer=6, *, weights=None):
         """NEW, additive: global min-curvature QP.  The control points of
         `traj_in_s` slide along the normals of that line; every sample of the result stays within the
         half-widths |p - L|, |p - R| that `traj_in_d`'s bound columns give it, minus `margin` metres.
         Returns the optimised BSplineTrajectory; `last_global_stats` = [interior-point iterations,
         sum kappa^2 before, after, largest bound violation [m], last Gauss-Newton step [m],
-        samples on a bound (active set), 0, 0]."""
+        samples on a bound (active set), refused weights, 0].  weights: None, or one weight per sample of `traj_in_d` for
+        the cost sum w kappa^2, e.g. `speed_weights(traj_d)` of a simulated table (1 / SPEED: the line spends the track's
+        width where THIS vehicle is slow); the two sums of the stats are then the weighted ones."""
         from .. import batch
         traj_out_s = traj_in_s.copy()
         trk = self._device_track(traj_out_s, len(traj_in_d))
         wl, wr = batch.half_widths_from_bounds(traj_in_d.points)
         ctrl, xy, a, st, stats = ops.global_batch_host(trk, np.stack([wl, wr], axis=1)[None], margin, n_outer,
-                                                       want_xy=False)
+                                                       want_xy=False, weights=weights)
         traj_out_s._spl_x.c[:] = ctrl[0, :, 0]
         traj_out_s._spl_y.c[:] = ctrl[0, :, 1]
         self.last_global_stats = st[0]

@@ -119,7 +119,8 @@ int rl_ctx_get_arith(const rl_ctx* ctx);
  * end of outer iteration 0 (optimizer.py:333).  The fast arithmetic does not model numpy's error state: on such input a
  * step whose QP solves always refreshes the table. */
 int rl_ctx_set_numpy_raise(rl_ctx* ctx, int on);
-/* Test hooks (no effect on results: every variant returns the same bits).  name / value:
+/* Test hooks (no effect on results: every variant returns the same bits, "qss_df_redo" and "global_last_as_mid" excepted).
+ * name / value:
  *   "qss_kernel"      -1 = rl_qss_sim[_dev] picks by the rounds the batch takes on the chip (default), 0 = the list-order kernel
  *                     k_qss_sim, 1 = the dataflow kernel k_qss_dfw for every size its tables hold
  *   "qss_df_waves"    1 | 2 | 4 waves per instance of the dataflow kernel (default 4)
@@ -130,7 +131,7 @@ int rl_ctx_set_numpy_raise(rl_ctx* ctx, int on);
  *                     `points` keep the bits they came in with.  reason: 2 an agent beyond iteration N - 1, 3 more unnumbered
  *                     fronts than the scratch holds, 4 no free exit record, 5 front ids beyond the table, 7 "qss_df_bail_at"
  *                     (capacities and the hook); 6 an empty queue with live agents, 8 the window-counter guard, 9 more than
- *                     3 N + 64 passes per iteration (the scheduler is broken: no input may produce these).  This option alone changes what a
+ *                     3 N + 64 passes per iteration (the scheduler is broken: no input may produce these).  This option changes what a
  *                     call returns, and only for handed-back instances; it exists so that tests can see them.
  *   "tables_search"   RL_SEARCH_BRUTE | _CULLED | _WINDOWED (default): ring search of rl_tables_batch_* and rl_pose_tables_batch_*
  *   "tables_rings"    0 = rl_tables_batch_* and rl_pose_tables_batch_* keep an instance's ring vertices in LDS where they fit
@@ -140,6 +141,14 @@ int rl_ctx_set_numpy_raise(rl_ctx* ctx, int on);
  *   "sweep_bracket"   1 = the sweep's window scan (rings in global memory) brackets the crossing around the edge it was found on
  *                     last time, where the window's direction cone proves the side values monotone (default), 0 = it always
  *                     forms the side of all 25 vertices
+ *   "global_last_as_mid"  0 (default) | 1: with 1 the LAST linearisation of rl_mincurv_global_batch_*, rl_mincurv_global_weighted_batch_*
+ *                     and rl_mincurv_global_xy_batch_* leaves its interior-point loop at the tolerance of the linearisations before
+ *                     it (complementarity 1e-7, 1e-9 with both coordinates free) instead of the final 1e-10.  The second option
+ *                     that changes what a call returns: a call with n_outer = m - 1 and the hook on returns, bit for bit, the
+ *                     a_{m-1} / z_{m-1} (and the stats so far) about which a call with n_outer = m forms its last QP -- which a
+ *                     plain (m-1)-call does not (it converges its last QP further; the two points differ by up to 1e-2 m).  Tests
+ *                     certify a_m on that QP (tests/global_kkt_cases.py).  With 0 every kernel returns the bits it returns
+ *                     without the option.
  * Defaults come from RL_QSS_DF / RL_QSS_V1 / RL_QSS_DF_WAVES / RL_QSS_DF_BAIL_AT, read ONCE in rl_ctx_create. */
 int rl_ctx_set_option(rl_ctx* ctx, const char* name, int value);
 /* test aid: out[n,5] = yaw, cos / sin(yaw + pi/2), cos / sin(yaw - pi/2) of the tangents (dx, dy), as the
@@ -367,7 +376,13 @@ int rl_spline_fit_batch_host(rl_ctx* ctx, const rl_track* trk, const double* xy,
  *              violation of the result [m], last outer step max|delta a| [m], number of samples
  *              of the result within 1e-6 m of a bound (the active set), 2 reserved
  * CPU twin for tests: oracle/mincurv_oracle.c: orc_global_mincurv.  *_dev takes device pointers and
- * enqueues on the context's stream; *_host copies in/out, synchronises and fills stats->kernel_ms. */
+ * enqueues on the context's stream; *_host copies in/out, synchronises and fills stats->kernel_ms.
+ * An EMPTY corridor (w_left_i + w_right_i - 2 margin < 0 at some sample of some instance) has no feasible line.  The three
+ * *_host entries (this one, the weighted and the two-coordinate one) check the widths before anything is staged or enqueued:
+ * RL_ERR_ARG, the message names the first such instance and sample.  *_dev cannot read device memory on the host: such an
+ * instance runs every linearisation to the cap of 80 iterations and returns a finite line OUTSIDE its bounds; out_stats[3],
+ * the largest violation [m] (at least half the largest emptiness), is then the report, the other instances of the batch are
+ * not touched and the call returns RL_OK. */
 int rl_mincurv_global_batch_dev(rl_ctx* ctx, const rl_track* trk, const double* widths, int B,
                                 double margin, int n_outer, double* out_ctrl, double* out_xy,
                                 double* out_a, double* out_stats, rl_stats* stats);

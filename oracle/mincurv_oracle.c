@@ -1340,10 +1340,18 @@ static void spd_solve_dense(int n, const double* Lm, double* b) {
 
 /* Exit rule of the interior-point iterations of both global QPs -- the twin of csrc/rl_device.hpp: ipm_done, same constants (the
  * measurements behind them are in its comment): the complementarity mu alone, below tol_mid for every linearisation before the
- * last (1e-7 with one offset per control point, 1e-9 with both coordinates free), below 1e-10 for the last.  No residual clause:
- * going on past the complementarity drives the residual UP with the conditioning and breaks down within a few iterations. */
+ * last (1e-7 with one offset per control point, 1e-9 with both coordinates free), below kIpmTolLast = 1e-10 for the last.  No
+ * residual clause: going on past the complementarity (here: 1e-14 with one offset, 1e-13 with both coordinates free) drives the residual
+ * UP with the conditioning and breaks down within a few iterations. */
 static const double kIpmTolOneOffset = 1e-7, kIpmTolTwoCoords = 1e-9;
-static int ipm_done(double tol_mid, int last_qp, double mu) { return mu < (last_qp ? 1e-10 : tol_mid); }
+static const double kIpmTolLast = 1e-10;
+static int ipm_done(double tol_mid, int last_qp, double mu) { return mu < (last_qp ? kIpmTolLast : tol_mid); }
+
+/* Twin of the test hook rl_ctx_set_option(ctx, "global_last_as_mid", 1) (include/rl_mincurv.h): the last linearisation of both
+ * global QPs leaves at the intermediate tolerance, so that a call with n_outer = m - 1 returns the point the m-run linearised
+ * about.  Thread-local, default 0. */
+static _Thread_local int g_global_last_as_mid = 0;
+void orc_set_global_last_as_mid(int on) { g_global_last_as_mid = on ? 1 : 0; }
 
 int orc_global_mincurv(const double* t, int nt, const double* cx0, const double* cy0, int k, int N,
                        const double* w_left, const double* w_right, double margin, int n_outer,
@@ -1488,7 +1496,7 @@ int orc_global_mincurv(const double* t, int nt, const double* cx0, const double*
       double rdmax = 0.0;
       for (int j = 0; j < np_; ++j) rdmax = fmax(rdmax, fabs(rd[j]));
       (void)rdmax; (void)rpmax; (void)qinf;
-      if (ipm_done(kIpmTolOneOffset, outer + 1 >= n_outer, mu)) break;
+      if (ipm_done(kIpmTolOneOffset, outer + 1 >= n_outer && !g_global_last_as_mid, mu)) break;
       ++total_it;
       /* normal matrix */
       memcpy(Kq, P, (size_t)np_ * np_ * sizeof(double));
@@ -1725,7 +1733,7 @@ int orc_global_mincurv_xy(const double* t, int nt, const double* cx0, const doub
       double rdmax = 0.0;
       for (int j = 0; j < nz; ++j) rdmax = fmax(rdmax, fabs(rd[j]));
       (void)rdmax; (void)rpmax; (void)qinf;
-      if (ipm_done(kIpmTolTwoCoords, outer + 1 >= n_outer, mu)) break;
+      if (ipm_done(kIpmTolTwoCoords, outer + 1 >= n_outer && !g_global_last_as_mid, mu)) break;
       ++total_it;
       memcpy(Kq, P, (size_t)nz * nz * sizeof(double));
       for (int r = 0; r < R; ++r) {

@@ -174,6 +174,10 @@ void orc_replay_steps(const double* t, int nt, int k, int N, const double* ringL
                       const double* ringR, int nR, int n_steps, const int* idx,
                       const double* cxs, const double* cys, double* out, int nthreads);
 
+/* test hook of the two global QPs, twin of rl_ctx_set_option(ctx, "global_last_as_mid", on): 1 = the last linearisation leaves at
+ * the intermediate tolerance (thread-local, default 0) */
+void orc_set_global_last_as_mid(int on);
+
 /* numpy's error state at the start of the two drivers (see mincurv_oracle.c, "numpy's error state"; fixture G12):
  * 1 = np.seterr(all='raise') is already in effect (the simulator has run before, as in the reference's own test);
  * thread-local; orc_last_raised() = steps / windows of the last driver call whose re-sampling raised */

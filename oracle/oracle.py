@@ -287,6 +287,23 @@ def run_joint_min_curvature_qp(t, cx, cy, k, length, N, ringL, ringR, i_start, m
     return cx, cy, pts, ns
 
 
+class global_last_as_mid:
+    """with orc.global_last_as_mid(): ...  -- the twin of the library's test hook "global_last_as_mid" (include/rl_mincurv.h): the
+    last linearisation of global_mincurv / global_mincurv_xy leaves at the intermediate tolerance, so a call with n_outer = m - 1
+    returns the point that the m-run linearised about."""
+
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        lib().orc_set_global_last_as_mid(1 if self.on else 0)
+        return self
+
+    def __exit__(self, *exc):
+        lib().orc_set_global_last_as_mid(0)
+        return False
+
+
 def global_mincurv(t, cx0, cy0, k, N, w_left, w_right, margin=0.0, n_outer=6):
     """The build's own global min-curvature QP (lateral control-point offsets, interior point);
     returns (cx, cy, xy [N,2], a [n-k], stats[6]: ipm iterations, sum kappa^2 before/after,

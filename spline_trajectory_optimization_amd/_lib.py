@@ -229,7 +229,8 @@ class Context:
 
     def set_option(self, name, value):
         """Test hooks (include/rl_mincurv.h: rl_ctx_set_option): "qss_kernel", "qss_df_waves", "qss_df_bail_at", "qss_df_redo",
-        "tables_search", "tables_rings", "frenet_search", "sweep_bracket"."""
+        "tables_search", "tables_rings", "frenet_search", "sweep_bracket", "global_last_as_mid" (1: the last linearisation of the
+        global QPs leaves at the intermediate tolerance -- it changes what the call returns; tests/global_kkt_cases.py)."""
         check(self.lib.rl_ctx_set_option(self.h, name.encode(), int(value)))
 
     def set_numpy_raise(self, on):

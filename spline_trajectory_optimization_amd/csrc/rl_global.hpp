@@ -49,6 +49,7 @@ struct GlobalArgs {
   const double* widths;  // [B][N][2] (w_left, w_right)
   double margin;
   int n_outer, max_ipm;
+  int last_as_mid;       // test hook "global_last_as_mid": the last linearisation leaves at the intermediate tolerance
   double* out_ctrl;      // [B][n][2]
   double* out_xy;        // [B][N][2] or null
   double* out_a;         // [B][np] or null

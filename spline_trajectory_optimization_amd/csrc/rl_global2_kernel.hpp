@@ -561,7 +561,7 @@ __global__ void __launch_bounds__(kG2Block) k_global_qp2(GlobalArgs a) {
           const double mu = mu_sum / (double)(2 * N);
           // the exit rule (rl_device.hpp: ipm_done): the complementarity alone, 1e-7 before the last linearisation, 1e-10 on it
           (void)rdmax; (void)rpmax; (void)qinf;
-          conv = ipm_done(kIpmTolOneOffset, outer + 1 >= RL_G2_N_OUTER, mu);
+          conv = ipm_done(kIpmTolOneOffset, outer + 1 >= RL_G2_N_OUTER && !a.last_as_mid, mu);
           if (lane == 0) ctl[0] = conv ? 1.0 : 0.0;
         }
         double bx[G];

@@ -277,7 +277,7 @@ __global__ void __launch_bounds__(MAXB) k_global_qp(GlobalArgs a) {
       double d0 = 0.0, d1 = 0.0;
       reduce3(d0, rdmax, d1);
       (void)rdmax; (void)rpmax; (void)qinf;   // the residuals no longer decide anything (rl_device.hpp: ipm_done)
-      if (ipm_done(kIpmTolOneOffset, outer + 1 >= RL_GQ_N_OUTER, mu)) break;
+      if (ipm_done(kIpmTolOneOffset, outer + 1 >= RL_GQ_N_OUTER && !a.last_as_mid, mu)) break;
       ++total_it;
       // ---- factor, affine direction
       if (wave == 0) {

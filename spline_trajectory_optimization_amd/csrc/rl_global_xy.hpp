@@ -53,6 +53,7 @@ struct GlobalXYArgs {
   const double* widths;    // [B][N][2] (w_left, w_right)
   double margin, lon;
   int n_outer, max_ipm;
+  int last_as_mid;         // test hook "global_last_as_mid": the last linearisation leaves at the intermediate tolerance
   double* out_ctrl;        // [B][n][2]
   double* out_xy;          // [B][N][2] or null
   double* out_z;           // [B][np][2] or null
@@ -683,7 +684,7 @@ __global__ void __launch_bounds__(NT) k_global_xy(GlobalXYArgs a) {
         // the exit rule (rl_device.hpp: ipm_done): the complementarity alone, 1e-9 before the last linearisation, 1e-10 on it (going
         // on past it only drives mu down -- 1e-156 was seen -- and the residual UP with the normal matrix's conditioning)
         (void)rdmax; (void)rpmax; (void)qinf;
-        const bool done = ipm_done(kIpmTolTwoCoords, outer + 1 >= a.n_outer, mu);
+        const bool done = ipm_done(kIpmTolTwoCoords, outer + 1 >= a.n_outer && !a.last_as_mid, mu);
         if (done) break;
       }
       ++total_it;

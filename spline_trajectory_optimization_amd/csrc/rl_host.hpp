@@ -70,6 +70,7 @@ struct rl_ctx {
   // the dataflow kernel, the iteration at which it hands every instance back (0 = never), whether the list-order kernel re-runs
   // what it handed back (1; 0 = no: such an instance returns iters = RL_QSS_HANDED_BACK - reason and keeps its input rows)
   int qss_kernel = -1, qss_df_waves = 4, qss_df_bail_at = 0, qss_df_redo = 1;
+  int global_last_as_mid = 0;  // test hook: the global QPs' last linearisation leaves at the intermediate tolerance
   int sweep_bracket = 1;   // the sweep's window scan may bracket the crossing around its hint (test hook "sweep_bracket" = 0: always the full sign pass)
   // test hooks of rl_tables_batch_*: ring search (RL_SEARCH_*), 1 = ring vertices in the arena even where they fit LDS
   int tables_search = RL_SEARCH_WINDOWED, tables_rings_global = 0;

@@ -398,6 +398,7 @@ int rl_ctx_set_option(rl_ctx* ctx, const char* name, int value) {
   else if (k == "qss_df_waves") { if (value != 1 && value != 2 && value != 4) return fail(RL_ERR_ARG, "qss_df_waves: 1, 2 or 4"); ctx->qss_df_waves = value; }
   else if (k == "qss_df_bail_at") { if (value < 0) return fail(RL_ERR_ARG, "qss_df_bail_at >= 0"); ctx->qss_df_bail_at = value; }
   else if (k == "qss_df_redo") { if (value != 0 && value != 1) return fail(RL_ERR_ARG, "qss_df_redo: 0 or 1"); ctx->qss_df_redo = value; }
+  else if (k == "global_last_as_mid") { if (value != 0 && value != 1) return fail(RL_ERR_ARG, "global_last_as_mid: 0 or 1"); ctx->global_last_as_mid = value; }
   else if (k == "sweep_bracket") { if (value != 0 && value != 1) return fail(RL_ERR_ARG, "sweep_bracket: 0 or 1"); ctx->sweep_bracket = value; }
   else if (k == "tables_search") { if (value < RL_SEARCH_BRUTE || value > RL_SEARCH_WINDOWED) return fail(RL_ERR_ARG, "tables_search: RL_SEARCH_BRUTE, _CULLED or _WINDOWED"); ctx->tables_search = value; }
   else if (k == "tables_rings") { if (value != 0 && value != 1) return fail(RL_ERR_ARG, "tables_rings: 0 (LDS where they fit) or 1 (arena)"); ctx->tables_rings_global = value; }
@@ -979,7 +980,7 @@ int global_common(rl_ctx* ctx, const rl_track* trk, const double* widths, const 
   a.trk = trk->dev();
   a.A = trk->gq_A.p; a.nu = trk->gq_nu.p; a.chunk = trk->gq_chunk.p; a.span_ch0 = trk->gq_span.p;
   a.nc = trk->gq_nc; a.np = trk->n - trk->k;
-  a.widths = widths; a.margin = margin; a.n_outer = n_outer; a.max_ipm = 80;
+  a.widths = widths; a.margin = margin; a.n_outer = n_outer; a.max_ipm = 80; a.last_as_mid = ctx->global_last_as_mid;
   a.out_ctrl = out_ctrl; a.out_xy = out_xy; a.out_a = out_a; a.out_stats = out_stats;
   // fast path: wave-specialised kernel (rl_global2.hpp) when the chunks fit 7 row waves and the LDS
   if (!ctx->force_global_v1 && trk->gq2_rows != 0 && a.np <= 192) {
@@ -1084,7 +1085,7 @@ int global_xy_common(rl_ctx* ctx, const rl_track* trk, const double* widths, int
   a.trk = trk->dev();
   a.span_first = trk->gxy_span.p; a.chunk_first = trk->gxy_chunk.p; a.span_chunk0 = trk->gxy_sch0.p; a.nch = trk->gxy_nch;
   a.bbx = trk->gxy_bbx.p; a.np = trk->n - trk->k;
-  a.widths = widths; a.margin = margin; a.lon = lon; a.n_outer = n_outer; a.max_ipm = 80;
+  a.widths = widths; a.margin = margin; a.lon = lon; a.n_outer = n_outer; a.max_ipm = 80; a.last_as_mid = ctx->global_last_as_mid;
   a.out_ctrl = out_ctrl; a.out_xy = out_xy; a.out_z = out_z; a.out_stats = out_stats;
   const int block = trk->N <= 512 * rl::kXYRows ? 512 : 1024;
   if (trk->N > block * rl::kXYRows) return fail(RL_ERR_UNSUPPORTED, "global QP (dof 2): more than 4096 samples");
@@ -1097,15 +1098,33 @@ int global_xy_common(rl_ctx* ctx, const rl_track* trk, const double* widths, int
   });
 }
 
+// An empty corridor (w_left + w_right - 2 margin < 0 at a sample) has no feasible line: the kernels run every linearisation to
+// its iteration cap and return a line outside, with stats[3] as the only report.  The `_host` entries can read the widths and
+// refuse such a batch before anything is staged (the `_dev` entries cannot: there stats[3] is the report).
+int corridor_check(const double* widths, int B, int N, double margin) {
+  for (int b = 0; b < B; ++b)
+    for (int i = 0; i < N; ++i) {
+      const double* w = widths + ((size_t)b * N + i) * 2;
+      if (w[0] + w[1] - 2.0 * margin < 0.0) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "empty corridor: instance %d, sample %d has w_left + w_right - 2 margin = %g < 0", b, i,
+                 w[0] + w[1] - 2.0 * margin);
+        return fail(RL_ERR_ARG, msg);
+      }
+    }
+  return RL_OK;
+}
+
 // The two global QPs with host buffers: the same staging around their table builder and their `_common` call.  `opt_width`:
 // doubles per free control point of the optional third output (a [B, n-k]: 1, z [B, n-k, 2]: 2).  The table build stays in
 // front of the timed region.
 template <typename Tables, typename Common>
-int global_batch_host(rl_ctx* ctx, const rl_track* trk, const double* widths, int B, int opt_width, double* out_ctrl,
+int global_batch_host(rl_ctx* ctx, const rl_track* trk, const double* widths, int B, double margin, int opt_width, double* out_ctrl,
                              double* out_xy, double* out_opt, double* out_stats, rl_stats* stats, Tables tables, Common common) {
   if (!ctx || !trk || !widths || !out_ctrl || !out_stats) return fail(RL_ERR_ARG, "null argument");
   if (B <= 0) return fail(RL_ERR_ARG, "B <= 0");
   const int n = trk->n, N = trk->N;
+  if (int rc = corridor_check(widths, B, N, margin)) return rc;   // before anything is staged or enqueued
   Staging sg(ctx);
   const double* dw = sg.in(widths, (size_t)B * N * 2);
   double *dctrl = sg.out(out_ctrl, (size_t)B * n * 2), *dxy = sg.out(out_xy, (size_t)B * N * 2);
@@ -1127,7 +1146,7 @@ int rl_mincurv_global_xy_batch_dev(rl_ctx* ctx, const rl_track* trk, const doubl
 int rl_mincurv_global_xy_batch_host(rl_ctx* ctx, const rl_track* trk, const double* widths, int B, double margin, double lon,
                                     int n_outer, double* out_ctrl, double* out_xy, double* out_z, double* out_stats,
                                     rl_stats* stats) {
-  return global_batch_host(ctx, trk, widths, B, 2, out_ctrl, out_xy, out_z, out_stats, stats, global_xy_tables,
+  return global_batch_host(ctx, trk, widths, B, margin, 2, out_ctrl, out_xy, out_z, out_stats, stats, global_xy_tables,
                            [&](const double* w, double* c, double* xy, double* z, double* st) {
                              return global_xy_common(ctx, trk, w, B, margin, lon, n_outer, c, xy, z, st, stats);
                            });
@@ -1142,7 +1161,7 @@ int rl_mincurv_global_batch_dev(rl_ctx* ctx, const rl_track* trk, const double* 
 int rl_mincurv_global_batch_host(rl_ctx* ctx, const rl_track* trk, const double* widths, int B,
                                  double margin, int n_outer, double* out_ctrl, double* out_xy,
                                  double* out_a, double* out_stats, rl_stats* stats) {
-  return global_batch_host(ctx, trk, widths, B, 1, out_ctrl, out_xy, out_a, out_stats, stats, global_tables,
+  return global_batch_host(ctx, trk, widths, B, margin, 1, out_ctrl, out_xy, out_a, out_stats, stats, global_tables,
                            [&](const double* w, double* c, double* xy, double* a, double* st) {
                              return global_common(ctx, trk, w, nullptr, B, margin, n_outer, c, xy, a, st, stats);
                            });
@@ -1167,6 +1186,7 @@ int rl_mincurv_global_weighted_batch_host(rl_ctx* ctx, const rl_track* trk, cons
       return fail(RL_ERR_ARG, msg);
     }
   const int n = trk->n, N = trk->N;
+  if (int rc = corridor_check(widths, B, N, margin)) return rc;
   Staging sg(ctx);   // global_batch_host's staging with one more input
   const double *dw = sg.in(widths, (size_t)B * N * 2), *dwt = sg.in(weights, (size_t)B * N);
   double *dctrl = sg.out(out_ctrl, (size_t)B * n * 2), *dxy = sg.out(out_xy, (size_t)B * N * 2);

@@ -139,6 +139,34 @@ def certify_qp(P, q, A, lo, hi, a):
     return cert, (QP_STAT_REL * qinf, QP_COMPL_REL * max(1.0, float(cert.z.max())), QP_VIOL)
 
 
+def polish_qp(P, q, A, lo, hi, a, near=1e-6, max_iter=400):
+    """The exact optimum a* of  min 1/2 a'Pa + q'a, lo <= A a <= hi  by a primal-dual active-set iteration started from the rows
+    that `a` leaves within `near` of a bound: solve the equality-constrained KKT system on the working rows, add the worst
+    violated row, else drop the row with the most negative multiplier, until neither exists.  Plain numpy; the working rows may
+    be dependent (more samples than control points touch a bound), so the KKT system is solved in the least-squares sense.
+    -> (a*, number of working rows, passes).  The caller certifies a* (certify_qp): nothing here is taken on trust."""
+    a = np.asarray(a, dtype=np.float64).reshape(-1)
+    n, Aa = len(a), A @ a
+    rows = np.vstack([A, -A]); rhs = np.r_[hi, -lo]                     # rows x <= rhs
+    work = list(np.where(np.r_[Aa >= hi - near, Aa <= lo + near])[0])
+    x = a
+    for it in range(max_iter):
+        C = rows[work]
+        K = np.block([[P, C.T], [C, np.zeros((len(work), len(work)))]])
+        sol = np.linalg.lstsq(K, np.r_[-q, rhs[work]], rcond=1e-14)[0]
+        x, lam = sol[:n], sol[n:]
+        excess = rows @ x - rhs
+        excess[work] = -np.inf
+        worst = int(excess.argmax())
+        if excess[worst] > 1e-12:
+            work.append(worst)
+        elif len(work) and lam.min() < -1e-10 * max(1.0, np.abs(lam).max()):
+            work.pop(int(lam.argmin()))
+        else:
+            return x, len(work), it + 1
+    raise RuntimeError(f"polish_qp: no optimal working set within {max_iter} passes")
+
+
 # --------------------------------------------------------------------------------------------------------- the NLPs
 def node_colours(N):
     """Colour classes of the ring of N nodes in which no two neighbours share a colour."""

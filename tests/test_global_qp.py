@@ -255,3 +255,32 @@ def test_global_torch_entry_and_errors(rl, fits):
         rl.ops.global_batch_host(trk, W[:, :100], MARGIN, 3)
     with pytest.raises(rl.lib.RlError):
         rl.ops.global_batch_host(trk, W, MARGIN, -1)
+
+
+@pytest.mark.gpu
+def test_global_empty_corridor(rl, fits):
+    """A sample with w_left + w_right - 2 margin < 0 leaves no feasible line.  The three host entries refuse the batch before
+    anything is staged and name the first instance and sample; the device entry cannot see the widths: the instance returns a
+    finite line outside its bounds, stats[3] reports it, and the other rows of the batch carry the bits they have without it."""
+    import torch
+    N, margin = 500, MARGIN
+    t, cx, cy, k, u, wl, wr = monza_widths(fits, "c100", N)
+    trk = rl.lib.Track(rl.lib.Context.get(0), t, cx, cy, k, N)
+    W = rl.batch.width_batch(wl, wr, 3, seed=3)
+    W[1, 100:110] = 0.1                                   # margin > half-width at ten samples: the corridor is 0.3 m short
+    emptiness = float((2 * margin - W[1].sum(1)).max())
+    assert emptiness == pytest.approx(0.3) and ((W.sum(2) - 2 * margin) < 0).sum() == 10
+    for kw in (dict(), dict(weights=np.ones(N)), dict(dof=2)):
+        with pytest.raises(rl.lib.RlError, match="instance 1, sample 100"):
+            rl.ops.global_batch_host(trk, W, margin, 3, **kw)
+    dev = torch.device("cuda", 0)
+    out = rl.ops.global_batch_torch(trk, torch.from_numpy(W).to(dev), margin, 3)           # returns: RL_OK
+    ref = rl.ops.global_batch_torch(trk, torch.from_numpy(np.ascontiguousarray(W[[0, 2]])).to(dev), margin, 3)
+    torch.cuda.synchronize()
+    st = out["stats"].cpu().numpy()
+    print(f"[empty corridor] emptiness {emptiness:.3f} m, stats[1] {st[1]}")
+    for key in ("ctrl", "xy", "a", "stats"):
+        o, r = out[key].cpu().numpy(), ref[key].cpu().numpy()
+        assert np.isfinite(o).all()
+        assert o[0].tobytes() == r[0].tobytes() and o[2].tobytes() == r[1].tobytes(), key
+    assert st[1, 3] >= 0.5 * emptiness and st[0, 3] <= 1e-9 and st[2, 3] <= 1e-9

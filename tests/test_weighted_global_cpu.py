@@ -18,6 +18,7 @@ import types
 import numpy as np
 import pytest
 
+import global_kkt_cases as gk
 import kkt_certificate as kc
 import weighted_global_twin as tw
 from conftest import ROOT
@@ -71,17 +72,9 @@ def test_weighted_twin_solves_the_independent_weighted_qp(monza):
     1e-9 I), q = 2 G'W kappa, with G by finite differences of scipy's BSpline curvature (NumpyGlobal, restated for W)."""
     m = monza
     ng = NumpyGlobal(m.t, m.cx, m.cy, m.k, m.u)
-    a0, h = np.zeros(ng.np), 1e-3
-    G = np.zeros((N, ng.np)); A = np.zeros((N, ng.np))
-    for j in range(ng.np):
-        e = np.zeros(ng.np); e[j] = 1.0
-        G[:, j] = (ng.kappa(a0 + h * e) - ng.kappa(a0 - h * e)) / (2 * h)
-        A[:, j] = ng.lateral(e)
-    kap = ng.kappa(a0)
-    P = 2 * G.T @ (m.w[:, None] * G)
-    q = 2 * G.T @ (m.w * (kap - G @ a0))
-    sc = ng.np / np.trace(P)
-    P, q = P * sc + 1e-9 * np.eye(ng.np), q * sc
+    a0 = np.zeros(ng.np)
+    G, A, kap = gk.gauss_newton_rows(ng, a0)                 # the restatement, shared with the certificates of the kernels
+    P, q = gk.scaled_qp(G, kap, a0, m.w)
     _, _, _, a, st = m.weighted[1]
     cert, bounds = kc.certify_qp(P, q, A, -(m.wr - MARGIN), m.wl - MARGIN, a)
     print(f"[weighted twin kkt] stat {cert.stat:.2e} (bound {bounds[0]:.2e})  compl {cert.compl:.2e} (bound {bounds[1]:.2e})  "
@@ -90,10 +83,8 @@ def test_weighted_twin_solves_the_independent_weighted_qp(monza):
     assert st[1] == pytest.approx((m.w * kap ** 2).sum(), rel=1e-10)
     assert st[2] == pytest.approx((m.w * ng.kappa(a) ** 2).sum(), rel=1e-10)
     # and the same point is NOT a solution of the unweighted QP: the certificate tells the two problems apart
-    P1 = 2 * G.T @ G
-    q1 = 2 * G.T @ (kap - G @ a0)
-    sc1 = ng.np / np.trace(P1)
-    cert1, bounds1 = kc.certify_qp(P1 * sc1 + 1e-9 * np.eye(ng.np), q1 * sc1, A, -(m.wr - MARGIN), m.wl - MARGIN, a)
+    P1, q1 = gk.scaled_qp(G, kap, a0)
+    cert1, bounds1 = kc.certify_qp(P1, q1, A, -(m.wr - MARGIN), m.wl - MARGIN, a)
     assert cert1.stat > bounds1[0] or cert1.compl > bounds1[1]
 
 

@@ -20,10 +20,11 @@ from scipy.linalg import cho_factor, cho_solve
 from oracle import oracle as orc
 
 IPM_TOL_ONE_OFFSET = 1e-7   # oracle/mincurv_oracle.c: kIpmTolOneOffset
+IPM_TOL_LAST = 1e-10        # oracle/mincurv_oracle.c: kIpmTolLast
 
 
 def ipm_done(tol_mid, last_qp, mu):
-    return mu < (1e-10 if last_qp else tol_mid)
+    return mu < (IPM_TOL_LAST if last_qp else tol_mid)
 
 
 class Tables:
@@ -113,9 +114,11 @@ def weighted_qp(tab, av, weights):
     return P * sc + 1e-9 * np.eye(tab.np), q * sc, kp
 
 
-def global_mincurv_weighted(t, cx0, cy0, k, N, w_left, w_right, margin=0.0, n_outer=6, weights=None, tables=None):
+def global_mincurv_weighted(t, cx0, cy0, k, N, w_left, w_right, margin=0.0, n_outer=6, weights=None, tables=None,
+                            last_as_mid=False):
     """orc_global_mincurv with the cost sum_i weights[i] kappa_i^2 (None = ones).  Returns (cx [n], cy [n], xy [N,2], a [n-k],
-    stats [8]) as oracle.global_mincurv does; stats[1], [2] are the weighted sums."""
+    stats [8]) as oracle.global_mincurv does; stats[1], [2] are the weighted sums.  last_as_mid: the twin of the library's test
+    hook "global_last_as_mid" -- the last linearisation leaves at the intermediate tolerance."""
     tab = tables or Tables(t, cx0, cy0, k, N)
     w = np.ones(N) if weights is None else np.asarray(weights, dtype=np.float64)
     assert w.shape == (N,)
@@ -146,7 +149,7 @@ def global_mincurv_weighted(t, cx0, cy0, k, N, w_left, w_right, margin=0.0, n_ou
             rpl, rpu = ax - lo - sl, hi - ax - su
             rd = P @ xv + qv + A.T @ (lu - ll)
             mu = float(np.sum(sl * ll + su * lu)) / float(2 * N)
-            if ipm_done(IPM_TOL_ONE_OFFSET, outer + 1 >= n_outer, mu):
+            if ipm_done(IPM_TOL_ONE_OFFSET, outer + 1 >= n_outer and not last_as_mid, mu):
                 break
             total_it += 1
             dm = ll / sl + lu / su

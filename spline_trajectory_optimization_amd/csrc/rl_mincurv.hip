@@ -85,6 +85,10 @@ int by_degree(int k, F&& f) {
 }
 #define RL_DEGREE(kc) (std::decay_t<decltype(kc)>::value)
 
+// the same for a run-time flag that selects a template argument: f(std::bool_constant<V>)
+template <typename F>
+int by_flag(bool v, F&& f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
+
 // Samples [s0, s1) under control points j .. j + span - 1, with the reference's own mask (u >= t[j]) & (u < t[j+span+k]),
 // u_i = i * (1/N).  The two loops ARE the mask: the indices are part of the bit-exact contract.
 struct SupportRange { int s0, s1; };
@@ -982,6 +986,11 @@ int global_common(rl_ctx* ctx, const rl_track* trk, const double* widths, const 
   a.nc = trk->gq_nc; a.np = trk->n - trk->k;
   a.widths = widths; a.margin = margin; a.n_outer = n_outer; a.max_ipm = 80; a.last_as_mid = ctx->global_last_as_mid;
   a.out_ctrl = out_ctrl; a.out_xy = out_xy; a.out_a = out_a; a.out_stats = out_stats;
+  a.weights = weights;
+  // the two compile-time choices of every launch below: f(spline degree K, weighted cost W)
+  auto by_kernel = [&](auto&& f) {
+    return by_degree(trk->k, [&](auto kc) { return by_flag(weights != nullptr, [&](auto wc) { return f(kc, wc); }); });
+  };
   // fast path: wave-specialised kernel (rl_global2.hpp) when the chunks fit 7 row waves and the LDS
   if (!ctx->force_global_v1 && trk->gq2_rows != 0 && a.np <= 192) {
     const int groups = a.np <= 64 ? 1 : 3;
@@ -993,17 +1002,13 @@ int global_common(rl_ctx* ctx, const rl_track* trk, const double* widths, const 
       if (R != 10 || groups == 1) {
         a.chunk = trk->gq2_chunk.p; a.span_ch0 = trk->gq2_span.p; a.nc = trk->gq2_nc;
         if (stats) { stats->lds_bytes = (int)lds2; stats->block_threads = block2; stats->rings_in_lds = 0; }
-        return by_degree(trk->k, [&](auto kc) {
+        return by_kernel([&](auto kc, auto wc) {
           constexpr int K = RL_DEGREE(kc);
+          constexpr bool W = RL_DEGREE(wc);
           const dim3 grid(B), blk(block2);
-          if (weights) {
-            if (R == 5) return groups == 1 ? launch(ctx, rl::k_global_qp2_weighted<K, 5, 1, true>, grid, blk, lds2, a, weights) : launch(ctx, rl::k_global_qp2_weighted<K, 5, 3, true>, grid, blk, lds2, a, weights);
-            if (R == 6) return groups == 1 ? launch(ctx, rl::k_global_qp2_weighted<K, 6, 1, true>, grid, blk, lds2, a, weights) : launch(ctx, rl::k_global_qp2_weighted<K, 6, 3, true>, grid, blk, lds2, a, weights);
-            return launch(ctx, rl::k_global_qp2_weighted<K, 10, 1, false>, grid, blk, lds2, a, weights);
-          }
-          if (R == 5) return groups == 1 ? launch(ctx, rl::k_global_qp2<K, 5, 1, true>, grid, blk, lds2, a) : launch(ctx, rl::k_global_qp2<K, 5, 3, true>, grid, blk, lds2, a);
-          if (R == 6) return groups == 1 ? launch(ctx, rl::k_global_qp2<K, 6, 1, true>, grid, blk, lds2, a) : launch(ctx, rl::k_global_qp2<K, 6, 3, true>, grid, blk, lds2, a);
-          return launch(ctx, rl::k_global_qp2<K, 10, 1, false>, grid, blk, lds2, a);
+          if (R == 5) return groups == 1 ? launch(ctx, rl::k_global_qp2<K, 5, 1, true, W>, grid, blk, lds2, a) : launch(ctx, rl::k_global_qp2<K, 5, 3, true, W>, grid, blk, lds2, a);
+          if (R == 6) return groups == 1 ? launch(ctx, rl::k_global_qp2<K, 6, 1, true, W>, grid, blk, lds2, a) : launch(ctx, rl::k_global_qp2<K, 6, 3, true, W>, grid, blk, lds2, a);
+          return launch(ctx, rl::k_global_qp2<K, 10, 1, false, W>, grid, blk, lds2, a);
         });
       }
     }
@@ -1012,16 +1017,12 @@ int global_common(rl_ctx* ctx, const rl_track* trk, const double* widths, const 
   const size_t lds = (size_t)rl::global_layout(trk->k, trk->n, a.np, block).total * sizeof(double);
   if (lds > (size_t)ctx->max_lds) return fail(RL_ERR_UNSUPPORTED, "global QP does not fit LDS");
   if (stats) { stats->lds_bytes = (int)lds; stats->block_threads = block; stats->rings_in_lds = 0; }
-  return by_degree(trk->k, [&](auto kc) {
+  return by_kernel([&](auto kc, auto wc) {
     constexpr int K = RL_DEGREE(kc);
-    if (weights) {
-      if (block <= 384) return launch(ctx, rl::k_global_qp_weighted<K, 384>, dim3(B), dim3(block), lds, a, weights);
-      if (block <= 640) return launch(ctx, rl::k_global_qp_weighted<K, 640>, dim3(B), dim3(block), lds, a, weights);
-      return launch(ctx, rl::k_global_qp_weighted<K, 1024>, dim3(B), dim3(block), lds, a, weights);
-    }
-    if (block <= 384) return launch(ctx, rl::k_global_qp<K, 384>, dim3(B), dim3(block), lds, a);
-    if (block <= 640) return launch(ctx, rl::k_global_qp<K, 640>, dim3(B), dim3(block), lds, a);
-    return launch(ctx, rl::k_global_qp<K, 1024>, dim3(B), dim3(block), lds, a);
+    constexpr bool W = RL_DEGREE(wc);
+    if (block <= 384) return launch(ctx, rl::k_global_qp<K, 384, W>, dim3(B), dim3(block), lds, a);
+    if (block <= 640) return launch(ctx, rl::k_global_qp<K, 640, W>, dim3(B), dim3(block), lds, a);
+    return launch(ctx, rl::k_global_qp<K, 1024, W>, dim3(B), dim3(block), lds, a);
   });
 }
 
@@ -1116,21 +1117,28 @@ int corridor_check(const double* widths, int B, int N, double margin) {
 }
 
 // The two global QPs with host buffers: the same staging around their table builder and their `_common` call.  `opt_width`:
-// doubles per free control point of the optional third output (a [B, n-k]: 1, z [B, n-k, 2]: 2).  The table build stays in
-// front of the timed region.
+// doubles per free control point of the optional third output (a [B, n-k]: 1, z [B, n-k, 2]: 2).  `weights`: the optional
+// second input [B, N] (null: none), refused here like an empty corridor.  The table build stays in front of the timed region.
 template <typename Tables, typename Common>
-int global_batch_host(rl_ctx* ctx, const rl_track* trk, const double* widths, int B, double margin, int opt_width, double* out_ctrl,
-                             double* out_xy, double* out_opt, double* out_stats, rl_stats* stats, Tables tables, Common common) {
+int global_batch_host(rl_ctx* ctx, const rl_track* trk, const double* widths, const double* weights, int B, double margin,
+                      int opt_width, double* out_ctrl, double* out_xy, double* out_opt, double* out_stats, rl_stats* stats,
+                      Tables tables, Common common) {
   if (!ctx || !trk || !widths || !out_ctrl || !out_stats) return fail(RL_ERR_ARG, "null argument");
   if (B <= 0) return fail(RL_ERR_ARG, "B <= 0");
   const int n = trk->n, N = trk->N;
-  if (int rc = corridor_check(widths, B, N, margin)) return rc;   // before anything is staged or enqueued
+  for (int b = 0; weights && b < B; ++b)   // before anything is staged or enqueued
+    if (!weights_ok(weights + (size_t)b * N, N)) {
+      char msg[96];
+      snprintf(msg, sizeof msg, "weights of instance %d must be finite and within [2^-30, 2^30]", b);
+      return fail(RL_ERR_ARG, msg);
+    }
+  if (int rc = corridor_check(widths, B, N, margin)) return rc;   // the same
   Staging sg(ctx);
-  const double* dw = sg.in(widths, (size_t)B * N * 2);
+  const double *dw = sg.in(widths, (size_t)B * N * 2), *dwt = sg.in(weights, (size_t)B * N);
   double *dctrl = sg.out(out_ctrl, (size_t)B * n * 2), *dxy = sg.out(out_xy, (size_t)B * N * 2);
   double *dopt = sg.out(out_opt, (size_t)B * (n - trk->k) * opt_width), *dst = sg.out(out_stats, (size_t)B * 8);
   sg.run([&] { return tables(ctx, trk); });
-  sg.run_timed([&] { return common(dw, dctrl, dxy, dopt, dst); });
+  sg.run_timed([&] { return common(dw, dwt, dctrl, dxy, dopt, dst); });
   return sg.finish(stats);
 }
 
@@ -1146,8 +1154,8 @@ int rl_mincurv_global_xy_batch_dev(rl_ctx* ctx, const rl_track* trk, const doubl
 int rl_mincurv_global_xy_batch_host(rl_ctx* ctx, const rl_track* trk, const double* widths, int B, double margin, double lon,
                                     int n_outer, double* out_ctrl, double* out_xy, double* out_z, double* out_stats,
                                     rl_stats* stats) {
-  return global_batch_host(ctx, trk, widths, B, margin, 2, out_ctrl, out_xy, out_z, out_stats, stats, global_xy_tables,
-                           [&](const double* w, double* c, double* xy, double* z, double* st) {
+  return global_batch_host(ctx, trk, widths, nullptr, B, margin, 2, out_ctrl, out_xy, out_z, out_stats, stats, global_xy_tables,
+                           [&](const double* w, const double*, double* c, double* xy, double* z, double* st) {
                              return global_xy_common(ctx, trk, w, B, margin, lon, n_outer, c, xy, z, st, stats);
                            });
 }
@@ -1161,8 +1169,8 @@ int rl_mincurv_global_batch_dev(rl_ctx* ctx, const rl_track* trk, const double* 
 int rl_mincurv_global_batch_host(rl_ctx* ctx, const rl_track* trk, const double* widths, int B,
                                  double margin, int n_outer, double* out_ctrl, double* out_xy,
                                  double* out_a, double* out_stats, rl_stats* stats) {
-  return global_batch_host(ctx, trk, widths, B, margin, 1, out_ctrl, out_xy, out_a, out_stats, stats, global_tables,
-                           [&](const double* w, double* c, double* xy, double* a, double* st) {
+  return global_batch_host(ctx, trk, widths, nullptr, B, margin, 1, out_ctrl, out_xy, out_a, out_stats, stats, global_tables,
+                           [&](const double* w, const double*, double* c, double* xy, double* a, double* st) {
                              return global_common(ctx, trk, w, nullptr, B, margin, n_outer, c, xy, a, st, stats);
                            });
 }
@@ -1177,23 +1185,10 @@ int rl_mincurv_global_weighted_batch_host(rl_ctx* ctx, const rl_track* trk, cons
                                           double margin, int n_outer, double* out_ctrl, double* out_xy, double* out_a,
                                           double* out_stats, rl_stats* stats) {
   if (!weights) return rl_mincurv_global_batch_host(ctx, trk, widths, B, margin, n_outer, out_ctrl, out_xy, out_a, out_stats, stats);
-  if (!ctx || !trk || !widths || !out_ctrl || !out_stats) return fail(RL_ERR_ARG, "null argument");
-  if (B <= 0) return fail(RL_ERR_ARG, "B <= 0");
-  for (int b = 0; b < B; ++b)   // before anything is staged or enqueued
-    if (!weights_ok(weights + (size_t)b * trk->N, trk->N)) {
-      char msg[96];
-      snprintf(msg, sizeof msg, "weights of instance %d must be finite and within [2^-30, 2^30]", b);
-      return fail(RL_ERR_ARG, msg);
-    }
-  const int n = trk->n, N = trk->N;
-  if (int rc = corridor_check(widths, B, N, margin)) return rc;
-  Staging sg(ctx);   // global_batch_host's staging with one more input
-  const double *dw = sg.in(widths, (size_t)B * N * 2), *dwt = sg.in(weights, (size_t)B * N);
-  double *dctrl = sg.out(out_ctrl, (size_t)B * n * 2), *dxy = sg.out(out_xy, (size_t)B * N * 2);
-  double *da = sg.out(out_a, (size_t)B * (n - trk->k)), *dst = sg.out(out_stats, (size_t)B * 8);
-  sg.run([&] { return global_tables(ctx, trk); });
-  sg.run_timed([&] { return global_common(ctx, trk, dw, dwt, B, margin, n_outer, dctrl, dxy, da, dst, stats); });
-  return sg.finish(stats);
+  return global_batch_host(ctx, trk, widths, weights, B, margin, 1, out_ctrl, out_xy, out_a, out_stats, stats, global_tables,
+                           [&](const double* w, const double* wt, double* c, double* xy, double* a, double* st) {
+                             return global_common(ctx, trk, w, wt, B, margin, n_outer, c, xy, a, st, stats);
+                           });
 }
 
 int rl_mincurv_sweep(rl_ctx* ctx, rl_track* trk, const int* i_start, int max_iter,

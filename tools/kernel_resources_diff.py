@@ -40,6 +40,13 @@ def renamed(before, after):
         if name in before or not m:
             continue
         fn, targs, params = m.group(1), [a.strip() for a in m.group(2).split(",")], m.group(3)
+        if targs[-1] in ("true", "false"):
+            # a pair `k<A>(P)` / `k_weighted<A>(P, w)` that became one template over a trailing flag: `k<A, false>` / `k<A, true>`
+            head = f"void {fn}{'_weighted' if targs[-1] == 'true' else ''}<{', '.join(targs[:-1])}>("
+            old = [b for b in before if b.startswith(head) and b not in after]
+            if len(old) == 1:
+                out[old[0]] = name
+            continue
         first = params.split(",")[0].strip()
         if targs[-1] != first:
             continue

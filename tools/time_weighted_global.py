@@ -4,7 +4,8 @@ table, N = 2000, B = 1024 width-perturbed instances, 6 linearisations.  ONE run 
 warm-up and three timed calls per leg:
   1. the unweighted entry on this build and -- with --compare-lib PARENT.so -- on another build of the library (the parent
      commit's), in child processes that alternate, --rounds each: whether this build's median lies within the spread the other
-     build's own timings show in the same session;
+     build's own timings show in the same session; the children time the weighted entry too (w = 1 / linspace(20, 80, N)),
+     judged the same way;
   2. the weighted entry with w = 1;
   3. the weighted entry with w = 1 / SPEED of every instance's simulated table;
   4. batch.vehicle_lines_torch(rounds=2) for the 32 x 32 grip x power grid of tools/time_vehicle_sweep.py on the nominal widths:
@@ -61,8 +62,8 @@ def main():
     ap.add_argument("--B", type=int, default=1024)
     ap.add_argument("--compare-lib", default=None)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--lib", default=None, help="child mode: the unweighted leg on this library, JSON on stdout")
-    ap.add_argument("--unweighted-only", action="store_true")
+    ap.add_argument("--lib", default=None, help="child mode: the library to time")
+    ap.add_argument("--child", action="store_true", help="the unweighted and the weighted entry only, JSON on stdout")
     a = ap.parse_args()
     _lib, ops = load_package(a.lib)
     import torch
@@ -72,8 +73,10 @@ def main():
     W = torch.from_numpy(batch.width_batch(w_nom[:, 0], w_nom[:, 1], a.B, seed=1234)).to(dev)
     out = ops.global_batch_torch(trk, W, MARGIN, N_OUTER)
     unweighted = timed_ms(lambda: ops.global_batch_torch(trk, W, MARGIN, N_OUTER, out=out))
-    if a.unweighted_only:
-        print("UNWEIGHTED " + json.dumps(unweighted))
+    if a.child:   # and the weighted entry, with synthetic weights that need no simulated table
+        syn = torch.from_numpy(np.ascontiguousarray(np.tile(1.0 / np.linspace(20.0, 80.0, a.N), (a.B, 1)))).to(dev)
+        weighted = timed_ms(lambda: ops.global_batch_torch(trk, W, MARGIN, N_OUTER, out=out, weights=syn))
+        print("CHILD " + json.dumps({"unweighted": unweighted, "weighted": weighted}))
         return
     res = {"B": a.B, "N": a.N, "n_outer": N_OUTER, "margin_m": MARGIN, "device": torch.cuda.get_device_name(0),
            "timing": "device events, one warm-up and three timed calls per leg",
@@ -137,20 +140,22 @@ def main():
         rounds = {"this": [], "other": []}
         for _ in range(a.rounds):
             for who, lib in (("other", a.compare_lib), ("this", _lib.LIB_PATH)):
-                o = subprocess.run([sys.executable, os.path.abspath(__file__), "--lib", lib, "--unweighted-only", "--N", str(a.N),
+                o = subprocess.run([sys.executable, os.path.abspath(__file__), "--lib", lib, "--child", "--N", str(a.N),
                                     "--B", str(a.B)], capture_output=True, text=True, timeout=600)
                 if o.returncode != 0:
                     raise RuntimeError(f"child on {lib} failed ({o.returncode}): {o.stderr[-800:]}")
-                line = [ln for ln in o.stdout.splitlines() if ln.startswith("UNWEIGHTED ")][-1]
-                rounds[who].append(json.loads(line[len("UNWEIGHTED "):]))
-        mine = [r["median"] for r in rounds["this"]]
-        theirs = [x for r in rounds["other"] for x in r["calls_ms"]]
-        res["unweighted_this_build_vs_other"] = {
-            "rounds": a.rounds, "order": "other, this, other, this, ...", "this": rounds["this"], "other": rounds["other"],
-            "this_median_of_rounds_ms": float(np.median(mine)),
-            "other_median_of_rounds_ms": float(np.median([r["median"] for r in rounds["other"]])),
-            "other_min_ms": float(min(theirs)), "other_max_ms": float(max(theirs)),
-            "this_within_other_spread": bool(np.median(mine) <= max(theirs))}
+                line = [ln for ln in o.stdout.splitlines() if ln.startswith("CHILD ")][-1]
+                rounds[who].append(json.loads(line[len("CHILD "):]))
+        for leg in ("unweighted", "weighted"):   # weighted: w = 1 / linspace(20, 80, N) for every instance
+            this, other = [r[leg] for r in rounds["this"]], [r[leg] for r in rounds["other"]]
+            mine = [r["median"] for r in this]
+            theirs = [x for r in other for x in r["calls_ms"]]
+            res[f"{leg}_this_build_vs_other"] = {
+                "rounds": a.rounds, "order": "other, this, other, this, ...", "this": this, "other": other,
+                "this_median_of_rounds_ms": float(np.median(mine)),
+                "other_median_of_rounds_ms": float(np.median([r["median"] for r in other])),
+                "other_min_ms": float(min(theirs)), "other_max_ms": float(max(theirs)),
+                "this_within_other_spread": bool(np.median(mine) <= max(theirs))}
         write()
     print(json.dumps({k_: v for k_, v in res.items() if k_ != "vehicle_lines"} |
                      {"vehicle_lines": {k_: v for k_, v in res["vehicle_lines"].items() if k_ != "lap_time_s"}}))

@@ -57,6 +57,7 @@ _SPLINE_FIT = [_vp, _vp, _D, _i, _i, _i, _D, _i, _D, _D]
 _DT_EVAL = [_vp, _dp, _i, _i, _dp, _dp, _dp, _dp, _d, _d, _dp, _dp, _dp, _dp, _dp, _dp]
 _MINTIME_SOLVE = [_vp, _dp, _i, _i, _D, _D, _D, _D, _i, _d, _d, _d, _d, _D, _D, _D, _i, _d, _D]   # and _vehicles
 _BICYCLE_SOLVE = [_vp, _dp, _i, _i, _D, _D, _D, _D, _i, _D, _D, _D, _i, _d, _D]
+_BICYCLE_LINES = [_vp, _dp, _i, _i, _i, _D, _D, _i, _D, _D, _i, _D, _D, _D, _i, _d, _D]
 _QSS_SIM = [_vp, _D, _i, _i, _dp, _dp, _i, _dp, _dp, _i, _dp, _I]
 _QSS_SIM_VEHICLES = [_vp, _D, _i, _i, _D, _D, _i, _D, _D, _i, _D, _I]
 _GLOBAL = [_vp, _vp, _D, _i, _d, _i, _D, _D, _D, _D, _st]
@@ -116,6 +117,9 @@ _SIGNATURES = {
     "rl_bicycle_eval_nodes": (_i, [_vp, _dp, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "rl_bicycle_solve_batch": _host(_BICYCLE_SOLVE),
     "rl_bicycle_solve_batch_dev": _dev(_BICYCLE_SOLVE),
+    "rl_bicycle_solve_lines": _host(_BICYCLE_LINES),
+    "rl_bicycle_solve_lines_dev": _dev(_BICYCLE_LINES),
+    "rl_bicycle_eval_nodes_lines": (_i, [_vp, _dp, _i, _i, _i, _dp, _dp, _i, _dp, _dp, _dp, _dp, _dp, _dp]),
     "rl_qss_sim_dev": _dev(_QSS_SIM),
     "rl_mincurv_global_batch_dev": _dev(_GLOBAL),
     "rl_mincurv_global_batch_host": _host(_GLOBAL),

@@ -407,6 +407,85 @@ def min_time_guess_from_lines_torch(race_track, points, s_nodes, kappa_nodes, ba
     return X, U, T, status
 
 
+def _unwrap_torch(p):
+    """numpy.unwrap along the last axis (period 2 pi) with torch ops."""
+    import torch
+    dd = p[..., 1:] - p[..., :-1]
+    ddmod = torch.remainder(dd + np.pi, 2.0 * np.pi) - np.pi
+    ddmod = torch.where((ddmod == -np.pi) & (dd > 0), torch.full_like(ddmod, np.pi), ddmod)
+    corr = torch.where(dd.abs() < np.pi, torch.zeros_like(dd), ddmod - dd)
+    out = p.clone()
+    out[..., 1:] = p[..., 1:] + corr.cumsum(dim=-1)
+    return out
+
+
+def bicycle_inputs_from_tables_torch(points):
+    """What the bicycle NLP reads of B tables, with torch ops on the tables' device: points [B,N,19] (float64 cuda tensor, e.g.
+    lap_times_torch(...)["points"]) -> dict(P0 [B,N,2], yaw [B,N], dl [B,N] >= 0, dr [B,N] <= 0, X0 [B,N,5], U0 [B,N,2], T0 [B,N],
+    usable [B] bool): the line, its headings, the distances to its bounds and the centre-line guess, with BicycleProblem's
+    expressions (SPEED where it is filled, else 10 m/s).  The distances are norms, as in the reference: a table whose bound
+    point IS the line's point -- what rl_tables_batch_* writes where the normal ray finds no crossing, i.e. where the line lies
+    on or outside that bound (models/trajectory.py:127) -- gives dl == 0 or dr == 0 there.  The solver needs dr < dl at every
+    node, which holds while only one side is 0; usable[b] says that instance b has it, with every value finite.  Lines meant
+    for this chain should keep a margin to the bounds in the solve that made them.  No host round trip."""
+    import torch
+    from .models.trajectory import Trajectory as Tr
+    if getattr(points, "ndim", None) != 3 or points.shape[2] != _lib.NCOL:
+        raise ValueError("points: expected [B,N,19]")
+    ops._check_torch(points, "points", points.shape)
+    B, N = int(points.shape[0]), int(points.shape[1])
+    P0 = points[:, :, Tr.X:Tr.Y + 1].contiguous()
+    yaw = points[:, :, Tr.YAW].contiguous()
+    dl = torch.linalg.norm(points[:, :, Tr.LEFT_BOUND_X:Tr.LEFT_BOUND_Y + 1] - P0, dim=2).contiguous()
+    dr = (-torch.linalg.norm(points[:, :, Tr.RIGHT_BOUND_X:Tr.RIGHT_BOUND_Y + 1] - P0, dim=2)).contiguous()
+    v = points[:, :, Tr.SPEED]
+    v = torch.where(torch.isfinite(v) & (v > 0.0), v, torch.full_like(v, 10.0))
+    X0 = torch.zeros((B, N, 5), dtype=torch.float64, device=points.device)
+    X0[:, :, 0:2] = P0
+    X0[:, :, 2] = _unwrap_torch(yaw)
+    X0[:, :, 4] = v
+    U0 = torch.zeros((B, N, 2), dtype=torch.float64, device=points.device)
+    T0 = (torch.linalg.norm(torch.roll(P0, -1, dims=1) - P0, dim=2) / v).contiguous()
+    finite = torch.isfinite(P0).all(dim=2) & torch.isfinite(yaw) & torch.isfinite(dl) & torch.isfinite(dr) & torch.isfinite(T0)
+    usable = (finite & (dr < dl)).all(dim=1)
+    return {"P0": P0, "yaw": yaw, "dl": dl, "dr": dr, "X0": X0, "U0": U0, "T0": T0, "usable": usable}
+
+
+def bicycle_on_tables_torch(points, models, max_iter=200, tol=1e-6, check=False):
+    """The time-optimal bicycle trajectory along each of B lines, as one chain on torch's current stream: points [B,N,19]
+    (cuda tensor: B lines with their bounds, e.g. lap_times_torch(...)["points"] of a solved min-curvature batch) -> the
+    solver's inputs and the centre-line guess (bicycle_inputs_from_tables_torch) -> ops.bicycle_solve_lines_torch.  models:
+    one model dict or B of them -- the only host data of the call.  Returns dict(X [B,N,5], U [B,N,2], T [B,N], stats
+    [B,12], lap [B] = T.sum(1), P0, yaw, dl, dr, usable [B] bool) of cuda tensors; a table of the result is
+    ops.pose_tables_torch(track, POSE_GLOBAL, X, None, ...).
+    An instance whose table is not usable (bicycle_inputs_from_tables_torch: a node with dr >= dl -- the line on or outside
+    BOTH bounds there -- or a value that is not finite) is not a problem the solver can be given: it runs on a stand-in (a
+    straight line with bounds of +-1 m, so that the device-pointer entry's "caller guarantees dr < dl" holds for the whole
+    batch), and its X, U, T, lap come back NaN with stats[b, 5] = 2 (failed).  check=True reads `usable` on the host first (one
+    synchronisation) and raises a ValueError naming the first such instance instead."""
+    import torch
+    inp = bicycle_inputs_from_tables_torch(points)
+    ok = inp["usable"]
+    if check and not bool(ok.all()):
+        bad = torch.nonzero(~ok).flatten()
+        raise ValueError(f"points: instance {int(bad[0])} (and {len(bad) - 1} more): a node with dr >= dl or a value that is not "
+                         "finite; the lines need a margin to their bounds")
+    B, N = int(points.shape[0]), int(points.shape[1])
+    ramp = torch.arange(N, dtype=torch.float64, device=points.device)
+    sP0 = torch.stack([ramp, torch.zeros_like(ramp)], dim=1)                       # stand-in: 1 m steps along x
+    sel = lambda a, stand_in: torch.where(ok.reshape((B,) + (1,) * (a.dim() - 1)), a, stand_in).contiguous()  # noqa: E731
+    P0, yaw = sel(inp["P0"], sP0[None]), sel(inp["yaw"], torch.zeros_like(ramp)[None])
+    dl, dr = sel(inp["dl"], torch.ones_like(ramp)[None]), sel(inp["dr"], -torch.ones_like(ramp)[None])
+    sX = torch.zeros((N, 5), dtype=torch.float64, device=points.device); sX[:, 0] = ramp; sX[:, 4] = 10.0
+    X, U, T = sel(inp["X0"], sX[None]), inp["U0"], sel(inp["T0"], torch.full_like(ramp, 0.1)[None])
+    stats = ops.bicycle_solve_lines_torch(models, P0, yaw, dl, dr, X, U, T, max_iter=max_iter, tol=tol)
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=points.device)
+    X, U, T = (torch.where(ok.reshape((B,) + (1,) * (a.dim() - 1)), a, nan) for a in (X, U, T))
+    stats[:, 5] = torch.where(ok, stats[:, 5], torch.full_like(stats[:, 5], 2.0))
+    return {"X": X, "U": U, "T": T, "stats": stats, "lap": T.sum(1), "P0": inp["P0"], "yaw": inp["yaw"], "dl": inp["dl"],
+            "dr": inp["dr"], "usable": ok}
+
+
 def signed_curvature(points):
     """Centre-line curvature with sign at the samples of a sampled table (the turn radius of column 5 is
     unsigned): heading change per arc length, central differences over the closed line."""

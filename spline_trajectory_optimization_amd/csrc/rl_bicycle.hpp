@@ -18,6 +18,9 @@
 // 6N negative, else the unknowns' diagonal is regularised (IPOPT's delta_w rule).  Exact Hessian of the pair's
 // Lagrangian (only theta, delta, v, a, delta_dot, T carry curvature) by forward-over-forward duals (rl_dtrack.hpp).
 // Fraction to the boundary, filter line search with backtracking, IPOPT's z safeguard.  CPU twin: tests/bicycle_twin.py.
+//
+// Two forms of the problem data, one text of the kernels: BkProblem (one model, one line for the batch; only dl / dr may
+// differ per instance) and BkProblemV (model, line and bounds of instance b from row b of device tables), see there.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -57,6 +60,31 @@ struct BkProblem {
   double tol;
 };
 
+// One line and one vehicle per instance (rl_bicycle_solve_lines*): the model of instance b is row b of a table
+// [B, BK_NPARAM] in device memory instead of a kernel argument, and with `lines` P0 / yaw are [B,N,2] / [B,N].  Every kernel
+// takes its instance from blockIdx, so a row's address is the same in all lanes; bk_instance moves the pointers to the
+// instance's rows once, at the kernel's head, and everything below reads P.m[], P.P0[], P.yaw[] with the text it reads them
+// with from BkProblem -- node j+1 of the wrap-around pair included, which is then the instance's own P0 at jn.  The table
+// pointer is in the constant address space (the table is written by a copy that is complete before the first kernel of the
+// solve starts, and by nothing else), as the model table of rl_mintime.hpp: a value is a scalar load whatever the kernel
+// stores in between.  The kernels and the device functions that read the problem are templates over the problem type:
+// <BkProblem> is what the shared-model entries launch, <BkProblemV> what the per-instance entries launch.
+typedef const double __attribute__((address_space(4))) * BkTab;
+struct BkProblemV {
+  BkTab m;               // row 0 of the table [B, BK_NPARAM]
+  int N, per, lines;     // per: dl / dr are [B,N] (else [N]); lines: P0 [B,N,2], yaw [B,N] (else [N,2], [N])
+  const double* P0;
+  const double* yaw;
+  const double* dl;
+  const double* dr;
+  double tol;
+};
+__device__ __forceinline__ void bk_instance(BkProblem&, int) {}
+__device__ __forceinline__ void bk_instance(BkProblemV& P, int b) {
+  P.m += (size_t)b * BK_NPARAM;
+  if (P.lines) { P.P0 += (size_t)b * P.N * 2; P.yaw += (size_t)b * P.N; }
+}
+
 struct BkState {         // per-instance device arrays, instance-major; their shapes are kBkArrays below
   int B, N;
   double *p, *yc, *yd, *zl, *zu, *D, *r, *Dinv, *Tk, *v, *Jd, *dcur, *dp, *scal, *filt;
@@ -90,8 +118,8 @@ __device__ __forceinline__ Dual<ND, T> bk_tan(const Dual<ND, T>& x) {
 }
 
 // d/dt (x, y, theta, delta, v) of models/dynamic_bicycle.py:4-23; beta = atan2(lr delta, L) = atan(lr delta / L), L > 0
-template <typename S>
-__device__ __forceinline__ void bk_dyn(const double* m, const S& th, const S& de, const S& v, S (&f)[3]) {
+template <typename M, typename S>
+__device__ __forceinline__ void bk_dyn(M m, const S& th, const S& de, const S& v, S (&f)[3]) {
   const S beta = m_atan(de * (m[BK_LR] / m[BK_L]));
   S sb, cb, st, ct;
   m_sincos(beta, sb, cb);
@@ -102,8 +130,8 @@ __device__ __forceinline__ void bk_dyn(const double* m, const S& th, const S& de
 
 // the curved part of a node: q = scaled (theta, delta, v, a, delta_dot, T) -> RK4 increments of the 5 states and the
 // traction function lat^2 + lon^2 (lat = omega |(vx, vy)|, lon = a)
-template <typename S>
-__device__ __forceinline__ void bk_curved(const double* m, const S (&q)[6], S (&inc)[5], S& trac) {
+template <typename M, typename S>
+__device__ __forceinline__ void bk_curved(M m, const S (&q)[6], S (&inc)[5], S& trac) {
   const S th = q[0] * kBkSx[2], de = q[1] * kBkSx[3], v = q[2] * kBkSx[4];
   const S a = q[3] * kBkSu[0], dd = q[4] * kBkSu[1], dt = q[5];
   S k1[3], k2[3], k3[3], k4[3];
@@ -119,8 +147,9 @@ __device__ __forceinline__ void bk_curved(const double* m, const S (&q)[6], S (&
   trac = k1[2] * k1[2] * (k1[0] * k1[0] + k1[1] * k1[1]) + a * a;
 }
 
-__device__ __forceinline__ void bk_bounds(const BkProblem& P, int b, int j, double (&lo)[kBkNb], double (&hi)[kBkNb]) {
-  const double* m = P.m;
+template <typename PT>
+__device__ __forceinline__ void bk_bounds(const PT& P, int b, int j, double (&lo)[kBkNb], double (&hi)[kBkNb]) {
+  const auto m = P.m;
   const double inf = __builtin_huge_val();
   const size_t o = P.per ? (size_t)b * P.N + j : (size_t)j;
   lo[0] = lo[1] = lo[2] = -inf; hi[0] = hi[1] = hi[2] = inf;
@@ -134,7 +163,8 @@ __device__ __forceinline__ void bk_bounds(const BkProblem& P, int b, int j, doub
 }
 
 // values of node j's functions: c [6] (defect 5, longitudinal coordinate), d [2] (lateral coordinate, traction)
-__device__ __forceinline__ void bk_values(const BkProblem& P, int j, const double* w, const double* wn, double (&c)[kBkNe],
+template <typename PT>
+__device__ __forceinline__ void bk_values(const PT& P, int j, const double* w, const double* wn, double (&c)[kBkNe],
                                           double (&d)[2]) {
   const int jn = j + 1 == P.N ? 0 : j + 1;
   double q[6] = {w[2], w[3], w[4], w[5], w[6], w[7]}, inc[5], trac;
@@ -188,9 +218,11 @@ __device__ __forceinline__ double bk_push(double p, double lo, double hi) {
 }
 
 // physical X [B,N,5], U [B,N,2], T [B,N] -> scaled unknowns, pushed inside their bounds; slacks; multipliers; scalars
-__global__ void __launch_bounds__(kBkThreads) k_bk_init(BkProblem P, BkState st, const double* X, const double* U,
+template <typename PT>
+__global__ void __launch_bounds__(kBkThreads) k_bk_init(PT P, BkState st, const double* X, const double* U,
                                                         const double* T) {
   const int b = blockIdx.x, N = P.N;
+  bk_instance(P, b);
   for (int j = threadIdx.x; j < N; j += kBkThreads) {
     const size_t n = (size_t)b * N + j;
     double lo[kBkNb], hi[kBkNb];
@@ -227,7 +259,8 @@ __global__ void __launch_bounds__(kBkThreads) k_bk_init(BkProblem P, BkState st,
 
 // node j: functions, Jacobians and Hessian of the Lagrangian into D (H in the unknowns' block, Jc and Jc^T), the
 // gradient of the Lagrangian without bound terms into r[0:8], c into r[8:14]; Jd, d.  Returns the error contributions.
-__device__ __forceinline__ void bk_node_derivs(const BkProblem& P, const BkState& st, int b, int j, double& dual, double& prim,
+template <typename PT>
+__device__ __forceinline__ void bk_node_derivs(const PT& P, const BkState& st, int b, int j, double& dual, double& prim,
                                                double& gzmax, double& gzmin, double& comp0, double& lap) {
   const int N = P.N, jn = j + 1 == N ? 0 : j + 1, jp = j == 0 ? N - 1 : j - 1;
   const size_t n = (size_t)b * N + j;
@@ -299,7 +332,8 @@ __device__ __forceinline__ void bk_node_derivs(const BkProblem& P, const BkState
 }
 
 // theta (sum |c| + |d - s|) and phi (sum T - mu sum log gaps) at p + a dp
-__device__ __forceinline__ void bk_trial(const BkProblem& P, const BkState& st, const double* dp, int b, double a, double mu,
+template <typename PT>
+__device__ __forceinline__ void bk_trial(const PT& P, const BkState& st, const double* dp, int b, double a, double mu,
                                          double& th, double& ph) {
   const int N = P.N;
   th = 0.0; ph = 0.0;
@@ -349,8 +383,10 @@ __device__ __forceinline__ void bk_invert(double* M, double* diag0, int t, int& 
 }
 
 // one interior-point iteration per instance; final != 0: only the convergence test and the statistics
-__global__ void __launch_bounds__(kBkThreads) k_bk_iter(BkProblem P, BkState st, int final_pass) {
+template <typename PT>
+__global__ void __launch_bounds__(kBkThreads) k_bk_iter(PT P, BkState st, int final_pass) {
   const int b = blockIdx.x, N = P.N, t = threadIdx.x;
+  bk_instance(P, b);
   double* sc = st.scal + (size_t)b * kBkScal;
   if (sc[BS_DONE] != 0.0) return;
   __shared__ double red[8 * (kBkThreads / 64)];
@@ -638,8 +674,10 @@ __global__ void __launch_bounds__(kBkThreads) k_bk_iter(BkProblem P, BkState st,
   }
 }
 
-__global__ void k_bk_unpack(BkProblem P, BkState st, double* X, double* U, double* T, double* stats) {
+template <typename PT>
+__global__ void k_bk_unpack(PT P, BkState st, double* X, double* U, double* T, double* stats) {
   const int b = blockIdx.y, N = P.N;
+  bk_instance(P, b);
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j < N) {
     const size_t n = (size_t)b * N + j;
@@ -654,10 +692,12 @@ __global__ void k_bk_unpack(BkProblem P, BkState st, double* X, double* U, doubl
 
 // functions at a given physical point, one thread per (instance, node): eq [B,N,6], ineq [B,N,2] (lateral coordinate,
 // lat^2 + lon^2), cost part T
-__global__ void k_bk_eval(BkProblem P, int B, const double* X, const double* U, const double* T, double* eq, double* ineq) {
+template <typename PT>
+__global__ void k_bk_eval(PT P, int B, const double* X, const double* U, const double* T, double* eq, double* ineq) {
   const int b = blockIdx.y, N = P.N;
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= N || b >= B) return;
+  bk_instance(P, b);
   const int jn = j + 1 == N ? 0 : j + 1;
   const size_t n = (size_t)b * N + j, nn = (size_t)b * N + jn;
   double w[kBkNv], wn[kBkNv];

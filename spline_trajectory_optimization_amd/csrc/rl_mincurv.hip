@@ -2033,16 +2033,89 @@ int rl_mintime_solve_vehicles(rl_ctx* ctx, const double* models, int B, int N, c
 }
 
 // ---- the bicycle min-time NLP (rl_bicycle.hpp)
-static int bk_problem(const double* model, int N, rl::BkProblem& P) {
-  for (int i = 0; i < rl::BK_NPARAM; ++i) {
-    if (!std::isfinite(model[i])) return fail(RL_ERR_ARG, "bicycle model: non-finite parameter");
-    P.m[i] = model[i];
-  }
+// what the kernels divide by and what makes the box bounds a box: the one statement of the checks on a model, for the
+// shared-model entries (`who` = "bicycle model") and for every row of a per-instance call ("models: instance b")
+static int bk_check_model(const double* model, const std::string& who) {
+  for (int i = 0; i < rl::BK_NPARAM; ++i)
+    if (!std::isfinite(model[i])) return fail(RL_ERR_ARG, who + ": non-finite parameter");
   if (!(model[RL_BK_L] > 0.0) || !(model[RL_BK_DELTA_MAX] > 0.0) || !(model[RL_BK_V_MAX] > 0.0) ||
       !(model[RL_BK_A_LON_MAX] > model[RL_BK_A_LON_MIN]) || !(model[RL_BK_DELTA_DOT_MAX] > 0.0) || !(model[RL_BK_ACC_MAX] > 0.0))
-    return fail(RL_ERR_ARG, "bicycle model: L, delta_max, v_max, delta_dot_max, acc_max > 0 and a_lon_max > a_lon_min");
+    return fail(RL_ERR_ARG, who + ": L, delta_max, v_max, delta_dot_max, acc_max > 0 and a_lon_max > a_lon_min");
+  return RL_OK;
+}
+
+static int bk_problem(const double* model, int N, rl::BkProblem& P) {
+  if (int rc = bk_check_model(model, "bicycle model")) return rc;
+  for (int i = 0; i < rl::BK_NPARAM; ++i) P.m[i] = model[i];
   P.N = N;
   return RL_OK;
+}
+
+// a per-instance call checks every row before anything is staged or enqueued; RL_ERR_ARG names the first bad instance
+static int bk_check_models(const double* models, int models_per_instance, int B) {
+  for (int b = 0; b < (models_per_instance ? B : 1); ++b)
+    if (int rc = bk_check_model(models + (size_t)b * RL_BK_NPARAM, "models: instance " + std::to_string(b))) return rc;
+  return RL_OK;
+}
+
+// One text of the device work for both problem types (<BkProblem>: the shared-model entries, <BkProblemV>: the per-instance
+// entries): the bit-equality of the two rests on the launch sequences being the same.
+extern "C++" {
+inline void bk_set_table(rl::BkProblem&, const double*) {}
+inline void bk_set_table(rl::BkProblemV& P, const double* table) { P.m = (rl::BkTab)table; }
+
+// the solve on device pointers: state (and the model table `rows`, if any) from the context's scratch, the launches
+template <typename PT>
+int bk_solve_dev(rl_ctx* ctx, PT P, const std::vector<double>& rows, int B, int N, double* X, double* U, double* T, int max_iter, double* stats) {
+  RL_HIP(hipSetDevice(ctx->device));
+  Arena ar(ctx);
+  rl::BkState st;
+  double* table = nullptr;
+  RL_HIP(ar.carve([&](Arena& x) {
+    rl::carve(x, st, rl::kBkArrays, B, N);
+    if (!rows.empty()) table = x.take<double>(rows.size());
+  }));
+  // a pageable copy on the context's stream, before the first launch: the runtime has read `rows` when it returns (as for
+  // the model table of rl_mintime_solve_vehicles*)
+  if (!rows.empty()) RL_HIP(hipMemcpyAsync(table, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  bk_set_table(P, table);
+  const dim3 grid(B), block(rl::kBkThreads);
+  RL_TRY(launch(ctx, rl::k_bk_init<PT>, grid, block, 0, P, st, X, U, T));
+  // exactly max_iter iterations are enqueued; an instance that has converged or failed returns from each at once
+  for (int it = 0; it < max_iter; ++it) RL_TRY(launch(ctx, rl::k_bk_iter<PT>, grid, block, 0, P, st, 0));
+  RL_TRY(launch(ctx, rl::k_bk_iter<PT>, grid, block, 0, P, st, 1));
+  RL_TRY(launch(ctx, rl::k_bk_unpack<PT>, dim3((N + 63) / 64, B), dim3(64), 0, P, st, X, U, T, stats));
+  RL_HIP(ar.end());
+  return RL_OK;
+}
+
+// the function evaluation on host pointers; nl: doubles of yaw (N shared, B N per instance)
+template <typename PT>
+int bk_eval_host(rl_ctx* ctx, PT P, const std::vector<double>& rows, int B, int N, const double* P0, const double* yaw, size_t nl,
+                 const double* X, const double* U, const double* T, double* eq, double* ineq, double* cost) {
+  const size_t bn = (size_t)B * N;
+  Staging sg(ctx);
+  bk_set_table(P, sg.in(rows.empty() ? nullptr : rows.data(), rows.size()));
+  P.P0 = sg.in(P0, 2 * nl); P.yaw = sg.in(yaw, nl);
+  const double *dX = sg.in(X, bn * 5), *dU = sg.in(U, bn * 2), *dT = sg.in(T, bn);
+  double *deq = sg.out(eq, bn * rl::kBkNe), *din = sg.out(ineq, bn * 2);
+  sg.run([&] { return launch(ctx, rl::k_bk_eval<PT>, dim3((N + 63) / 64, B), dim3(64), 0, P, B, dX, dU, dT, deq, din); });
+  if (int rc = sg.finish()) return rc;
+  for (int b = 0; b < B; ++b) {   // min_time_cost (:9-10), summed in node order
+    double c = 0.0;
+    for (int j = 0; j < N; ++j) c += T[(size_t)b * N + j];
+    cost[b] = c;
+  }
+  return RL_OK;
+}
+}  // extern "C++"
+
+// the table [B, RL_BK_NPARAM] the <BkProblemV> kernels read: the caller's rows, or its one row B times
+static std::vector<double> bk_table(const double* models, int models_per_instance, int B) {
+  std::vector<double> rows((size_t)B * RL_BK_NPARAM);
+  for (int b = 0; b < B; ++b)
+    for (int i = 0; i < RL_BK_NPARAM; ++i) rows[(size_t)b * RL_BK_NPARAM + i] = models[(models_per_instance ? (size_t)b * RL_BK_NPARAM : 0) + i];
+  return rows;
 }
 
 int rl_bicycle_eval_nodes(rl_ctx* ctx, const double* model, int B, int N, const double* P0, const double* yaw,
@@ -2051,19 +2124,7 @@ int rl_bicycle_eval_nodes(rl_ctx* ctx, const double* model, int B, int N, const 
   if (B <= 0 || N < 8) return fail(RL_ERR_ARG, "bad sizes (N >= 8 nodes)");
   rl::BkProblem P{};
   if (int rc = bk_problem(model, N, P)) return rc;
-  const size_t bn = (size_t)B * N;
-  Staging sg(ctx);
-  P.P0 = sg.in(P0, (size_t)2 * N); P.yaw = sg.in(yaw, N);
-  const double *dX = sg.in(X, bn * 5), *dU = sg.in(U, bn * 2), *dT = sg.in(T, bn);
-  double *deq = sg.out(eq, bn * rl::kBkNe), *din = sg.out(ineq, bn * 2);
-  sg.run([&] { return launch(ctx, rl::k_bk_eval, dim3((N + 63) / 64, B), dim3(64), 0, P, B, dX, dU, dT, deq, din); });
-  if (int rc = sg.finish()) return rc;
-  for (int b = 0; b < B; ++b) {   // min_time_cost (:9-10), summed in node order
-    double c = 0.0;
-    for (int j = 0; j < N; ++j) c += T[(size_t)b * N + j];
-    cost[b] = c;
-  }
-  return RL_OK;
+  return bk_eval_host(ctx, P, {}, B, N, P0, yaw, (size_t)N, X, U, T, eq, ineq, cost);
 }
 
 int rl_bicycle_solve_batch_dev(rl_ctx* ctx, const double* model, int B, int N, const double* P0, const double* yaw,
@@ -2073,20 +2134,9 @@ int rl_bicycle_solve_batch_dev(rl_ctx* ctx, const double* model, int B, int N, c
   if (B <= 0 || N < 8 || max_iter < 1 || !(tol > 0.0)) return fail(RL_ERR_ARG, "bad sizes (N >= 8 nodes, max_iter >= 1, tol > 0)");
   rl::BkProblem P{};
   if (int rc = bk_problem(model, N, P)) return rc;
-  RL_HIP(hipSetDevice(ctx->device));
   P.per = bounds_per_instance ? 1 : 0;
   P.P0 = P0; P.yaw = yaw; P.dl = dl; P.dr = dr; P.tol = tol;
-  Arena ar(ctx);
-  rl::BkState st;
-  RL_HIP(ar.carve([&](Arena& x) { rl::carve(x, st, rl::kBkArrays, B, N); }));
-  const dim3 grid(B), block(rl::kBkThreads);
-  RL_TRY(launch(ctx, rl::k_bk_init, grid, block, 0, P, st, X, U, T));
-  // exactly max_iter iterations are enqueued; an instance that has converged or failed returns from each at once
-  for (int it = 0; it < max_iter; ++it) RL_TRY(launch(ctx, rl::k_bk_iter, grid, block, 0, P, st, 0));
-  RL_TRY(launch(ctx, rl::k_bk_iter, grid, block, 0, P, st, 1));
-  RL_TRY(launch(ctx, rl::k_bk_unpack, dim3((N + 63) / 64, B), dim3(64), 0, P, st, X, U, T, stats));
-  RL_HIP(ar.end());
-  return RL_OK;
+  return bk_solve_dev(ctx, P, {}, B, N, X, U, T, max_iter, stats);
 }
 
 int rl_bicycle_solve_batch(rl_ctx* ctx, const double* model, int B, int N, const double* P0, const double* yaw,
@@ -2103,6 +2153,56 @@ int rl_bicycle_solve_batch(rl_ctx* ctx, const double* model, int B, int N, const
   double* dst = sg.out(stats, (size_t)B * rl::kBkStats);
   sg.run([&] {
     return rl_bicycle_solve_batch_dev(ctx, model, B, N, dP0, dyaw, ddl, ddr, bounds_per_instance, dX, dU, dT, max_iter, tol, dst);
+  });
+  return sg.finish();
+}
+
+int rl_bicycle_eval_nodes_lines(rl_ctx* ctx, const double* models, int models_per_instance, int B, int N, const double* P0,
+                                const double* yaw, int lines_per_instance, const double* X, const double* U, const double* T,
+                                double* eq, double* ineq, double* cost) {
+  if (!ctx || !models || !P0 || !yaw || !X || !U || !T || !eq || !ineq || !cost) return fail(RL_ERR_ARG, "null argument");
+  if (B <= 0 || N < 8) return fail(RL_ERR_ARG, "bad sizes (N >= 8 nodes)");
+  if (int rc = bk_check_models(models, models_per_instance, B)) return rc;
+  const std::vector<double> rows = bk_table(models, models_per_instance, B);
+  rl::BkProblemV P{};
+  P.N = N; P.lines = lines_per_instance ? 1 : 0;
+  return bk_eval_host(ctx, P, rows, B, N, P0, yaw, lines_per_instance ? (size_t)B * N : (size_t)N, X, U, T, eq, ineq, cost);
+}
+
+int rl_bicycle_solve_lines_dev(rl_ctx* ctx, const double* models, int models_per_instance, int B, int N, const double* P0,
+                               const double* yaw, int lines_per_instance, const double* dl, const double* dr,
+                               int bounds_per_instance, double* X, double* U, double* T, int max_iter, double tol, double* stats) {
+  if (!ctx || !models || !P0 || !yaw || !dl || !dr || !X || !U || !T || !stats) return fail(RL_ERR_ARG, "null argument");
+  if (B <= 0 || N < 8 || max_iter < 1 || !(tol > 0.0)) return fail(RL_ERR_ARG, "bad sizes (N >= 8 nodes, max_iter >= 1, tol > 0)");
+  if (lines_per_instance && !bounds_per_instance)
+    return fail(RL_ERR_ARG, "lines_per_instance needs bounds_per_instance: dl / dr are distances from the instance's own line");
+  if (int rc = bk_check_models(models, models_per_instance, B)) return rc;
+  const std::vector<double> rows = bk_table(models, models_per_instance, B);
+  rl::BkProblemV P{};
+  P.N = N; P.per = bounds_per_instance ? 1 : 0; P.lines = lines_per_instance ? 1 : 0;
+  P.P0 = P0; P.yaw = yaw; P.dl = dl; P.dr = dr; P.tol = tol;
+  return bk_solve_dev(ctx, P, rows, B, N, X, U, T, max_iter, stats);
+}
+
+int rl_bicycle_solve_lines(rl_ctx* ctx, const double* models, int models_per_instance, int B, int N, const double* P0,
+                           const double* yaw, int lines_per_instance, const double* dl, const double* dr,
+                           int bounds_per_instance, double* X, double* U, double* T, int max_iter, double tol, double* stats) {
+  if (!ctx || !models || !P0 || !yaw || !dl || !dr || !X || !U || !T || !stats) return fail(RL_ERR_ARG, "null argument");
+  if (B <= 0 || N < 8 || max_iter < 1 || !(tol > 0.0)) return fail(RL_ERR_ARG, "bad sizes (N >= 8 nodes, max_iter >= 1, tol > 0)");
+  if (lines_per_instance && !bounds_per_instance)
+    return fail(RL_ERR_ARG, "lines_per_instance needs bounds_per_instance: dl / dr are distances from the instance's own line");
+  if (int rc = bk_check_models(models, models_per_instance, B)) return rc;   // before anything is staged
+  const size_t bn = (size_t)B * N, nb_ = bounds_per_instance ? bn : (size_t)N, nl = lines_per_instance ? bn : (size_t)N;
+  for (size_t i = 0; i < nb_; ++i)
+    if (!(dr[i] < dl[i]))
+      return fail(RL_ERR_ARG, "bounds: instance " + std::to_string(bounds_per_instance ? i / N : 0) + ": need dr < dl at every node (min_time_optimizer.py:66-68)");
+  Staging sg(ctx);
+  const double *dP0 = sg.in(P0, 2 * nl), *dyaw = sg.in(yaw, nl), *ddl = sg.in(dl, nb_), *ddr = sg.in(dr, nb_);
+  double *dX = sg.inout(X, bn * 5), *dU = sg.inout(U, bn * 2), *dT = sg.inout(T, bn);
+  double* dst = sg.out(stats, (size_t)B * rl::kBkStats);
+  sg.run([&] {
+    return rl_bicycle_solve_lines_dev(ctx, models, models_per_instance, B, N, dP0, dyaw, lines_per_instance, ddl, ddr,
+                                      bounds_per_instance, dX, dU, dT, max_iter, tol, dst);
   });
   return sg.finish();
 }

@@ -292,12 +292,7 @@ class BicycleProblem:
         pts = params["traj_d"].points if isinstance(params["traj_d"], Trajectory) else np.asarray(params["traj_d"])
         self.N = int(params.get("N", len(pts)))
         assert self.N == len(pts)
-        self.P0 = np.ascontiguousarray(pts[:, Trajectory.X:Trajectory.Y + 1], dtype=np.float64)              # :26
-        self.yaw = np.ascontiguousarray(pts[:, Trajectory.YAW], dtype=np.float64)                             # :28
-        bl = pts[:, Trajectory.LEFT_BOUND_X:Trajectory.LEFT_BOUND_Y + 1]                                      # :29-32
-        br = pts[:, Trajectory.RIGHT_BOUND_X:Trajectory.RIGHT_BOUND_Y + 1]
-        self.left = np.ascontiguousarray(np.linalg.norm(bl - self.P0, axis=1))                               # dl, :66
-        self.right = np.ascontiguousarray(-np.linalg.norm(br - self.P0, axis=1))                             # dr, :67
+        self.P0, self.yaw, self.left, self.right = self.table_data(pts)
         self.scale_x = np.array([[10.0, 10.0, 3.14, 0.1, 80.0]])                                              # :33-35
         self.scale_u = np.array([[20.0, 1.0]])
         self.scale_t = 1.0
@@ -305,18 +300,37 @@ class BicycleProblem:
         mode = params.get("initial_guess", "reference")
         if mode not in ("reference", "centerline"):
             raise ValueError(f"initial_guess must be 'reference' or 'centerline', not {mode!r}")
-        self.X0 = np.zeros((self.N, 5)); self.U0 = np.zeros((self.N, 2))
-        self.X0[:, 2] = self.yaw
         if mode == "reference":                                                                               # :80-83
+            self.X0 = np.zeros((self.N, 5)); self.U0 = np.zeros((self.N, 2))
+            self.X0[:, 2] = self.yaw
             self.X0[:, 4] = 1.0
             self.T0 = np.ones(self.N)
         else:
-            v = pts[:, Trajectory.SPEED]
-            v = np.where(np.isfinite(v) & (v > 0.0), v, 10.0)
-            self.X0[:, 0:2] = self.P0
-            self.X0[:, 2] = np.unwrap(self.yaw)
-            self.X0[:, 4] = v
-            self.T0 = np.linalg.norm(np.roll(self.P0, -1, axis=0) - self.P0, axis=1) / v
+            self.X0, self.U0, self.T0 = self.centerline_guess(pts, self.P0, self.yaw)
+
+    @staticmethod
+    def table_data(pts):
+        """(P0 [N,2], yaw [N], dl [N] > 0, dr [N] < 0) of one table [N,19]: the line and the distances to its bounds."""
+        P0 = np.ascontiguousarray(pts[:, Trajectory.X:Trajectory.Y + 1], dtype=np.float64)                   # :26
+        yaw = np.ascontiguousarray(pts[:, Trajectory.YAW], dtype=np.float64)                                  # :28
+        bl = pts[:, Trajectory.LEFT_BOUND_X:Trajectory.LEFT_BOUND_Y + 1]                                      # :29-32
+        br = pts[:, Trajectory.RIGHT_BOUND_X:Trajectory.RIGHT_BOUND_Y + 1]
+        left = np.ascontiguousarray(np.linalg.norm(bl - P0, axis=1))                                          # dl, :66
+        right = np.ascontiguousarray(-np.linalg.norm(br - P0, axis=1))                                        # dr, :67
+        return P0, yaw, left, right
+
+    @staticmethod
+    def centerline_guess(pts, P0, yaw):
+        """The "centerline" guess (X0 [N,5], U0 [N,2], T0 [N]) on one table's line."""
+        N = len(pts)
+        X0 = np.zeros((N, 5)); U0 = np.zeros((N, 2))
+        v = pts[:, Trajectory.SPEED]
+        v = np.where(np.isfinite(v) & (v > 0.0), v, 10.0)
+        X0[:, 0:2] = P0
+        X0[:, 2] = np.unwrap(yaw)
+        X0[:, 4] = v
+        T0 = np.linalg.norm(np.roll(P0, -1, axis=0) - P0, axis=1) / v
+        return X0, U0, T0
 
     def solve(self, max_iter=None, tol=None):
         """-> (X [N,5], U [N,2], T [N], stats [12]); stats as include/rl_mincurv.h: rl_bicycle_solve_batch."""
@@ -333,6 +347,27 @@ class BicycleProblem:
         U0 = rep(self.U0) if U0 is None else U0
         T0 = rep(self.T0) if T0 is None else T0
         return ops.bicycle_solve_batch(self.model, self.P0, self.yaw, left, right, X0, U0, T0,
+                                       max_iter=int(max_iter or self.params.get("max_iter", 200)),
+                                       tol=float(tol if tol is not None else 1e-6))
+
+    def tables_data(self, tables):
+        """What solve_tables hands the solver for `tables` [B,N,19]: (P0 [B,N,2], yaw [B,N], dl [B,N], dr [B,N], X0 [B,N,5],
+        U0 [B,N,2], T0 [B,N]), every row derived as a BicycleProblem built on that table derives its own."""
+        tables = np.asarray(tables, dtype=np.float64)
+        if tables.ndim != 3 or tables.shape[1] != self.N or tables.shape[2] != 19:
+            raise ValueError(f"tables: expected [B,{self.N},19], got {tables.shape}")
+        rows = [self.table_data(pts) for pts in tables]
+        guess = [self.centerline_guess(pts, r[0], r[1]) for pts, r in zip(tables, rows)]
+        return tuple(np.stack(a) for a in zip(*rows)) + tuple(np.stack(a) for a in zip(*guess))
+
+    def solve_tables(self, tables, models=None, X0=None, U0=None, T0=None, max_iter=None, tol=None):
+        """One line per instance (ops.bicycle_solve_lines): `tables` [B,N,19] are B lines with their bounds, e.g. the
+        tables of a solved min-curvature batch; instance b is the problem a BicycleProblem built on tables[b] would solve,
+        from its "centerline" guess unless X0 [B,N,5], U0 [B,N,2], T0 [B,N] are given.  models: None (this problem's model for
+        all), one model dict, or B of them.  -> (X [B,N,5], U [B,N,2], T [B,N], stats [B,12])."""
+        P0, yaw, dl, dr, Xc, Uc, Tc = self.tables_data(tables)
+        return ops.bicycle_solve_lines(self.model if models is None else models, P0, yaw, dl, dr,
+                                       Xc if X0 is None else X0, Uc if U0 is None else U0, Tc if T0 is None else T0,
                                        max_iter=int(max_iter or self.params.get("max_iter", 200)),
                                        tol=float(tol if tol is not None else 1e-6))
 

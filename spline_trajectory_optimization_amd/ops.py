@@ -1058,3 +1058,102 @@ def bicycle_solve_torch(model, P0, yaw, dl, dr, X, U, T, max_iter=200, tol=1e-6)
     Returns the stats tensor [B,12]."""
     _assert_cuda_f64(P0, yaw, dl, dr, X, U, T)
     return _bicycle_solve(_Torch, model, P0, yaw, dl, dr, X, U, T, max_iter, tol, None)
+
+
+_BK_POSITIVE = ("L", "delta_max", "v_max", "delta_dot_max", "acc_max")   # and a_lon_max > a_lon_min: what the library checks per row
+
+
+def bk_models_table(models, B=None):
+    """B bicycle models -> the [B, len(BK_PARAMS)] float64 array rl_bicycle_solve_lines* takes.  `models`: a sequence of B
+    model dicts (the reference test's keys) or an array of that shape.  Checks what the library checks, before anything
+    reaches it: B (when given), every row finite, L, delta_max, v_max, delta_dot_max, acc_max > 0 and a_lon_max > a_lon_min
+    -- a ValueError names the first bad instance."""
+    if len(models) > 0 and isinstance(models[0], dict):
+        tab = np.array([[float(m[k]) for k in BK_PARAMS] for m in models], dtype=np.float64)
+    else:
+        tab = np.array(models, dtype=np.float64, order="C")
+    if tab.ndim != 2 or tab.shape[1] != len(BK_PARAMS) or tab.shape[0] == 0:
+        raise ValueError(f"models: expected B dicts or an array [B, {len(BK_PARAMS)}], got shape {tab.shape}")
+    if B is not None and tab.shape[0] != B:
+        raise ValueError(f"models: {tab.shape[0]} vehicles for a batch of {B} instances")
+    for b, row in enumerate(tab):
+        if not np.all(np.isfinite(row)):
+            raise ValueError(f"models: instance {b}: parameter {BK_PARAMS[int(np.flatnonzero(~np.isfinite(row))[0])]} is not finite")
+        for k in _BK_POSITIVE:
+            if not row[BK_PARAMS.index(k)] > 0.0:
+                raise ValueError(f"models: instance {b}: {k} must be > 0")
+        if not row[BK_PARAMS.index("a_lon_max")] > row[BK_PARAMS.index("a_lon_min")]:
+            raise ValueError(f"models: instance {b}: a_lon_max must be > a_lon_min")
+    return np.ascontiguousarray(tab)
+
+
+def _bk_models(models, B):
+    """(host table, models_per_instance) of a `models` argument: one dict (or one row [8]) for all, or B of them."""
+    if isinstance(models, dict) or (not isinstance(models, (list, tuple)) and np.ndim(models) == 1):
+        return bk_models_table([models]), 0
+    return bk_models_table(models, B), 1
+
+
+def _bk_lines(A, B, N, P0, yaw):
+    """lines_per_instance of a P0 / yaw pair, shapes checked: [N,2] / [N] shared or [B,N,2] / [B,N] per instance."""
+    lines = len(P0.shape) == 3
+    A.check(P0, "P0", (B, N, 2) if lines else (N, 2))
+    A.check(yaw, "yaw", (B, N) if lines else (N,))
+    return lines
+
+
+def _bicycle_solve_lines(A, models, P0, yaw, dl, dr, X, U, T, max_iter, tol, device):
+    """The per-instance bicycle solve in A's memory space, X / U / T in place -> stats [B,12].  Everything that can be
+    refused is refused here, as a ValueError, before any device call."""
+    if len(T.shape) != 2:
+        raise ValueError(f"T: expected [B,N], got {tuple(T.shape)}")
+    B, N = T.shape
+    tab, mper = _bk_models(models, B)
+    lines = _bk_lines(A, B, N, P0, yaw)
+    per = len(dl.shape) == 2
+    if lines and not per:
+        raise ValueError("dl / dr: one line per instance needs [B,N] bounds (distances from the instance's own line)")
+    A.check(dl, "dl", (B, N) if per else (N,)); A.check(dr, "dr", (B, N) if per else (N,))
+    A.check(X, "X", (B, N, 5)); A.check(U, "U", (B, N, 2)); A.check(T, "T", (B, N))
+    A.same_device(X, "X", (("U", U), ("T", T), ("P0", P0), ("yaw", yaw), ("dl", dl), ("dr", dr)))
+    ctx = A.bind(None, X, device)
+    stats = A.new(X, (B, 12), zero=True)
+    check(A.entry(ctx, "rl_bicycle_solve_lines", "rl_bicycle_solve_lines_dev")(
+        ctx.h, _Host.ptr(tab), int(mper), B, N, A.ptr(P0), A.ptr(yaw), int(lines), A.ptr(dl), A.ptr(dr), int(per), A.ptr(X),
+        A.ptr(U), A.ptr(T), int(max_iter), float(tol), A.ptr(stats)))
+    return stats
+
+
+def bicycle_solve_lines(models, P0, yaw, dl, dr, X0, U0, T0, max_iter=200, tol=1e-6, device=None):
+    """bicycle_solve_batch with ONE LINE AND ONE VEHICLE PER INSTANCE (include/rl_mincurv.h: rl_bicycle_solve_lines).
+    models: one model dict, or B of them (or an array [B,8], bk_models_table).  P0 / yaw: [N,2] / [N] shared, or
+    [B,N,2] / [B,N] -- then dl / dr must be [B,N] too.  Everything else, and the result, as bicycle_solve_batch: B equal
+    rows give its bits."""
+    X, U, T = _copy_guess(X0, U0, T0)
+    return X, U, T, _bicycle_solve_lines(_Host, models, _f64(P0), _f64(yaw), _f64(dl), _f64(dr), X, U, T, max_iter, tol, device)
+
+
+def bicycle_solve_lines_torch(models, P0, yaw, dl, dr, X, U, T, max_iter=200, tol=1e-6):
+    """rl_bicycle_solve_lines_dev on DEVICE tensors (float64, cuda, contiguous), shapes as bicycle_solve_lines; X, U, T are
+    updated in place.  `models` is a HOST argument, read before the call returns.  Enqueues on torch's current stream, no
+    sync.  Returns the stats tensor [B,12]."""
+    return _bicycle_solve_lines(_Torch, models, P0, yaw, dl, dr, X, U, T, max_iter, tol, None)
+
+
+def bicycle_eval_nodes_lines(models, P0, yaw, X, U, T, device=None):
+    """bicycle_eval_nodes with the per-instance data of bicycle_solve_lines (include/rl_mincurv.h:
+    rl_bicycle_eval_nodes_lines): models one dict or B, P0 / yaw [N,2] / [N] or [B,N,2] / [B,N]; X [B,N,5], U [B,N,2],
+    T [B,N].  Returns (eq [B,N,6], ineq [B,N,2], cost [B])."""
+    X, U, T, P0, yaw = _f64(X), _f64(U), _f64(T), _f64(P0), _f64(yaw)
+    if T.ndim != 2:
+        raise ValueError(f"T: expected [B,N], got {T.shape}")
+    B, N = T.shape
+    tab, mper = _bk_models(models, B)
+    lines = _bk_lines(_Host, B, N, P0, yaw)
+    _check_np(X, "X", (B, N, 5)); _check_np(U, "U", (B, N, 2))
+    ctx = Context.get(device)
+    eq = np.empty((B, N, 6)); ineq = np.empty((B, N, 2)); cost = np.empty(B)
+    check(ctx.lib.rl_bicycle_eval_nodes_lines(ctx.h, _Host.ptr(tab), int(mper), B, N, _Host.ptr(P0), _Host.ptr(yaw), int(lines),
+                                              _Host.ptr(X), _Host.ptr(U), _Host.ptr(T), _Host.ptr(eq), _Host.ptr(ineq),
+                                              _Host.ptr(cost)))
+    return eq, ineq, cost

@@ -526,6 +526,40 @@ int rl_mintime_solve_vehicles_dev(rl_ctx* ctx, const double* models, int B, int 
                                   const double* left, const double* right, int bounds_per_instance, double margin,
                                   double track_length, double average_track_width, double speed_cap, double* X, double* U,
                                   double* T, int max_iter, double tol, double* stats);
+/* One CENTRE LINE per instance as well: the two vehicles entries with T tracks of equal node count in one call -- V
+ * vehicles on T circuits, lap time against circuit size, a circuit and its mirror image, centre-line variants.
+ *   s, kappa [T,N]: row t = track t (DEVICE pointers in _dev, like left / right)
+ *   track_length, average_track_width, speed_cap [T]: HOST arrays in both entries
+ *   track_of [B]: a HOST int array in both entries, instance b runs on track track_of[b]; NULL = the identity, which
+ *       needs T == B
+ *   models [B, RL_DT_NPARAM] when models_per_instance != 0, else [1, RL_DT_NPARAM] for all instances; a HOST array
+ *   left, right [B,N]: always per instance (bounds_per_instance is implied); margin one scalar (fold per-vehicle
+ *       margins into left / right as for the vehicles entries)
+ * The scales of instance b are those of the other entries, from ITS model and ITS track's average_track_width /
+ * speed_cap, so T = 1 with equal rows gives the bits of rl_mintime_solve_batch, T = 1 with B rows those of
+ * rl_mintime_solve_vehicles, and every instance of a mixed batch the bits of its own single call.  Refused with
+ * RL_ERR_ARG before anything is staged or enqueued, naming the first bad instance or track: the model checks of the
+ * vehicles entries; track_of outside [0, T); track_length, average_track_width or speed_cap not finite or <= 0; in the
+ * host entry also s not strictly increasing within [0, track_length) and non-finite kappa.  The table row of an
+ * instance (p | sw | se, 44 doubles of 48) carries its track_length in slot 44 and its track in slot 45; all host
+ * arrays have been read when the call returns.  Sub-batches, the polling of the host entry and stats [B,12] are
+ * unchanged. */
+int rl_mintime_solve_tracks(rl_ctx* ctx, const double* models, int models_per_instance, int B, int N, int T,
+                            const int* track_of, const double* s, const double* kappa, const double* left,
+                            const double* right, double margin, const double* track_length,
+                            const double* average_track_width, const double* speed_cap, double* X, double* U, double* Tn,
+                            int max_iter, double tol, double* stats);
+int rl_mintime_solve_tracks_dev(rl_ctx* ctx, const double* models, int models_per_instance, int B, int N, int T,
+                                const int* track_of, const double* s, const double* kappa, const double* left,
+                                const double* right, double margin, const double* track_length,
+                                const double* average_track_width, const double* speed_cap, double* X, double* U,
+                                double* Tn, int max_iter, double tol, double* stats);
+/* The host half of those calls without a device: the checks above (T >= 1), or those of the vehicles entries with the
+ * scalars average_track_width[0], speed_cap[0] (T = 0, models [B, RL_DT_NPARAM]), then the table rows [B,48] the call
+ * would copy to the device: p | sw | se | track_length | track (an int) | 0 | 0.  For tests. */
+int rl_debug_mt_rows(const double* models, int models_per_instance, int B, int T, const int* track_of,
+                     const double* track_length, const double* average_track_width, const double* speed_cap,
+                     double* rows);
 
 /* ---- the bicycle min-time NLP of set_up_bicycle_problem (min_time_optm/min_time_optimizer.py:14-90; models/
  * dynamic_bicycle.py, utils/integrator.py:13-19, utils/utils.py:3-13): kinematic bicycle, RK4 defects, closed lap,

@@ -1,1 +1,1 @@
-from spline_trajectory_optimization_amd.models.race_track import RaceTrack  # noqa: F401
+from spline_trajectory_optimization_amd.models.race_track import RaceTrack, interval_for_nodes, race_track_with_nodes  # noqa: F401

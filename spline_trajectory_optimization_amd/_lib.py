@@ -56,6 +56,7 @@ _SOLVE_BATCH_FROM = [_vp, _vp, _i, _D, _i, _D, _I, _i, _i, _i, _D, _D, _I, _I, _
 _SPLINE_FIT = [_vp, _vp, _D, _i, _i, _i, _D, _i, _D, _D]
 _DT_EVAL = [_vp, _dp, _i, _i, _dp, _dp, _dp, _dp, _d, _d, _dp, _dp, _dp, _dp, _dp, _dp]
 _MINTIME_SOLVE = [_vp, _dp, _i, _i, _D, _D, _D, _D, _i, _d, _d, _d, _d, _D, _D, _D, _i, _d, _D]   # and _vehicles
+_MINTIME_TRACKS = [_vp, _dp, _i, _i, _i, _i, _ip, _D, _D, _D, _D, _d, _dp, _dp, _dp, _D, _D, _D, _i, _d, _D]
 _BICYCLE_SOLVE = [_vp, _dp, _i, _i, _D, _D, _D, _D, _i, _D, _D, _D, _i, _d, _D]
 _BICYCLE_LINES = [_vp, _dp, _i, _i, _i, _D, _D, _i, _D, _D, _i, _D, _D, _D, _i, _d, _D]
 _QSS_SIM = [_vp, _D, _i, _i, _dp, _dp, _i, _dp, _dp, _i, _dp, _I]
@@ -114,6 +115,9 @@ _SIGNATURES = {
     "rl_mintime_solve_batch_dev": _dev(_MINTIME_SOLVE),
     "rl_mintime_solve_vehicles": _host(_MINTIME_SOLVE),
     "rl_mintime_solve_vehicles_dev": _dev(_MINTIME_SOLVE),
+    "rl_mintime_solve_tracks": _host(_MINTIME_TRACKS),
+    "rl_mintime_solve_tracks_dev": _dev(_MINTIME_TRACKS),
+    "rl_debug_mt_rows": (_i, [_dp, _i, _i, _i, _ip, _dp, _dp, _dp, _dp]),
     "rl_bicycle_eval_nodes": (_i, [_vp, _dp, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "rl_bicycle_solve_batch": _host(_BICYCLE_SOLVE),
     "rl_bicycle_solve_batch_dev": _dev(_BICYCLE_SOLVE),

@@ -1727,24 +1727,30 @@ namespace {
 // veh: one vehicle per instance -- V carries the group's slice of the vehicle table and the kernels that read the model are
 // launched as their <MtProblemV> instance (rl_mintime.hpp); P.p / sw / se are then NaN, so that a kernel that read the model
 // from its arguments in such a call could not go unnoticed.
-struct MtGroup { hipStream_t q; rl::MtProblem P; rl::MtProblemV V; bool veh; rl::MtState st; double *X, *U, *T, *stats; dim3 rows, per_node, per_inst; };
+// trk (rl_mintime_solve_tracks*): one centre line per instance as well -- K carries the slice of the table and the tables s /
+// kappa [T,N], the kernels are launched as their <MtProblemT> instance.
+struct MtGroup { hipStream_t q; rl::MtProblem P; rl::MtProblemV V; rl::MtProblemT K; bool veh, trk; rl::MtState st; double *X, *U, *T, *stats; dim3 rows, per_node, per_inst; };
 using MtKernel = void (*)(rl::MtProblem, rl::MtState);
 using MtKernelV = void (*)(rl::MtProblemV, rl::MtState);
-struct MtKernels { MtKernel shared; MtKernelV vehicles; };   // the two forms of a kernel that reads the model
-#define MT_K(name) MtKernels{rl::name<rl::MtProblem>, rl::name<rl::MtProblemV>}
-#define MT_KT(name, arg) MtKernels{rl::name<arg, rl::MtProblem>, rl::name<arg, rl::MtProblemV>}
+using MtKernelT = void (*)(rl::MtProblemT, rl::MtState);
+struct MtKernels { MtKernel shared; MtKernelV vehicles; MtKernelT tracks; };   // the three forms of a kernel that reads the model or the track
+#define MT_K(name) MtKernels{rl::name<rl::MtProblem>, rl::name<rl::MtProblemV>, rl::name<rl::MtProblemT>}
+#define MT_KT(name, arg) MtKernels{rl::name<arg, rl::MtProblem>, rl::name<arg, rl::MtProblemV>, rl::name<arg, rl::MtProblemT>}
 int mt_run(const rl_ctx* ctx, const MtGroup& G, MtKernel kernel, dim3 grid, int threads) {   // a kernel that never reads the model
   return launch(ctx, G.q, kernel, grid, dim3(threads), 0, G.P, G.st);
 }
 int mt_run_model(const rl_ctx* ctx, const MtGroup& G, MtKernels k, dim3 grid, int threads) {
+  if (G.trk) return launch(ctx, G.q, k.tracks, grid, dim3(threads), 0, G.K, G.st);
   return G.veh ? launch(ctx, G.q, k.vehicles, grid, dim3(threads), 0, G.V, G.st)
                : launch(ctx, G.q, k.shared, grid, dim3(threads), 0, G.P, G.st);
 }
 int mt_pack(const rl_ctx* ctx, const MtGroup& G) {
+  if (G.trk) return launch(ctx, G.q, rl::k_mt_pack<rl::MtProblemT>, G.rows, dim3(64), 0, G.K, G.st, G.X, G.U, G.T);
   return G.veh ? launch(ctx, G.q, rl::k_mt_pack<rl::MtProblemV>, G.rows, dim3(64), 0, G.V, G.st, G.X, G.U, G.T)
                : launch(ctx, G.q, rl::k_mt_pack<rl::MtProblem>, G.rows, dim3(64), 0, G.P, G.st, G.X, G.U, G.T);
 }
 int mt_unpack(const rl_ctx* ctx, const MtGroup& G) {
+  if (G.trk) return launch(ctx, G.q, rl::k_mt_unpack<rl::MtProblemT>, G.rows, dim3(64), 0, G.K, G.st, G.X, G.U, G.T);
   return G.veh ? launch(ctx, G.q, rl::k_mt_unpack<rl::MtProblemV>, G.rows, dim3(64), 0, G.V, G.st, G.X, G.U, G.T)
                : launch(ctx, G.q, rl::k_mt_unpack<rl::MtProblem>, G.rows, dim3(64), 0, G.P, G.st, G.X, G.U, G.T);
 }
@@ -1828,20 +1834,60 @@ int mt_check_models(const double* models, int B) {
   return RL_OK;
 }
 
+// What a tracks call (rl_mintime_solve_tracks*) has per track or per instance, all HOST arrays: checked by mt_check_tracks.
+struct MtTracks { int T; const int* track_of; const double *track_length, *average_track_width, *speed_cap; int models_per_instance; };
+int mt_check_tracks(const MtTracks& tr, const double* models, int B) {
+  if (tr.T <= 0 || !tr.track_length || !tr.average_track_width || !tr.speed_cap) return fail(RL_ERR_ARG, "tracks: T >= 1 and the three arrays [T]");
+  if (!tr.track_of && tr.T != B) return fail(RL_ERR_ARG, "track_of: NULL is the identity and needs T == B");
+  RL_TRY(mt_check_models(models, tr.models_per_instance ? B : 1));
+  for (int b = 0; tr.track_of && b < B; ++b)
+    if (tr.track_of[b] < 0 || tr.track_of[b] >= tr.T)
+      return fail(RL_ERR_ARG, "track_of: instance " + std::to_string(b) + ": track " + std::to_string(tr.track_of[b]) + " outside [0, " + std::to_string(tr.T) + ")");
+  for (int t = 0; t < tr.T; ++t) {
+    const struct { const double* v; const char* name; } positive[] = {
+        {tr.track_length, "track_length"}, {tr.average_track_width, "average_track_width"}, {tr.speed_cap, "speed_cap"}};
+    for (const auto& q : positive)
+      if (!std::isfinite(q.v[t]) || !(q.v[t] > 0.0)) return fail(RL_ERR_ARG, "tracks: track " + std::to_string(t) + ": " + q.name + " must be finite and > 0");
+  }
+  return RL_OK;
+}
+
+// The table of a vehicles or a tracks call: row b = p | sw | se of instance b, and in a tracks call the length and the index
+// of its track (rl_mintime.hpp: kMtRowLen, kMtRowTrack).  `rows` [B, kMtRow] arrives zeroed; the arguments are checked.
+void mt_build_rows(double* rows, const double* models, int B, const MtTracks* tr, double average_track_width, double speed_cap) {
+  for (int b = 0; b < B; ++b) {
+    const double* m = models + (tr && !tr->models_per_instance ? 0 : (size_t)b * RL_DT_NPARAM);
+    double* r = rows + (size_t)b * rl::kMtRow;
+    for (int i = 0; i < rl::DT_NPARAM; ++i) r[i] = m[i];
+    if (tr) {   // the instance's track: its scales, its length, its index (an int in the low word of the slot)
+      const int t = tr->track_of ? tr->track_of[b] : b;
+      mt_scales(m, tr->average_track_width[t], tr->speed_cap[t], r + rl::kMtRowSw, r + rl::kMtRowSe);
+      r[rl::kMtRowLen] = tr->track_length[t];
+      std::memcpy(r + rl::kMtRowTrack, &t, sizeof(int));
+    } else {
+      mt_scales(m, average_track_width, speed_cap, r + rl::kMtRowSw, r + rl::kMtRowSe);
+    }
+  }
+}
+
 // Both entry points of the solve, on device pointers.  poll: stop enqueueing once every instance has finished (the host
 // entry point, which synchronises anyway); without it all max_iter iterations are enqueued and the call does not wait.
 // vehicles: `model` is [B, RL_DT_NPARAM], one row per instance (rl_mintime_solve_vehicles*).
+// tr: a tracks call (rl_mintime_solve_tracks*) -- s, kappa are [T,N], `model` is [B or 1, RL_DT_NPARAM], the scalars
+// track_length / average_track_width / speed_cap are not read; `vehicles` is then true (the table is built either way).
 int mintime_solve_common(rl_ctx* ctx, const double* model, bool vehicles, int B, int N, const double* s, const double* kappa, const double* left,
                          const double* right, int bounds_per_instance, double margin, double track_length, double average_track_width,
-                         double speed_cap, double* X, double* U, double* T, int max_iter, double tol, double* stats, bool poll) {
+                         double speed_cap, double* X, double* U, double* T, int max_iter, double tol, double* stats, bool poll,
+                         const MtTracks* tr = nullptr) {
   if (!ctx || !model || !s || !kappa || !left || !right || !X || !U || !T || !stats) return fail(RL_ERR_ARG, "null argument");
-  if (B <= 0 || N < 8 || !(track_length > 0.0) || max_iter < 1 || !(tol > 0.0)) return fail(RL_ERR_ARG, "bad sizes (N >= 8 nodes)");
-  if (!(average_track_width > 0.0) || !(speed_cap > 0.0)) return fail(RL_ERR_ARG, "bad scales");
-  if (vehicles) RL_TRY(mt_check_models(model, B));
+  if (B <= 0 || N < 8 || !(tr || track_length > 0.0) || max_iter < 1 || !(tol > 0.0)) return fail(RL_ERR_ARG, "bad sizes (N >= 8 nodes)");
+  if (!tr && (!(average_track_width > 0.0) || !(speed_cap > 0.0))) return fail(RL_ERR_ARG, "bad scales");
+  if (tr) RL_TRY(mt_check_tracks(*tr, model, B));
+  else if (vehicles) RL_TRY(mt_check_models(model, B));
   RL_HIP(hipSetDevice(ctx->device));
   rl::MtProblem P;
   P.N = N; P.bounds_per_instance = bounds_per_instance ? 1 : 0;
-  P.margin = margin; P.track_length = track_length;
+  P.margin = margin; P.track_length = tr ? std::numeric_limits<double>::quiet_NaN() : track_length;
   P.s = s; P.kappa = kappa; P.left = left; P.right = right;
   std::vector<double> rows;   // vehicles: the table p | sw | se, kMtRow doubles per instance
   if (vehicles) {
@@ -1850,12 +1896,7 @@ int mintime_solve_common(rl_ctx* ctx, const double* model, bool vehicles, int B,
     for (double& v : P.sw) v = nan;
     for (double& v : P.se) v = nan;
     rows.assign((size_t)B * rl::kMtRow, 0.0);
-    for (int b = 0; b < B; ++b) {
-      const double* m = model + (size_t)b * RL_DT_NPARAM;
-      double* r = rows.data() + (size_t)b * rl::kMtRow;
-      for (int i = 0; i < rl::DT_NPARAM; ++i) r[i] = m[i];
-      mt_scales(m, average_track_width, speed_cap, r + rl::kMtRowSw, r + rl::kMtRowSe);
-    }
+    mt_build_rows(rows.data(), model, B, tr, average_track_width, speed_cap);
   } else {
     for (int i = 0; i < rl::DT_NPARAM; ++i) P.p[i] = model[i];
     mt_scales(model, average_track_width, speed_cap, P.sw, P.se);
@@ -1926,11 +1967,13 @@ int mintime_solve_common(rl_ctx* ctx, const double* model, bool vehicles, int B,
     MtGroup& G = grp[g];
     G.q = fork_stream(ctx, g); G.P = P; G.st = rl::slice(st, rl::kMtArrays, b0, nb);
     if (P.bounds_per_instance) { G.P.left = left + o; G.P.right = right + o; }
-    G.veh = vehicles;
+    G.veh = vehicles; G.trk = tr != nullptr;
     const double* row0 = table + (vehicles ? (size_t)b0 * rl::kMtRow : 0);   // the group's slice of the table, as of left / right
     G.V.p = (rl::MtTab)row0; G.V.sw = (rl::MtTab)(row0 + rl::kMtRowSw); G.V.se = (rl::MtTab)(row0 + rl::kMtRowSe);
     G.V.N = N; G.V.s = s; G.V.kappa = kappa; G.V.left = G.P.left; G.V.right = G.P.right;
-    G.V.bounds_per_instance = P.bounds_per_instance; G.V.margin = margin; G.V.track_length = track_length;
+    G.V.bounds_per_instance = P.bounds_per_instance; G.V.margin = margin; G.V.track_length = P.track_length;
+    G.K.p = G.V.p; G.K.sw = G.V.sw; G.K.se = G.V.se; G.K.N = N; G.K.s = s; G.K.kappa = kappa; G.K.left = G.P.left; G.K.right = G.P.right;
+    G.K.bounds_per_instance = P.bounds_per_instance; G.K.margin = margin; G.K.track_length = P.track_length;
     G.X = X + o * 6; G.U = U + o * 4; G.T = T + o; G.stats = stats + (size_t)b0 * rl::kMtStats;
     G.rows = dim3(rl::mt_row_blocks(N), nb); G.per_node = dim3(N, nb); G.per_inst = dim3(nb);
   }
@@ -2030,6 +2073,62 @@ int rl_mintime_solve_vehicles(rl_ctx* ctx, const double* models, int B, int N, c
   if (B > 0) RL_TRY(mt_check_models(models, B));   // before anything is staged
   return mintime_solve_host(ctx, models, true, B, N, s, kappa, left, right, bounds_per_instance, margin, track_length,
                             average_track_width, speed_cap, X, U, T, max_iter, tol, stats);
+}
+
+// The host half of a vehicles (T = 0: the scalars average_track_width[0], speed_cap[0]) or a tracks call (T >= 1) without a
+// device: the checks, then the table [B,48] the call would copy.  What the CPU tests compare with the shared entries' scales.
+int rl_debug_mt_rows(const double* models, int models_per_instance, int B, int T, const int* track_of, const double* track_length,
+                     const double* average_track_width, const double* speed_cap, double* rows) {
+  if (!models || !rows || !average_track_width || !speed_cap || B <= 0 || T < 0) return fail(RL_ERR_ARG, "null argument or bad sizes");
+  const MtTracks tr{T, track_of, track_length, average_track_width, speed_cap, models_per_instance ? 1 : 0};
+  if (T > 0) RL_TRY(mt_check_tracks(tr, models, B));
+  else RL_TRY(mt_check_models(models, B));
+  std::fill(rows, rows + (size_t)B * rl::kMtRow, 0.0);
+  mt_build_rows(rows, models, B, T > 0 ? &tr : nullptr, average_track_width[0], speed_cap[0]);
+  return RL_OK;
+}
+
+// One centre line per instance: s, kappa [T,N] DEVICE pointers; everything per track or per instance that the host reads
+// (models, track_of, the three arrays [T]) is a HOST array, checked before anything is enqueued.
+int rl_mintime_solve_tracks_dev(rl_ctx* ctx, const double* models, int models_per_instance, int B, int N, int T,
+                                const int* track_of, const double* s, const double* kappa, const double* left,
+                                const double* right, double margin, const double* track_length,
+                                const double* average_track_width, const double* speed_cap, double* X, double* U,
+                                double* Tn, int max_iter, double tol, double* stats) {
+  const MtTracks tr{T, track_of, track_length, average_track_width, speed_cap, models_per_instance ? 1 : 0};
+  return mintime_solve_common(ctx, models, true, B, N, s, kappa, left, right, 1, margin, 0.0, 0.0, 0.0, X, U, Tn, max_iter, tol,
+                              stats, false, &tr);
+}
+
+int rl_mintime_solve_tracks(rl_ctx* ctx, const double* models, int models_per_instance, int B, int N, int T,
+                            const int* track_of, const double* s, const double* kappa, const double* left,
+                            const double* right, double margin, const double* track_length,
+                            const double* average_track_width, const double* speed_cap, double* X, double* U, double* Tn,
+                            int max_iter, double tol, double* stats) {
+  if (!ctx || !models || !s || !kappa || !left || !right) return fail(RL_ERR_ARG, "null argument");
+  if (B <= 0 || N < 8) return fail(RL_ERR_ARG, "bad sizes (N >= 8 nodes)");
+  const MtTracks tr{T, track_of, track_length, average_track_width, speed_cap, models_per_instance ? 1 : 0};
+  RL_TRY(mt_check_tracks(tr, models, B));   // before anything is staged
+  for (int t = 0; t < T; ++t) {
+    const double *st = s + (size_t)t * N, *kt = kappa + (size_t)t * N;
+    for (int j = 0; j < N; ++j) {
+      if (!std::isfinite(kt[j])) return fail(RL_ERR_ARG, "tracks: track " + std::to_string(t) + ": kappa is not finite at node " + std::to_string(j));
+      if (!(st[j] >= 0.0 && st[j] < track_length[t] && (j == 0 || st[j] > st[j - 1])))
+        return fail(RL_ERR_ARG, "tracks: track " + std::to_string(t) + ": s must increase strictly within [0, track_length) (node " + std::to_string(j) + ")");
+    }
+  }
+  const size_t bn = (size_t)B * N, tn = (size_t)T * N;
+  for (size_t i = 0; i < bn; ++i)
+    if (!(right[i] + margin < left[i] - margin)) return fail(RL_ERR_ARG, "track narrower than the vehicle plus margins (min_time_optimizer.py:135)");
+  Staging sg(ctx);
+  const double *ds = sg.in(s, tn), *dk = sg.in(kappa, tn), *dl = sg.in(left, bn), *dr = sg.in(right, bn);
+  double *dX = sg.inout(X, bn * 6), *dU = sg.inout(U, bn * 4), *dT = sg.inout(Tn, bn);
+  double* dst = sg.out(stats, (size_t)B * rl::kMtStats);
+  sg.run([&] {
+    return mintime_solve_common(ctx, models, true, B, N, ds, dk, dl, dr, 1, margin, 0.0, 0.0, 0.0, dX, dU, dT, max_iter, tol, dst,
+                                true, &tr);
+  });
+  return sg.finish();
 }
 
 // ---- the bicycle min-time NLP (rl_bicycle.hpp)

@@ -86,8 +86,9 @@ struct MtProblem {
 // complete before the first kernel of the solve starts, and by nothing else), which makes every read of a value a scalar
 // load whatever the kernel stores in between -- the registers a value occupies are the ones the kernel argument
 // occupied.  The pair functions and the kernels that read the model are templates over the problem type -- <MtProblem> with
-// the model in the kernel arguments (what the shared-model entries launch), <MtProblemV> with the table -- and read P.p[],
-// P.sw[], P.se[] from either; the expressions on the values are the same text in the same order.  The other kernels
+// the model in the kernel arguments (what the shared-model entries launch), <MtProblemV> with the table, <MtProblemT> (below)
+// with the table and one centre line per instance -- and read P.p[], P.sw[], P.se[], P.s[], P.kappa[], P.track_length from
+// any of them; the expressions on the values are the same text in the same order.  The other kernels
 // (k_mt_assemble, k_mt_gc_pack, k_mt_kkt, k_mt_kkt4, k_mt_dir, k_mt_step, k_mt_init) never look at the model and take
 // MtProblem in both cases.
 typedef const double __attribute__((address_space(4))) * MtTab;
@@ -104,6 +105,33 @@ __device__ __forceinline__ void mt_model(MtProblem&, int) {}
 __device__ __forceinline__ void mt_model(MtProblemV& P, int b) {
   const size_t o = (size_t)b * kMtRow;
   P.p += o; P.sw += o; P.se += o;
+}
+
+// One centre line per instance as well (rl_mintime_solve_tracks*): MtProblemV with s / kappa as tables [T,N] and two more
+// entries of the instance's row -- slot kMtRowLen the track_length of its track, slot kMtRowTrack the index of its track
+// (an int in the low word of the slot; the high word and slots 46, 47 stay zero).  mt_model does all of the move: the
+// row pointers, P.track_length from the row, s / kappa to the track's row -- in mt_model rather than in mt_instance
+// because k_mt_hes_values, k_mt_jac_dirs, k_mt_hes_point and k_mt_unpack read s / kappa and never call mt_instance; the
+// template kernels that do call it call mt_model first, and mt_instance moves left / right as in the other two forms.
+// The row index comes from the row, which is read with scalar loads, so the two base addresses stay wave-uniform; the
+// reads P.s[j], P.kappa[j] are the per-lane loads they are in the other forms.
+typedef const int __attribute__((address_space(4))) * MtTabI;
+constexpr int kMtRowLen = kMtRowSe + kMtNe, kMtRowTrack = kMtRowLen + 1;   // 44, 45
+static_assert(kMtRowTrack < kMtRow, "a tracks row holds p | sw | se | track_length | track");
+struct MtProblemT {
+  MtTab p, sw, se;    // row 0 of the (sub-)batch
+  int N;
+  const double* s; const double* kappa;   // [T,N]: row 0; mt_model moves them to the instance's track
+  const double* left; const double* right;
+  int bounds_per_instance;
+  double margin, track_length;   // track_length: NaN in the arguments, set from the row by mt_model
+};
+__device__ __forceinline__ void mt_model(MtProblemT& P, int b) {
+  const size_t o = (size_t)b * kMtRow;
+  P.p += o; P.sw += o; P.se += o;
+  P.track_length = P.p[kMtRowLen];
+  const size_t t = (size_t)((MtTabI)(P.p + kMtRowTrack))[0] * P.N;
+  P.s += t; P.kappa += t;
 }
 
 template <typename S> struct MtLift;

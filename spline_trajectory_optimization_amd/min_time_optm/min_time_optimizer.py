@@ -136,14 +136,24 @@ class DoubleTrackProblem:
         X, U, T, st = self.solve_batch(self.left[None], self.right[None], max_iter=max_iter, tol=tol)
         return X[0], U[0], T[0], st[0]
 
-    def solve_batch(self, left, right, X0=None, U0=None, T0=None, max_iter=None, tol=None, models=None):
+    def solve_batch(self, left, right, X0=None, U0=None, T0=None, max_iter=None, tol=None, models=None, tracks=None,
+                    track_of=None):
         """B instances that differ in their boundary distances left/right [B,N] (and optionally in their initial
         guesses).  The reference's IPOPT tolerance `tol` (yaml :8) is a loose 0.1; the default here is 1e-6.
         models: None, or B model dicts (or an array [B, len(ops.DT_PARAMS)]): instance b is then solved for vehicle b
         (ops.mintime_solve_vehicles) instead of for the problem's own model; vehicles of different vehicle_width /
-        safety_margin get their margins folded into left / right (fold_margins).  The initial guesses stay the problem's."""
+        safety_margin get their margins folded into left / right (fold_margins).  The initial guesses stay the problem's.
+        tracks: None, or T centre lines of equal node count (ops.mintime_solve_tracks): DoubleTrackProblems, or dicts with
+        "s", "kappa", "track_length" (or "L") and optionally "average_track_width", "speed_cap" (else this problem's);
+        instance b runs on tracks[track_of[b]] (track_of None: T == B, instance b on track b).  left / right [B,N] are the
+        distances from each instance's OWN centre line.  A guess that is not given is the instance's track's own, which
+        only a DoubleTrackProblem has.  This problem supplies the model (unless models=) and the defaults of the scales."""
         left = np.ascontiguousarray(left, dtype=np.float64); right = np.ascontiguousarray(right, dtype=np.float64)
         B = left.shape[0]
+        if tracks is None and track_of is not None:
+            raise ValueError("track_of goes with tracks=")
+        if tracks is not None:
+            return self._solve_tracks(tracks, track_of, left, right, X0, U0, T0, max_iter, tol, models)
         rep = lambda a: np.repeat(np.asarray(a)[None], B, axis=0)  # noqa: E731
         X0 = rep(self.X0) if X0 is None else X0
         U0 = rep(self.U0) if U0 is None else U0
@@ -158,6 +168,37 @@ class DoubleTrackProblem:
                                        X0, U0, T0, self.average_track_width, self.speed_cap,
                                        max_iter=int(max_iter or self.params.get("max_iter", 200)),
                                        tol=float(tol if tol is not None else 1e-6))
+
+
+    def _solve_tracks(self, tracks, track_of, left, right, X0, U0, T0, max_iter, tol, models):
+        B, nt = left.shape[0], len(tracks)
+        get = lambda tr, key, alt=None: getattr(tr, key) if isinstance(tr, DoubleTrackProblem) else tr.get(key, alt)  # noqa: E731
+        s = [np.asarray(get(tr, "s"), dtype=np.float64) for tr in tracks]
+        counts = [len(a) for a in s]
+        if len(set(counts)) != 1:
+            raise ValueError(f"tracks: node counts differ: {counts}")
+        length = [get(tr, "track_length", None if isinstance(tr, DoubleTrackProblem) else tr.get("L")) for tr in tracks]
+        if any(v is None for v in length):
+            raise ValueError(f"tracks: track {[v is None for v in length].index(True)}: no \"track_length\" (or \"L\")")
+        atw = [get(tr, "average_track_width", self.average_track_width) for tr in tracks]
+        cap = [get(tr, "speed_cap", self.speed_cap) for tr in tracks]
+        track_of, length, atw, cap = ops.mintime_track_arrays(B, nt, track_of, length, atw, cap)
+        of = np.arange(B) if track_of is None else track_of
+        guess = []
+        for name, given in (("X0", X0), ("U0", U0), ("T0", T0)):
+            if given is None:
+                if not all(isinstance(tracks[t], DoubleTrackProblem) for t in of):
+                    raise ValueError(f"{name}: a track given as a dict has no initial guess of its own, pass {name}")
+                given = np.stack([getattr(tracks[t], name) for t in of])
+            guess.append(given)
+        if models is None:
+            table, margin = self.model, self.margin
+        else:
+            table, left, right, margin = _solver_margin(models, B, left, right, self.margin)
+        return ops.mintime_solve_tracks(table, track_of, np.stack(s), np.stack([np.asarray(get(tr, "kappa"), dtype=np.float64) for tr in tracks]),
+                                        np.ascontiguousarray(left), np.ascontiguousarray(right), margin, length, *guess, atw, cap,
+                                        max_iter=int(max_iter or self.params.get("max_iter", 200)),
+                                        tol=float(tol if tol is not None else 1e-6))
 
 
 class OptiVariable:
@@ -517,3 +558,99 @@ def optimise_track_batch(race_track, vehicle, model, left=None, right=None, aver
     if start_status is not None:
         out["start_status"] = start_status
     return out
+
+
+def optimise_tracks_batch(race_tracks, vehicle, model, models=None, vehicles=None, track_of=None, average_track_width=7.0,
+                          speed_cap=30.0, max_iter=200, tol=1e-6, device=None, tracks=None, start_points=None):
+    """optimise_track_batch for T race tracks of EQUAL node count in one chain on torch's current stream: per track the QSS
+    warm start and the initial guess, then ONE solve for all instances (ops.mintime_solve_tracks_torch), then per track the
+    tables of its instances (ops.pose_tables_batch_*, on the track's contiguous slice) and the summary of all.
+    Instances are ordered TRACK-MAJOR.  models / vehicles None: one instance per track with `model` / `vehicle`.  models: V
+    model dicts -> T x V instances, instance t V + v = vehicle v on track t (vehicles: V QSS vehicles for the warm starts, as
+    in optimise_track_batch).  track_of: None, or B non-decreasing track indices, with models (and vehicles) of length B:
+    instance b = models[b] on race_tracks[track_of[b]], every track at least once.  The distances are each track's own;
+    vehicles of different vehicle_width / safety_margin get their margins folded in (fold_margins).  average_track_width,
+    speed_cap: one value, or T of them.  tracks: None, or the T _lib.Tracks of an earlier call's result.
+    Returns the dict of optimise_track_batch with "track_of" (int32 [B], numpy) and "tracks" (list of T) in place of "track"."""
+    import torch
+    from .. import _lib, batch
+    from ..models.trajectory import _ring_coords
+    if start_points is not None:
+        raise ValueError("start_points with several tracks: the guess from lines takes one centre-line table, not one per track")
+    if vehicles is not None and models is None:
+        raise ValueError("vehicles: one QSS vehicle per instance goes with models=, one NLP model per instance")
+    nt = len(race_tracks)
+    if nt == 0:
+        raise ValueError("race_tracks: at least one track")
+    counts = [len(rt.center_d) for rt in race_tracks]
+    if len(set(counts)) != 1:
+        raise ValueError(f"race_tracks: node counts differ: {counts} (models.race_track.race_track_with_nodes builds a track with a given count)")
+    N = counts[0]
+    if models is not None:
+        ops.dt_models_table(models)   # a bad row is refused before anything is set up
+    if track_of is None:
+        nv = 1 if models is None else len(models)
+        track_of = np.repeat(np.arange(nt, dtype=np.int32), nv)
+        inst_models = None if models is None else [models[b % nv] for b in range(nt * nv)]
+        inst_vehicles = None if vehicles is None else [vehicles[b % nv] for b in range(nt * nv)]
+        if vehicles is not None and len(vehicles) != nv:
+            raise ValueError(f"vehicles: {len(vehicles)} QSS vehicles for {nv} models")
+    else:
+        if models is None:
+            raise ValueError("track_of: goes with models=, one per instance")
+        track_of = np.asarray(track_of)
+        if track_of.shape != (len(models),) or (vehicles is not None and len(vehicles) != len(models)):
+            raise ValueError(f"track_of: {track_of.shape} for {len(models)} models")
+        if np.any(np.diff(track_of) < 0) or sorted(set(track_of.tolist())) != list(range(nt)):
+            raise ValueError("track_of: track-major order, non-decreasing, every track at least once")
+        track_of = track_of.astype(np.int32)
+        inst_models, inst_vehicles = models, vehicles
+    B = len(track_of)
+    lengths = [float(rt.center_s.get_length()) for rt in race_tracks]
+    track_of, lengths, atw, cap = ops.mintime_track_arrays(B, nt, track_of, lengths, average_track_width, speed_cap)
+    dev = torch.device("cuda", _lib.Context.get(device).device)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)  # noqa: E731
+    slices = [slice(int(np.searchsorted(track_of, t, "left")), int(np.searchsorted(track_of, t, "right"))) for t in range(nt)]
+    s_h = [np.ascontiguousarray(rt.abscissa, dtype=np.float64) for rt in race_tracks]
+    s_d = up(np.stack(s_h))
+    kappa_d = up(np.stack([rt.curvature_intp(s) for rt, s in zip(race_tracks, s_h)]))
+    left_d = up(np.stack([np.asarray(race_tracks[t].left_intp(s_h[t])) for t in track_of]))
+    right_d = up(np.stack([np.asarray(race_tracks[t].right_intp(s_h[t])) for t in track_of]))
+    if inst_models is None:
+        table, left_s, right_s, margin = dict(model), left_d, right_d, model["vehicle_width"] / 2.0 + model["safety_margin"]
+    else:
+        table, left_s, right_s, margin = _solver_margin(inst_models, B, left_d, right_d, None)
+        left_s, right_s = left_s.contiguous(), right_s.contiguous()
+    X = torch.empty((B, N, 6), dtype=torch.float64, device=dev)
+    U = torch.empty((B, N, 4), dtype=torch.float64, device=dev)
+    T = torch.empty((B, N), dtype=torch.float64, device=dev)
+    bases, pieces = [], []
+    for t, rt in enumerate(race_tracks):
+        sl = slices[t]
+        nb = sl.stop - sl.start
+        traj_d = rt.center_d.copy()
+        rt.fill_trajectory_boundaries(traj_d)
+        if inst_vehicles is None:
+            base = up(traj_d.points)[None].contiguous()
+            ops.qss_sim_torch(base, *batch.vehicle_tables(vehicle))
+            base = base[0]
+        else:
+            base = up(traj_d.points)[None].repeat(nb, 1, 1).contiguous()
+            ops.qss_sim_vehicles_torch(base, *batch._vehicles_stacked(inst_vehicles[sl], nb, dev))
+        X[sl], U[sl], T[sl] = batch.min_time_centerline_guess_torch(s_d[t], base, nb)
+        bases.append(base)
+        pieces.append(tuple(up(a) for a in rt.centerline_pieces()))
+    stats = ops.mintime_solve_tracks_torch(table, track_of, s_d, kappa_d, left_s, right_s, margin, lengths, X, U, T, atw, cap,
+                                           max_iter=int(max_iter), tol=float(tol))
+    if tracks is None:
+        tracks = [batch.make_track(rt.center_s, N, device=dev.index) for rt in race_tracks]
+    elif len(tracks) != nt or any(trk.N != N for trk in tracks):
+        raise ValueError(f"tracks: expected {nt} tracks of {N} samples")
+    points = torch.empty((B, N, 19), dtype=torch.float64, device=dev)
+    for t, rt in enumerate(race_tracks):
+        sl = slices[t]
+        tracks[t].set_rings(_ring_coords(rt.left_r), _ring_coords(rt.right_r))
+        points[sl] = batch.min_time_tables_torch(rt, tracks[t], X[sl], T[sl], _lib.BOUNDS_SHARED_RINGS, None, base=bases[t],
+                                                 pieces=pieces[t])
+    summary = ops.table_summary_torch(points)
+    return {"points": points, "X": X, "U": U, "T": T, "stats": stats, "summary": summary, "tracks": tracks, "track_of": track_of}

@@ -132,3 +132,27 @@ class RaceTrack:
     def fill_trajectory_boundaries(self, traj: Trajectory):
         """Fills the boundary properties of a trajectory in place (race_track.py:98-104)."""
         traj.fill_bounds(self.left_r, self.right_r, max_dist=100.0)
+
+
+def interval_for_nodes(length, n):
+    """An interval for which sample_along gives exactly n nodes on a line of this length, int(length // interval) == n: the
+    middle of the admissible range (length / (n + 1), length / n], moved on if the floor still lands one off."""
+    if not (n >= 1 and np.isfinite(length) and length > 0.0):
+        raise ValueError(f"interval_for_nodes: {n} nodes on a line of {length} m")
+    interval = length / (n + 0.5)
+    for _ in range(8):
+        got = int(length // interval)
+        if got == n:
+            return interval
+        interval *= (got + 0.5) / (n + 0.5)
+    raise ValueError(f"interval_for_nodes: no interval gives {n} nodes on {length} m")
+
+
+def race_track_with_nodes(name, left, right, centerline, n, s=10.0):
+    """A RaceTrack whose centre line has exactly n nodes -- what min_time_optimizer.optimise_tracks_batch needs of the tracks
+    of one call: the interval is chosen from the fitted centre line's length, the count is checked."""
+    length = BSplineTrajectory(np.asarray(centerline)[:, :2], s, 3).get_length()
+    rt = RaceTrack(name, left, right, centerline, s=s, interval=interval_for_nodes(length, n))
+    if len(rt.center_d) != n:
+        raise ValueError(f"race_track_with_nodes: {len(rt.center_d)} nodes instead of {n}")
+    return rt

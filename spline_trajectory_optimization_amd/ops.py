@@ -1005,6 +1005,99 @@ def mintime_solve_vehicles_torch(models, s, kappa, left, right, margin, track_le
                           speed_cap, max_iter, tol, None)
 
 
+def _dt_models(models, B):
+    """(host table, models_per_instance) of a `models` argument: one dict (or one row [28]) for all, or B of them."""
+    if isinstance(models, dict) or (not isinstance(models, (list, tuple)) and np.ndim(models) == 1):
+        return dt_models_table([models]), 0
+    return dt_models_table(models, B), 1
+
+
+def mintime_track_arrays(B, T, track_of, track_length, average_track_width, speed_cap):
+    """The per-track HOST arguments of rl_mintime_solve_tracks*, checked as the library checks them, before anything
+    reaches it -> (track_of int32 [B] | None, track_length [T], average_track_width [T], speed_cap [T]).  A scalar
+    average_track_width / speed_cap is repeated T times.  A ValueError names the first bad instance or track."""
+    if T < 1:
+        raise ValueError(f"tracks: T = {T}, at least one track is needed")
+    per_track = []
+    for name, v in (("track_length", track_length), ("average_track_width", average_track_width), ("speed_cap", speed_cap)):
+        a = np.array(v, dtype=np.float64)
+        a = np.full(T, float(a)) if a.ndim == 0 and name != "track_length" else np.ascontiguousarray(a)
+        if a.shape != (T,):
+            raise ValueError(f"{name}: expected [T] = [{T}], got shape {a.shape}")
+        for t, x in enumerate(a):
+            if not (np.isfinite(x) and x > 0.0):
+                raise ValueError(f"tracks: track {t}: {name} must be finite and > 0, got {x}")
+        per_track.append(a)
+    if track_of is None:
+        if T != B:
+            raise ValueError(f"track_of: None is the identity and needs T == B, got T = {T}, B = {B}")
+    else:
+        given = np.asarray(track_of)
+        if given.shape != (B,) or not np.issubdtype(given.dtype, np.integer):
+            raise ValueError(f"track_of: expected B = {B} integers, got shape {given.shape}, dtype {given.dtype}")
+        bad = np.flatnonzero((given < 0) | (given >= T))
+        if len(bad):
+            raise ValueError(f"track_of: instance {int(bad[0])}: track {int(given[bad[0]])} outside [0, {T})")
+        track_of = np.ascontiguousarray(given, dtype=np.int32)
+    return (track_of, *per_track)
+
+
+def _mintime_solve_tracks(A, models, track_of, s, kappa, left, right, margin, track_length, X, U, T, average_track_width,
+                          speed_cap, max_iter, tol, device):
+    """The min-time solve with one centre line per instance in A's memory space, X / U / T in place -> stats [B,12].
+    Everything that can be refused is refused here, as a ValueError, before any device call."""
+    if len(T.shape) != 2:
+        raise ValueError(f"T: expected [B,N], got {tuple(T.shape)}")
+    B, N = T.shape
+    if len(s.shape) != 2 or s.shape[1] != N:
+        raise ValueError(f"s: expected [T,N] with N = {N}, got {tuple(s.shape)}")
+    nt = int(s.shape[0])
+    tab, mper = _dt_models(models, B)
+    track_of, L, atw, cap = mintime_track_arrays(B, nt, track_of, track_length, average_track_width, speed_cap)
+    A.check(s, "s", (nt, N)); A.check(kappa, "kappa", (nt, N))
+    A.check(left, "left", (B, N)); A.check(right, "right", (B, N))
+    A.check(X, "X", (B, N, 6)); A.check(U, "U", (B, N, 4)); A.check(T, "T", (B, N))
+    A.same_device(X, "X", (("U", U), ("T", T), ("s", s), ("kappa", kappa), ("left", left), ("right", right)))
+    if A is _Host:   # what only the host entry can look at
+        for t in range(nt):
+            if not np.all(np.isfinite(kappa[t])):
+                raise ValueError(f"tracks: track {t}: kappa is not finite at node {int(np.flatnonzero(~np.isfinite(kappa[t]))[0])}")
+            ok = (s[t] >= 0.0) & (s[t] < L[t])
+            ok[1:] &= np.diff(s[t]) > 0.0
+            if not ok.all():
+                raise ValueError(f"tracks: track {t}: s must increase strictly within [0, track_length) "
+                                 f"(node {int(np.flatnonzero(~ok)[0])})")
+    ctx = A.bind(None, X, device)
+    stats = A.new(X, (B, 12), zero=True)
+    check(A.entry(ctx, "rl_mintime_solve_tracks", "rl_mintime_solve_tracks_dev")(
+        ctx.h, _Host.ptr(tab), int(mper), B, N, nt, _Host.iptr(track_of), A.ptr(s), A.ptr(kappa), A.ptr(left), A.ptr(right),
+        float(margin), _Host.ptr(L), _Host.ptr(atw), _Host.ptr(cap), A.ptr(X), A.ptr(U), A.ptr(T), int(max_iter), float(tol),
+        A.ptr(stats)))
+    return stats
+
+
+def mintime_solve_tracks(models, track_of, s, kappa, left, right, margin, track_length, X0, U0, T0, average_track_width=7.0,
+                         speed_cap=30.0, max_iter=120, tol=1e-6, device=None):
+    """mintime_solve_vehicles with ONE CENTRE LINE PER INSTANCE as well (include/rl_mincurv.h: rl_mintime_solve_tracks):
+    s, kappa [T,N] are T tracks of equal node count, track_length [T], average_track_width / speed_cap [T] or one scalar
+    for all; instance b runs on track track_of[b] (B ints; None = the identity, T == B).  models: one model dict, or B
+    of them (or an array [B, len(DT_PARAMS)]).  left / right [B,N], margin one scalar.  X0 [B,N,6], U0 [B,N,4], T0 [B,N].
+    Every instance gets the bits of its own single call.  Returns (X, U, T, stats [B,12])."""
+    X, U, T = _copy_guess(X0, U0, T0)
+    stats = _mintime_solve_tracks(_Host, models, track_of, _f64(s), _f64(kappa), _f64(left), _f64(right), margin, track_length,
+                                  X, U, T, average_track_width, speed_cap, max_iter, tol, device)
+    return X, U, T, stats
+
+
+def mintime_solve_tracks_torch(models, track_of, s, kappa, left, right, margin, track_length, X, U, T,
+                               average_track_width=7.0, speed_cap=30.0, max_iter=120, tol=1e-6):
+    """rl_mintime_solve_tracks_dev on DEVICE tensors (float64, cuda, contiguous), shapes as mintime_solve_tracks; X, U, T
+    are updated in place.  models, track_of, track_length, average_track_width and speed_cap are HOST arguments, read
+    before the call returns.  Enqueues on torch's current stream, no sync.  Returns the stats tensor [B,12]."""
+    return _mintime_solve_tracks(_Torch, models, track_of, s, kappa, left, right, margin, track_length, X, U, T,
+                                 average_track_width, speed_cap, max_iter, tol, None)
+
+
 BK_PARAMS = ("lr", "L", "delta_max", "v_max", "a_lon_max", "a_lon_min", "delta_dot_max", "acc_max")   # rl_bk_param order
 
 

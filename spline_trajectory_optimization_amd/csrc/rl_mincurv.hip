@@ -1722,89 +1722,79 @@ int rl_dt_eval_jac(rl_ctx* ctx, const double* model, int B, int N, const double*
 }
 
 // ---- the min-time double-track NLP (rl_mintime.hpp)
+// One text of the driver for the three problem types (rl_mintime.hpp: <MtProblem> shared model, <MtProblemV> one vehicle, <MtProblemT>
+// one centre line per instance as well): the bit-equality of the forms rests on the launch sequences being the same.
 namespace {
-// A sub-batch: its stream, its views of the problem, the state and the caller's arrays, the grids most kernels share (y: the instance).
-// veh: one vehicle per instance -- V carries the group's slice of the vehicle table and the kernels that read the model are
-// launched as their <MtProblemV> instance (rl_mintime.hpp); P.p / sw / se are then NaN, so that a kernel that read the model
-// from its arguments in such a call could not go unnoticed.
-// trk (rl_mintime_solve_tracks*): one centre line per instance as well -- K carries the slice of the table and the tables s /
-// kappa [T,N], the kernels are launched as their <MtProblemT> instance.
-struct MtGroup { hipStream_t q; rl::MtProblem P; rl::MtProblemV V; rl::MtProblemT K; bool veh, trk; rl::MtState st; double *X, *U, *T, *stats; dim3 rows, per_node, per_inst; };
-using MtKernel = void (*)(rl::MtProblem, rl::MtState);
-using MtKernelV = void (*)(rl::MtProblemV, rl::MtState);
-using MtKernelT = void (*)(rl::MtProblemT, rl::MtState);
-struct MtKernels { MtKernel shared; MtKernelV vehicles; MtKernelT tracks; };   // the three forms of a kernel that reads the model or the track
-#define MT_K(name) MtKernels{rl::name<rl::MtProblem>, rl::name<rl::MtProblemV>, rl::name<rl::MtProblemT>}
-#define MT_KT(name, arg) MtKernels{rl::name<arg, rl::MtProblem>, rl::name<arg, rl::MtProblemV>, rl::name<arg, rl::MtProblemT>}
-int mt_run(const rl_ctx* ctx, const MtGroup& G, MtKernel kernel, dim3 grid, int threads) {   // a kernel that never reads the model
-  return launch(ctx, G.q, kernel, grid, dim3(threads), 0, G.P, G.st);
+extern "C++" {
+// A sub-batch: its stream, its two views of the problem, the state and the caller's arrays, the grids most kernels share (y: the
+// instance).  P goes to the kernels that never read the model, M to the <PT> instance of the ones that do; for PT = MtProblem the two are
+// equal.  In a table call M carries the group's slice of the table and P.p / sw / se are NaN: a kernel that read them would not go unnoticed.
+template <typename PT> struct MtGroup { hipStream_t q; rl::MtProblem P; PT M; rl::MtState st; double *X, *U, *T, *stats; dim3 rows, per_node, per_inst; };
+// M from the group's P and its slice of the table (row0: the row of the group's first instance), as of left / right
+inline void mt_set_model(rl::MtProblem& M, const rl::MtProblem& P, const double*) { M = P; }
+template <typename PT> void mt_set_model(PT& M, const rl::MtProblem& P, const double* row0) {
+  M.p = (rl::MtTab)row0; M.sw = (rl::MtTab)(row0 + rl::kMtRowSw); M.se = (rl::MtTab)(row0 + rl::kMtRowSe);
+  M.N = P.N; M.s = P.s; M.kappa = P.kappa; M.left = P.left; M.right = P.right;
+  M.bounds_per_instance = P.bounds_per_instance; M.margin = P.margin; M.track_length = P.track_length;
 }
-int mt_run_model(const rl_ctx* ctx, const MtGroup& G, MtKernels k, dim3 grid, int threads) {
-  if (G.trk) return launch(ctx, G.q, k.tracks, grid, dim3(threads), 0, G.K, G.st);
-  return G.veh ? launch(ctx, G.q, k.vehicles, grid, dim3(threads), 0, G.V, G.st)
-               : launch(ctx, G.q, k.shared, grid, dim3(threads), 0, G.P, G.st);
-}
-int mt_pack(const rl_ctx* ctx, const MtGroup& G) {
-  if (G.trk) return launch(ctx, G.q, rl::k_mt_pack<rl::MtProblemT>, G.rows, dim3(64), 0, G.K, G.st, G.X, G.U, G.T);
-  return G.veh ? launch(ctx, G.q, rl::k_mt_pack<rl::MtProblemV>, G.rows, dim3(64), 0, G.V, G.st, G.X, G.U, G.T)
-               : launch(ctx, G.q, rl::k_mt_pack<rl::MtProblem>, G.rows, dim3(64), 0, G.P, G.st, G.X, G.U, G.T);
-}
-int mt_unpack(const rl_ctx* ctx, const MtGroup& G) {
-  if (G.trk) return launch(ctx, G.q, rl::k_mt_unpack<rl::MtProblemT>, G.rows, dim3(64), 0, G.K, G.st, G.X, G.U, G.T);
-  return G.veh ? launch(ctx, G.q, rl::k_mt_unpack<rl::MtProblemV>, G.rows, dim3(64), 0, G.V, G.st, G.X, G.U, G.T)
-               : launch(ctx, G.q, rl::k_mt_unpack<rl::MtProblem>, G.rows, dim3(64), 0, G.P, G.st, G.X, G.U, G.T);
-}
+
+// a launch on the group's stream: of a kernel that never reads the model, of one that does, of the two that also take the caller's arrays
+template <typename PT> int mt_run(const rl_ctx* ctx, const MtGroup<PT>& G, void (*kernel)(rl::MtProblem, rl::MtState), dim3 grid, int threads) { return launch(ctx, G.q, kernel, grid, dim3(threads), 0, G.P, G.st); }
+template <typename PT> int mt_run_model(const rl_ctx* ctx, const MtGroup<PT>& G, void (*kernel)(PT, rl::MtState), dim3 grid, int threads) { return launch(ctx, G.q, kernel, grid, dim3(threads), 0, G.M, G.st); }
+template <typename PT> int mt_pack(const rl_ctx* ctx, const MtGroup<PT>& G) { return launch(ctx, G.q, rl::k_mt_pack<PT>, G.rows, dim3(64), 0, G.M, G.st, G.X, G.U, G.T); }
+template <typename PT> int mt_unpack(const rl_ctx* ctx, const MtGroup<PT>& G) { return launch(ctx, G.q, rl::k_mt_unpack<PT>, G.rows, dim3(64), 0, G.M, G.st, G.X, G.U, G.T); }
 
 // One iteration of one group on its stream; finished instances return at once from every kernel.  Three pipelines: the
 // default (k_mt_node), and the cross-checks RL_MT_HES_SWEEP=1 / RL_MT_UNFUSED=1 with the separate assembly kernels.
-int mt_enqueue_iteration(const rl_ctx* ctx, const MtGroup& G) {
+template <typename PT> int mt_enqueue_iteration(const rl_ctx* ctx, const MtGroup<PT>& G) {
   const int N = G.P.N, nb = G.st.B;
   if (ctx->mt_hes_sweep) {   // cross-check: forward (over forward) duals through the whole pair function
-    RL_TRY(mt_run_model(ctx, G, MT_KT(k_mt_derivs, 0), G.rows, 64));
-    RL_TRY(mt_run_model(ctx, G, MT_KT(k_mt_derivs, 1), dim3(G.rows.x, nb, rl::kMtJacSlices), 64));
-    RL_TRY(mt_run_model(ctx, G, MT_KT(k_mt_derivs, 2), dim3(G.rows.x, nb, rl::kMtHesSlices), 64));
+    RL_TRY(mt_run_model(ctx, G, rl::k_mt_derivs<0, PT>, G.rows, 64));
+    RL_TRY(mt_run_model(ctx, G, rl::k_mt_derivs<1, PT>, dim3(G.rows.x, nb, rl::kMtJacSlices), 64));
+    RL_TRY(mt_run_model(ctx, G, rl::k_mt_derivs<2, PT>, dim3(G.rows.x, nb, rl::kMtHesSlices), 64));
   } else {
-    RL_TRY(mt_run_model(ctx, G, MT_K(k_mt_values), G.rows, 64));   // functions; values of the dynamics at the two ends -> midpoint
-    RL_TRY(mt_run_model(ctx, G, MT_K(k_mt_jac_dirs), dim3(rl::mt_jac_blocks(N), nb, 3), 64));
-    if (ctx->mt_unfused) RL_TRY(mt_run_model(ctx, G, MT_K(k_mt_jac_assemble), G.per_node, 64));
-    RL_TRY(mt_run_model(ctx, G, MT_KT(k_mt_hes_point, 0), dim3(rl::mt_hes_blocks(N), nb, 1), 64));
-    RL_TRY(mt_run_model(ctx, G, MT_KT(k_mt_hes_point, 1), dim3(rl::mt_hes_blocks(N), nb, 2), 64));
+    RL_TRY(mt_run_model(ctx, G, rl::k_mt_values<PT>, G.rows, 64));   // functions; values of the dynamics at the two ends -> midpoint
+    RL_TRY(mt_run_model(ctx, G, rl::k_mt_jac_dirs<PT>, dim3(rl::mt_jac_blocks(N), nb, 3), 64));
+    if (ctx->mt_unfused) RL_TRY(mt_run_model(ctx, G, rl::k_mt_jac_assemble<PT>, G.per_node, 64));
+    RL_TRY(mt_run_model(ctx, G, rl::k_mt_hes_point<0, PT>, dim3(rl::mt_hes_blocks(N), nb, 1), 64));
+    RL_TRY(mt_run_model(ctx, G, rl::k_mt_hes_point<1, PT>, dim3(rl::mt_hes_blocks(N), nb, 2), 64));
     if (ctx->mt_unfused) {
-      RL_TRY(mt_run_model(ctx, G, MT_K(k_mt_hes_assemble), G.per_node, 64));
+      RL_TRY(mt_run_model(ctx, G, rl::k_mt_hes_assemble<PT>, G.per_node, 64));
     } else {   // Jacobian, Hessian, blocks and right-hand side in one pass over the pairs
-      RL_TRY(mt_run_model(ctx, G, MT_K(k_mt_node), dim3(rl::mt_node_blocks(N), nb), 64));
-      RL_TRY(mt_run_model(ctx, G, MT_K(k_mt_prepare2), G.per_inst, 256));
+      RL_TRY(mt_run_model(ctx, G, rl::k_mt_node<PT>, dim3(rl::mt_node_blocks(N), nb), 64));
+      RL_TRY(mt_run_model(ctx, G, rl::k_mt_prepare2<PT>, G.per_inst, 256));
     }
   }
   if (ctx->mt_hes_sweep || ctx->mt_unfused) {
-    RL_TRY(mt_run_model(ctx, G, MT_K(k_mt_prepare), G.per_inst, 64));
+    RL_TRY(mt_run_model(ctx, G, rl::k_mt_prepare<PT>, G.per_inst, 64));
     RL_TRY(mt_run(ctx, G, rl::k_mt_assemble, G.per_node, 64));
     RL_TRY(mt_run(ctx, G, rl::k_mt_gc_pack, G.per_node, 64));
   }
   if (ctx->mt_kkt4 && N >= 64) RL_TRY(mt_run(ctx, G, rl::k_mt_kkt4, G.per_inst, 256));
   else RL_TRY(mt_run(ctx, G, rl::k_mt_kkt, G.per_inst, 128));
   RL_TRY(mt_run(ctx, G, rl::k_mt_dir, dim3(rl::kMtDirBlocks(N), nb), 64));
-  RL_TRY(mt_run_model(ctx, G, MT_K(k_mt_trial), G.rows, 64));
+  RL_TRY(mt_run_model(ctx, G, rl::k_mt_trial<PT>, G.rows, 64));
   RL_TRY(mt_run(ctx, G, rl::k_mt_step, G.per_inst, 256));
-  RL_TRY(mt_run_model(ctx, G, MT_K(k_mt_trial_b), G.rows, 64));        // halvings of the instances whose first trial point was rejected
-  return mt_run_model(ctx, G, MT_K(k_mt_step_b), G.per_inst, 256);
+  RL_TRY(mt_run_model(ctx, G, rl::k_mt_trial_b<PT>, G.rows, 64));        // halvings of the instances whose first trial point was rejected
+  return mt_run_model(ctx, G, rl::k_mt_step_b<PT>, G.per_inst, 256);
 }
 
 // the closing pass of one group: final residuals of the instances still running (status 0 = iteration limit), the caller's arrays, the report
-int mt_enqueue_closing(const rl_ctx* ctx, const MtGroup& G) {
+template <typename PT> int mt_enqueue_closing(const rl_ctx* ctx, const MtGroup<PT>& G) {
   const int N = G.P.N, nb = G.st.B;
-  RL_TRY(mt_run_model(ctx, G, MT_KT(k_mt_derivs, 0), G.rows, 64));
+  RL_TRY(mt_run_model(ctx, G, rl::k_mt_derivs<0, PT>, G.rows, 64));
   if (ctx->mt_hes_sweep) {
-    RL_TRY(mt_run_model(ctx, G, MT_KT(k_mt_derivs, 1), dim3(G.rows.x, nb, rl::kMtJacSlices), 64));
+    RL_TRY(mt_run_model(ctx, G, rl::k_mt_derivs<1, PT>, dim3(G.rows.x, nb, rl::kMtJacSlices), 64));
   } else {
-    RL_TRY(mt_run_model(ctx, G, MT_K(k_mt_hes_values), G.rows, 64));
-    RL_TRY(mt_run_model(ctx, G, MT_K(k_mt_jac_dirs), dim3(rl::mt_jac_blocks(N), nb, 3), 64));
-    RL_TRY(mt_run_model(ctx, G, MT_K(k_mt_jac_assemble), G.per_node, 64));
+    RL_TRY(mt_run_model(ctx, G, rl::k_mt_hes_values<PT>, G.rows, 64));
+    RL_TRY(mt_run_model(ctx, G, rl::k_mt_jac_dirs<PT>, dim3(rl::mt_jac_blocks(N), nb, 3), 64));
+    RL_TRY(mt_run_model(ctx, G, rl::k_mt_jac_assemble<PT>, G.per_node, 64));
   }
-  RL_TRY(mt_run_model(ctx, G, MT_K(k_mt_residuals), G.per_inst, 64));
+  RL_TRY(mt_run_model(ctx, G, rl::k_mt_residuals<PT>, G.per_inst, 64));
   RL_TRY(mt_unpack(ctx, G));
   return launch(ctx, G.q, rl::k_mt_stats, dim3((nb + 63) / 64), dim3(64), 0, G.st, G.stats);
 }
+}  // extern "C++"
 
 // min_time_optimizer.py:109-113: scale_x = (1, average_track_width, 1, 1, 0.5, speed_cap),
 // scale_u = (Fd_max, |Fb_max|, delta_max, 50 mass), scale_t = 1  ->  sw [9], se [7] of one model (MtProblem).  The one
@@ -1835,11 +1825,26 @@ int mt_check_models(const double* models, int B) {
 }
 
 // What a tracks call (rl_mintime_solve_tracks*) has per track or per instance, all HOST arrays: checked by mt_check_tracks.
-struct MtTracks { int T; const int* track_of; const double *track_length, *average_track_width, *speed_cap; int models_per_instance; };
-int mt_check_tracks(const MtTracks& tr, const double* models, int B) {
+struct MtTracks { int T; const int* track_of; const double *track_length, *average_track_width, *speed_cap; };
+
+// One call of any of the six entries, as its entry filled it: mt_check_call refuses what is wrong with it, the driver reads it.
+// The form of the solve follows from it: a tracks call and a call with B model rows take the model from a table (mt_build_rows).
+struct MtCall {
+  const double* model; bool model_rows;   // HOST: one row [RL_DT_NPARAM] for all instances, or B rows
+  int B, N; const double *s, *kappa, *left, *right; int bounds_per_instance; double margin;
+  double *X, *U, *T, *stats; int max_iter; double tol;
+  // one centre line for all instances: its three scalars -- or a tracks call: s, kappa are [T,N] and the scalars stay NaN
+  static constexpr double kNaN = std::numeric_limits<double>::quiet_NaN();
+  double track_length = kNaN, average_track_width = kNaN, speed_cap = kNaN;
+  const MtTracks* tr = nullptr;
+  bool poll = false;   // stop enqueueing once every instance has finished (the host entries, which synchronise anyway)
+  bool table() const { return tr || model_rows; }
+};
+
+int mt_check_tracks(const MtTracks& tr, const double* models, bool model_rows, int B) {
   if (tr.T <= 0 || !tr.track_length || !tr.average_track_width || !tr.speed_cap) return fail(RL_ERR_ARG, "tracks: T >= 1 and the three arrays [T]");
   if (!tr.track_of && tr.T != B) return fail(RL_ERR_ARG, "track_of: NULL is the identity and needs T == B");
-  RL_TRY(mt_check_models(models, tr.models_per_instance ? B : 1));
+  RL_TRY(mt_check_models(models, model_rows ? B : 1));
   for (int b = 0; tr.track_of && b < B; ++b)
     if (tr.track_of[b] < 0 || tr.track_of[b] >= tr.T)
       return fail(RL_ERR_ARG, "track_of: instance " + std::to_string(b) + ": track " + std::to_string(tr.track_of[b]) + " outside [0, " + std::to_string(tr.T) + ")");
@@ -1853,10 +1858,11 @@ int mt_check_tracks(const MtTracks& tr, const double* models, int B) {
 }
 
 // The table of a vehicles or a tracks call: row b = p | sw | se of instance b, and in a tracks call the length and the index
-// of its track (rl_mintime.hpp: kMtRowLen, kMtRowTrack).  `rows` [B, kMtRow] arrives zeroed; the arguments are checked.
-void mt_build_rows(double* rows, const double* models, int B, const MtTracks* tr, double average_track_width, double speed_cap) {
-  for (int b = 0; b < B; ++b) {
-    const double* m = models + (tr && !tr->models_per_instance ? 0 : (size_t)b * RL_DT_NPARAM);
+// of its track (rl_mintime.hpp: kMtRowLen, kMtRowTrack).  `rows` [B, kMtRow] arrives zeroed; the call is checked.
+void mt_build_rows(double* rows, const MtCall& c) {
+  const MtTracks* tr = c.tr;
+  for (int b = 0; b < c.B; ++b) {
+    const double* m = c.model + (c.model_rows ? (size_t)b * RL_DT_NPARAM : 0);
     double* r = rows + (size_t)b * rl::kMtRow;
     for (int i = 0; i < rl::DT_NPARAM; ++i) r[i] = m[i];
     if (tr) {   // the instance's track: its scales, its length, its index (an int in the low word of the slot)
@@ -1865,53 +1871,56 @@ void mt_build_rows(double* rows, const double* models, int B, const MtTracks* tr
       r[rl::kMtRowLen] = tr->track_length[t];
       std::memcpy(r + rl::kMtRowTrack, &t, sizeof(int));
     } else {
-      mt_scales(m, average_track_width, speed_cap, r + rl::kMtRowSw, r + rl::kMtRowSe);
+      mt_scales(m, c.average_track_width, c.speed_cap, r + rl::kMtRowSw, r + rl::kMtRowSe);
     }
   }
 }
 
-// Both entry points of the solve, on device pointers.  poll: stop enqueueing once every instance has finished (the host
-// entry point, which synchronises anyway); without it all max_iter iterations are enqueued and the call does not wait.
-// vehicles: `model` is [B, RL_DT_NPARAM], one row per instance (rl_mintime_solve_vehicles*).
-// tr: a tracks call (rl_mintime_solve_tracks*) -- s, kappa are [T,N], `model` is [B or 1, RL_DT_NPARAM], the scalars
-// track_length / average_track_width / speed_cap are not read; `vehicles` is then true (the table is built either way).
-int mintime_solve_common(rl_ctx* ctx, const double* model, bool vehicles, int B, int N, const double* s, const double* kappa, const double* left,
-                         const double* right, int bounds_per_instance, double margin, double track_length, double average_track_width,
-                         double speed_cap, double* X, double* U, double* T, int max_iter, double tol, double* stats, bool poll,
-                         const MtTracks* tr = nullptr) {
-  if (!ctx || !model || !s || !kappa || !left || !right || !X || !U || !T || !stats) return fail(RL_ERR_ARG, "null argument");
-  if (B <= 0 || N < 8 || !(tr || track_length > 0.0) || max_iter < 1 || !(tol > 0.0)) return fail(RL_ERR_ARG, "bad sizes (N >= 8 nodes)");
-  if (!tr && (!(average_track_width > 0.0) || !(speed_cap > 0.0))) return fail(RL_ERR_ARG, "bad scales");
-  if (tr) RL_TRY(mt_check_tracks(*tr, model, B));
-  else if (vehicles) RL_TRY(mt_check_models(model, B));
-  RL_HIP(hipSetDevice(ctx->device));
-  rl::MtProblem P;
-  P.N = N; P.bounds_per_instance = bounds_per_instance ? 1 : 0;
-  P.margin = margin; P.track_length = tr ? std::numeric_limits<double>::quiet_NaN() : track_length;
-  P.s = s; P.kappa = kappa; P.left = left; P.right = right;
-  std::vector<double> rows;   // vehicles: the table p | sw | se, kMtRow doubles per instance
-  if (vehicles) {
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    for (double& v : P.p) v = nan;
-    for (double& v : P.sw) v = nan;
-    for (double& v : P.se) v = nan;
-    rows.assign((size_t)B * rl::kMtRow, 0.0);
-    mt_build_rows(rows.data(), model, B, tr, average_track_width, speed_cap);
-  } else {
-    for (int i = 0; i < rl::DT_NPARAM; ++i) P.p[i] = model[i];
-    mt_scales(model, average_track_width, speed_cap, P.sw, P.se);
+// The one check of a call, before anything is staged or enqueued.  mt_check_table: the rows a table is built from, also what
+// rl_debug_mt_rows checks.  host_arrays: s, kappa, left, right can be read here, so the host entries also look at them.
+int mt_check_table(const MtCall& c) {
+  if (c.tr) return mt_check_tracks(*c.tr, c.model, c.model_rows, c.B);
+  return c.model_rows ? mt_check_models(c.model, c.B) : RL_OK;
+}
+int mt_check_call(const rl_ctx* ctx, const MtCall& c, bool host_arrays) {
+  if (!ctx || !c.model || !c.s || !c.kappa || !c.left || !c.right || !c.X || !c.U || !c.T || !c.stats) return fail(RL_ERR_ARG, "null argument");
+  if (c.B <= 0 || c.N < 8 || !(c.tr || c.track_length > 0.0) || c.max_iter < 1 || !(c.tol > 0.0)) return fail(RL_ERR_ARG, "bad sizes (N >= 8 nodes)");
+  if (!c.tr && (!(c.average_track_width > 0.0) || !(c.speed_cap > 0.0))) return fail(RL_ERR_ARG, "bad scales");
+  RL_TRY(mt_check_table(c));
+  if (!host_arrays) return RL_OK;
+  const int N = c.N;
+  for (int t = 0; c.tr && t < c.tr->T; ++t) {
+    const double *st = c.s + (size_t)t * N, *kt = c.kappa + (size_t)t * N;
+    for (int j = 0; j < N; ++j) {
+      if (!std::isfinite(kt[j])) return fail(RL_ERR_ARG, "tracks: track " + std::to_string(t) + ": kappa is not finite at node " + std::to_string(j));
+      if (!(st[j] >= 0.0 && st[j] < c.tr->track_length[t] && (j == 0 || st[j] > st[j - 1])))
+        return fail(RL_ERR_ARG, "tracks: track " + std::to_string(t) + ": s must increase strictly within [0, track_length) (node " + std::to_string(j) + ")");
+    }
   }
+  const size_t nb_ = c.bounds_per_instance ? (size_t)c.B * N : (size_t)N;
+  for (size_t i = 0; i < nb_; ++i)
+    if (!(c.right[i] + c.margin < c.left[i] - c.margin)) return fail(RL_ERR_ARG, "track narrower than the vehicle plus margins (min_time_optimizer.py:135)");
+  return RL_OK;
+}
+
+// The solve of a checked call on device pointers, for one problem type.  P: the problem as the model-blind kernels take it;
+// rows: the table [B, kMtRow] of a table call, else empty.  With c.poll the call stops enqueueing once every instance has
+// finished; without it all max_iter iterations are enqueued and the call does not wait.
+extern "C++" {
+template <typename PT> int mt_solve_as(rl_ctx* ctx, const MtCall& c, const rl::MtProblem& P, const std::vector<double>& rows) {
+  const int B = c.B, N = c.N;
+  RL_HIP(hipSetDevice(ctx->device));
   Arena ar(ctx);
   rl::MtState st;
   double* table = nullptr;
   RL_HIP(ar.carve([&](Arena& x) {
     rl::carve(x, st, rl::kMtArrays, B, N);
-    if (vehicles) table = x.take<double>(rows.size());
+    if (!rows.empty()) table = x.take<double>(rows.size());
   }));
   // a pageable copy on the context's stream (the runtime has read `rows` when it returns, as for the long tables of
   // qss_sim_enqueue); the sub-batch streams fork behind it
-  if (vehicles) RL_HIP(hipMemcpyAsync(table, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  st.tol = tol;
+  if (!rows.empty()) RL_HIP(hipMemcpyAsync(table, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  st.tol = c.tol;
   // Strategy constants of the line search / barrier update.  Measured on 1024 width-perturbed MGKT tracks:
   // (d_up, a_lo, mu_kappa) = (5, 0.3, 10) 96.5 iterations on average, (3, 0.2, 30) 77.8 (round 2).  Round 4: the damping
   // delta came down only after a step longer than a_hi = 0.9 -- but for dozens of iterations per barrier problem the
@@ -1948,7 +1957,7 @@ int mintime_solve_common(rl_ctx* ctx, const double* model, bool vehicles, int B,
   auto event = [](hipEvent_t& e) { return e ? hipSuccess : hipEventCreateWithFlags(&e, hipEventDisableTiming); };
   for (int g = 0; g + 1 < ngrp; ++g) { RL_HIP(stream(ctx->aux_stream[g])); RL_HIP(event(ctx->ev_join[g])); }
   if (ngrp > 1) RL_HIP(event(ctx->ev_fork));
-  if (poll) {   // what the poll keeps on the context: its stream, its events, the pinned buffer of two slots
+  if (c.poll) {   // what the poll keeps on the context: its stream, its events, the pinned buffer of two slots
     RL_HIP(stream(ctx->poll_stream));
     for (int g = 0; g < ngrp; ++g) RL_HIP(event(ctx->ev_chunk[g]));
     for (auto& e : ctx->ev_poll) RL_HIP(event(e));
@@ -1960,34 +1969,28 @@ int mintime_solve_common(rl_ctx* ctx, const double* model, bool vehicles, int B,
     }
   }
   StreamFork fork{ctx, ngrp};   // after `ar`: joined before the arena's event is recorded, on every exit
-  MtGroup grp[rl_ctx::kMaxGroups];
+  MtGroup<PT> grp[rl_ctx::kMaxGroups];
   for (int g = 0; g < ngrp; ++g) {
     const int b0 = (int)((long long)B * g / ngrp), nb = (int)((long long)B * (g + 1) / ngrp) - b0;
     const size_t o = (size_t)b0 * N;
-    MtGroup& G = grp[g];
+    MtGroup<PT>& G = grp[g];
     G.q = fork_stream(ctx, g); G.P = P; G.st = rl::slice(st, rl::kMtArrays, b0, nb);
-    if (P.bounds_per_instance) { G.P.left = left + o; G.P.right = right + o; }
-    G.veh = vehicles; G.trk = tr != nullptr;
-    const double* row0 = table + (vehicles ? (size_t)b0 * rl::kMtRow : 0);   // the group's slice of the table, as of left / right
-    G.V.p = (rl::MtTab)row0; G.V.sw = (rl::MtTab)(row0 + rl::kMtRowSw); G.V.se = (rl::MtTab)(row0 + rl::kMtRowSe);
-    G.V.N = N; G.V.s = s; G.V.kappa = kappa; G.V.left = G.P.left; G.V.right = G.P.right;
-    G.V.bounds_per_instance = P.bounds_per_instance; G.V.margin = margin; G.V.track_length = P.track_length;
-    G.K.p = G.V.p; G.K.sw = G.V.sw; G.K.se = G.V.se; G.K.N = N; G.K.s = s; G.K.kappa = kappa; G.K.left = G.P.left; G.K.right = G.P.right;
-    G.K.bounds_per_instance = P.bounds_per_instance; G.K.margin = margin; G.K.track_length = P.track_length;
-    G.X = X + o * 6; G.U = U + o * 4; G.T = T + o; G.stats = stats + (size_t)b0 * rl::kMtStats;
+    if (P.bounds_per_instance) { G.P.left = c.left + o; G.P.right = c.right + o; }
+    mt_set_model(G.M, G.P, table ? table + (size_t)b0 * rl::kMtRow : nullptr);
+    G.X = c.X + o * 6; G.U = c.U + o * 4; G.T = c.T + o; G.stats = c.stats + (size_t)b0 * rl::kMtStats;
     G.rows = dim3(rl::mt_row_blocks(N), nb); G.per_node = dim3(N, nb); G.per_inst = dim3(nb);
   }
   if (ngrp > 1) RL_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));   // the auxiliary streams start behind what is already enqueued
   for (int g = 1; g < ngrp; ++g) RL_HIP(hipStreamWaitEvent(grp[g].q, ctx->ev_fork, 0));
   for (int g = 0; g < ngrp; ++g) {
-    const MtGroup& G = grp[g];
+    const MtGroup<PT>& G = grp[g];
     RL_TRY(mt_pack(ctx, G));
-    RL_TRY(mt_run_model(ctx, G, MT_KT(k_mt_derivs, 0), G.rows, 64));
+    RL_TRY(mt_run_model(ctx, G, rl::k_mt_derivs<0, PT>, G.rows, 64));
     RL_TRY(launch(ctx, G.q, rl::k_mt_init, dim3(rl::mt_init_blocks(N), G.st.B), dim3(256), 0, G.P, G.st, mt_mu0, mt_delta0));
   }
-  for (int it = 0; it < max_iter; ++it) {
+  for (int it = 0; it < c.max_iter; ++it) {
     for (int g = 0; g < ngrp; ++g) RL_TRY(mt_enqueue_iteration(ctx, grp[g]));
-    if (poll && (it & 7) == 7) {   // host entry point only: stop once every instance has finished
+    if (c.poll && (it & 7) == 7) {   // host entry point only: stop once every instance has finished
       const int chunk = it >> 3, slot = chunk & 1;
       fork.polled = true;
       for (int g = 0; g < ngrp; ++g) {
@@ -2010,69 +2013,83 @@ int mintime_solve_common(rl_ctx* ctx, const double* model, bool vehicles, int B,
       }
     }
   }
-  if (poll) { fork.polled = false; RL_HIP(hipStreamSynchronize(ctx->poll_stream)); }   // no copy in flight into the pinned buffer when the call returns
+  if (c.poll) { fork.polled = false; RL_HIP(hipStreamSynchronize(ctx->poll_stream)); }   // no copy in flight into the pinned buffer when the call returns
   for (int g = 0; g < ngrp; ++g) RL_TRY(mt_enqueue_closing(ctx, grp[g]));
   RL_HIP(join_streams(ctx, std::exchange(fork.n, 1)));
   RL_HIP(ar.end());
   return RL_OK;
 }
-#undef MT_K
-#undef MT_KT
-}  // namespace
+}  // extern "C++"
 
-int rl_mintime_solve_batch_dev(rl_ctx* ctx, const double* model, int B, int N, const double* s, const double* kappa,
-                               const double* left, const double* right, int bounds_per_instance, double margin,
-                               double track_length, double average_track_width, double speed_cap, double* X, double* U,
-                               double* T, int max_iter, double tol, double* stats) {
-  return mintime_solve_common(ctx, model, false, B, N, s, kappa, left, right, bounds_per_instance, margin, track_length,
-                              average_track_width, speed_cap, X, U, T, max_iter, tol, stats, false);
+// A checked call on device pointers: the problem as the model-blind kernels take it, the table of a table call -- and the one
+// place where the form of the solve is chosen.
+int mt_solve(rl_ctx* ctx, const MtCall& c) {
+  rl::MtProblem P;
+  P.N = c.N; P.bounds_per_instance = c.bounds_per_instance ? 1 : 0;
+  P.margin = c.margin; P.track_length = c.track_length;   // NaN in a tracks call: the kernels take it from the instance's row
+  P.s = c.s; P.kappa = c.kappa; P.left = c.left; P.right = c.right;
+  std::vector<double> rows;   // a table call: p | sw | se (| track_length | track), kMtRow doubles per instance
+  if (c.table()) {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (double& v : P.p) v = nan;
+    for (double& v : P.sw) v = nan;
+    for (double& v : P.se) v = nan;
+    rows.assign((size_t)c.B * rl::kMtRow, 0.0);
+    mt_build_rows(rows.data(), c);
+  } else {
+    for (int i = 0; i < rl::DT_NPARAM; ++i) P.p[i] = c.model[i];
+    mt_scales(c.model, c.average_track_width, c.speed_cap, P.sw, P.se);
+  }
+  if (c.tr) return mt_solve_as<rl::MtProblemT>(ctx, c, P, rows);
+  return c.model_rows ? mt_solve_as<rl::MtProblemV>(ctx, c, P, rows) : mt_solve_as<rl::MtProblem>(ctx, c, P, rows);
 }
 
-int rl_mintime_solve_vehicles_dev(rl_ctx* ctx, const double* models, int B, int N, const double* s, const double* kappa,
-                                  const double* left, const double* right, int bounds_per_instance, double margin,
-                                  double track_length, double average_track_width, double speed_cap, double* X, double* U,
-                                  double* T, int max_iter, double tol, double* stats) {
-  return mintime_solve_common(ctx, models, true, B, N, s, kappa, left, right, bounds_per_instance, margin, track_length,
-                              average_track_width, speed_cap, X, U, T, max_iter, tol, stats, false);
-}
-
-// the host entries: stage the arrays, run the shared function with the poll, bring the results down
-static int mintime_solve_host(rl_ctx* ctx, const double* model, bool vehicles, int B, int N, const double* s, const double* kappa,
-                              const double* left, const double* right, int bounds_per_instance, double margin,
-                              double track_length, double average_track_width, double speed_cap, double* X, double* U,
-                              double* T, int max_iter, double tol, double* stats) {
-  if (!ctx || !left || !right) return fail(RL_ERR_ARG, "null argument");   // what is read here; the shared function checks the rest
-  if (B <= 0 || N < 8) return fail(RL_ERR_ARG, "bad sizes (N >= 8 nodes)");
-  const size_t bn = (size_t)B * N, nb_ = bounds_per_instance ? bn : (size_t)N;
-  for (size_t i = 0; i < nb_; ++i)
-    if (!(right[i] + margin < left[i] - margin)) return fail(RL_ERR_ARG, "track narrower than the vehicle plus margins (min_time_optimizer.py:135)");
+// the host entries: stage the arrays of a checked call, solve with the poll, bring the results down
+int mt_stage_and_solve(rl_ctx* ctx, MtCall c) {
+  const size_t bn = (size_t)c.B * c.N, nb_ = c.bounds_per_instance ? bn : (size_t)c.N, ns = (size_t)(c.tr ? c.tr->T : 1) * c.N;
   Staging sg(ctx);
-  const double *ds = sg.in(s, N), *dk = sg.in(kappa, N), *dl = sg.in(left, nb_), *dr = sg.in(right, nb_);
-  double *dX = sg.inout(X, bn * 6), *dU = sg.inout(U, bn * 4), *dT = sg.inout(T, bn);
-  double* dst = sg.out(stats, (size_t)B * rl::kMtStats);
-  sg.run([&] {
-    return mintime_solve_common(ctx, model, vehicles, B, N, ds, dk, dl, dr, bounds_per_instance, margin, track_length,
-                                average_track_width, speed_cap, dX, dU, dT, max_iter, tol, dst, true);
-  });
+  c.s = sg.in(c.s, ns); c.kappa = sg.in(c.kappa, ns); c.left = sg.in(c.left, nb_); c.right = sg.in(c.right, nb_);
+  c.X = sg.inout(c.X, bn * 6); c.U = sg.inout(c.U, bn * 4); c.T = sg.inout(c.T, bn);
+  c.stats = sg.out(c.stats, (size_t)c.B * rl::kMtStats);
+  c.poll = true;
+  sg.run([&] { return mt_solve(ctx, c); });
   return sg.finish();
 }
 
-int rl_mintime_solve_batch(rl_ctx* ctx, const double* model, int B, int N, const double* s, const double* kappa,
-                           const double* left, const double* right, int bounds_per_instance, double margin,
-                           double track_length, double average_track_width, double speed_cap, double* X, double* U,
-                           double* T, int max_iter, double tol, double* stats) {
-  return mintime_solve_host(ctx, model, false, B, N, s, kappa, left, right, bounds_per_instance, margin, track_length,
-                            average_track_width, speed_cap, X, U, T, max_iter, tol, stats);
+}  // namespace
+
+// The six entries: fill the record (the arguments in the record's order), check it, then solve (device pointers) or stage and
+// solve (host pointers).  model_rows is what tells a vehicles entry from its shared-model twin.
+int rl_mintime_solve_batch_dev(rl_ctx* ctx, const double* model, int B, int N, const double* s, const double* kappa, const double* left,
+                               const double* right, int bounds_per_instance, double margin, double track_length, double average_track_width,
+                               double speed_cap, double* X, double* U, double* T, int max_iter, double tol, double* stats) {
+  const MtCall c{model, false, B, N, s, kappa, left, right, bounds_per_instance, margin, X, U, T, stats, max_iter, tol, track_length, average_track_width, speed_cap};
+  RL_TRY(mt_check_call(ctx, c, false));
+  return mt_solve(ctx, c);
 }
 
-int rl_mintime_solve_vehicles(rl_ctx* ctx, const double* models, int B, int N, const double* s, const double* kappa,
-                              const double* left, const double* right, int bounds_per_instance, double margin,
-                              double track_length, double average_track_width, double speed_cap, double* X, double* U,
-                              double* T, int max_iter, double tol, double* stats) {
-  if (!models) return fail(RL_ERR_ARG, "null argument");
-  if (B > 0) RL_TRY(mt_check_models(models, B));   // before anything is staged
-  return mintime_solve_host(ctx, models, true, B, N, s, kappa, left, right, bounds_per_instance, margin, track_length,
-                            average_track_width, speed_cap, X, U, T, max_iter, tol, stats);
+int rl_mintime_solve_vehicles_dev(rl_ctx* ctx, const double* models, int B, int N, const double* s, const double* kappa, const double* left,
+                                  const double* right, int bounds_per_instance, double margin, double track_length, double average_track_width,
+                                  double speed_cap, double* X, double* U, double* T, int max_iter, double tol, double* stats) {
+  const MtCall c{models, true, B, N, s, kappa, left, right, bounds_per_instance, margin, X, U, T, stats, max_iter, tol, track_length, average_track_width, speed_cap};
+  RL_TRY(mt_check_call(ctx, c, false));
+  return mt_solve(ctx, c);
+}
+
+int rl_mintime_solve_batch(rl_ctx* ctx, const double* model, int B, int N, const double* s, const double* kappa, const double* left,
+                           const double* right, int bounds_per_instance, double margin, double track_length, double average_track_width,
+                           double speed_cap, double* X, double* U, double* T, int max_iter, double tol, double* stats) {
+  const MtCall c{model, false, B, N, s, kappa, left, right, bounds_per_instance, margin, X, U, T, stats, max_iter, tol, track_length, average_track_width, speed_cap};
+  RL_TRY(mt_check_call(ctx, c, true));
+  return mt_stage_and_solve(ctx, c);
+}
+
+int rl_mintime_solve_vehicles(rl_ctx* ctx, const double* models, int B, int N, const double* s, const double* kappa, const double* left,
+                              const double* right, int bounds_per_instance, double margin, double track_length, double average_track_width,
+                              double speed_cap, double* X, double* U, double* T, int max_iter, double tol, double* stats) {
+  const MtCall c{models, true, B, N, s, kappa, left, right, bounds_per_instance, margin, X, U, T, stats, max_iter, tol, track_length, average_track_width, speed_cap};
+  RL_TRY(mt_check_call(ctx, c, true));
+  return mt_stage_and_solve(ctx, c);
 }
 
 // The host half of a vehicles (T = 0: the scalars average_track_width[0], speed_cap[0]) or a tracks call (T >= 1) without a
@@ -2080,55 +2097,37 @@ int rl_mintime_solve_vehicles(rl_ctx* ctx, const double* models, int B, int N, c
 int rl_debug_mt_rows(const double* models, int models_per_instance, int B, int T, const int* track_of, const double* track_length,
                      const double* average_track_width, const double* speed_cap, double* rows) {
   if (!models || !rows || !average_track_width || !speed_cap || B <= 0 || T < 0) return fail(RL_ERR_ARG, "null argument or bad sizes");
-  const MtTracks tr{T, track_of, track_length, average_track_width, speed_cap, models_per_instance ? 1 : 0};
-  if (T > 0) RL_TRY(mt_check_tracks(tr, models, B));
-  else RL_TRY(mt_check_models(models, B));
+  const MtTracks tr{T, track_of, track_length, average_track_width, speed_cap};
+  MtCall c{models, T == 0 || models_per_instance, B};
+  c.average_track_width = average_track_width[0]; c.speed_cap = speed_cap[0]; c.tr = T > 0 ? &tr : nullptr;
+  RL_TRY(mt_check_table(c));
   std::fill(rows, rows + (size_t)B * rl::kMtRow, 0.0);
-  mt_build_rows(rows, models, B, T > 0 ? &tr : nullptr, average_track_width[0], speed_cap[0]);
+  mt_build_rows(rows, c);
   return RL_OK;
 }
 
-// One centre line per instance: s, kappa [T,N] DEVICE pointers; everything per track or per instance that the host reads
-// (models, track_of, the three arrays [T]) is a HOST array, checked before anything is enqueued.
-int rl_mintime_solve_tracks_dev(rl_ctx* ctx, const double* models, int models_per_instance, int B, int N, int T,
-                                const int* track_of, const double* s, const double* kappa, const double* left,
-                                const double* right, double margin, const double* track_length,
-                                const double* average_track_width, const double* speed_cap, double* X, double* U,
-                                double* Tn, int max_iter, double tol, double* stats) {
-  const MtTracks tr{T, track_of, track_length, average_track_width, speed_cap, models_per_instance ? 1 : 0};
-  return mintime_solve_common(ctx, models, true, B, N, s, kappa, left, right, 1, margin, 0.0, 0.0, 0.0, X, U, Tn, max_iter, tol,
-                              stats, false, &tr);
+// One centre line per instance: s, kappa [T,N]; everything per track or per instance that the host reads (models, track_of,
+// the three arrays [T]) is a HOST array in both entries.  The bounds are per instance.
+int rl_mintime_solve_tracks_dev(rl_ctx* ctx, const double* models, int models_per_instance, int B, int N, int T, const int* track_of,
+                                const double* s, const double* kappa, const double* left, const double* right, double margin,
+                                const double* track_length, const double* average_track_width, const double* speed_cap, double* X,
+                                double* U, double* Tn, int max_iter, double tol, double* stats) {
+  const MtTracks tr{T, track_of, track_length, average_track_width, speed_cap};
+  MtCall c{models, models_per_instance != 0, B, N, s, kappa, left, right, 1, margin, X, U, Tn, stats, max_iter, tol};
+  c.tr = &tr;
+  RL_TRY(mt_check_call(ctx, c, false));
+  return mt_solve(ctx, c);
 }
 
-int rl_mintime_solve_tracks(rl_ctx* ctx, const double* models, int models_per_instance, int B, int N, int T,
-                            const int* track_of, const double* s, const double* kappa, const double* left,
-                            const double* right, double margin, const double* track_length,
-                            const double* average_track_width, const double* speed_cap, double* X, double* U, double* Tn,
-                            int max_iter, double tol, double* stats) {
-  if (!ctx || !models || !s || !kappa || !left || !right) return fail(RL_ERR_ARG, "null argument");
-  if (B <= 0 || N < 8) return fail(RL_ERR_ARG, "bad sizes (N >= 8 nodes)");
-  const MtTracks tr{T, track_of, track_length, average_track_width, speed_cap, models_per_instance ? 1 : 0};
-  RL_TRY(mt_check_tracks(tr, models, B));   // before anything is staged
-  for (int t = 0; t < T; ++t) {
-    const double *st = s + (size_t)t * N, *kt = kappa + (size_t)t * N;
-    for (int j = 0; j < N; ++j) {
-      if (!std::isfinite(kt[j])) return fail(RL_ERR_ARG, "tracks: track " + std::to_string(t) + ": kappa is not finite at node " + std::to_string(j));
-      if (!(st[j] >= 0.0 && st[j] < track_length[t] && (j == 0 || st[j] > st[j - 1])))
-        return fail(RL_ERR_ARG, "tracks: track " + std::to_string(t) + ": s must increase strictly within [0, track_length) (node " + std::to_string(j) + ")");
-    }
-  }
-  const size_t bn = (size_t)B * N, tn = (size_t)T * N;
-  for (size_t i = 0; i < bn; ++i)
-    if (!(right[i] + margin < left[i] - margin)) return fail(RL_ERR_ARG, "track narrower than the vehicle plus margins (min_time_optimizer.py:135)");
-  Staging sg(ctx);
-  const double *ds = sg.in(s, tn), *dk = sg.in(kappa, tn), *dl = sg.in(left, bn), *dr = sg.in(right, bn);
-  double *dX = sg.inout(X, bn * 6), *dU = sg.inout(U, bn * 4), *dT = sg.inout(Tn, bn);
-  double* dst = sg.out(stats, (size_t)B * rl::kMtStats);
-  sg.run([&] {
-    return mintime_solve_common(ctx, models, true, B, N, ds, dk, dl, dr, 1, margin, 0.0, 0.0, 0.0, dX, dU, dT, max_iter, tol, dst,
-                                true, &tr);
-  });
-  return sg.finish();
+int rl_mintime_solve_tracks(rl_ctx* ctx, const double* models, int models_per_instance, int B, int N, int T, const int* track_of,
+                            const double* s, const double* kappa, const double* left, const double* right, double margin,
+                            const double* track_length, const double* average_track_width, const double* speed_cap, double* X,
+                            double* U, double* Tn, int max_iter, double tol, double* stats) {
+  const MtTracks tr{T, track_of, track_length, average_track_width, speed_cap};
+  MtCall c{models, models_per_instance != 0, B, N, s, kappa, left, right, 1, margin, X, U, Tn, stats, max_iter, tol};
+  c.tr = &tr;
+  RL_TRY(mt_check_call(ctx, c, true));
+  return mt_stage_and_solve(ctx, c);
 }
 
 // ---- the bicycle min-time NLP (rl_bicycle.hpp)

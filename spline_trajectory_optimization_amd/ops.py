@@ -9,6 +9,7 @@ public *_host / *_torch functions are thin wrappers around it.
 """
 import contextlib
 import ctypes
+import functools
 
 import numpy as np
 
@@ -956,7 +957,39 @@ def mintime_solve_torch(model, s, kappa, left, right, margin, track_length, X, U
                           average_track_width, speed_cap, max_iter, tol, None)
 
 
-_DT_POSITIVE = ("Fd_max", "delta_max", "mass", "Pmax", "mu", "Td", "Tb", "Tdelta")   # and |Fb_max|: what the library checks per row
+def _models_table(models, B, params, checks):
+    """dt_models_table / bk_models_table: B model dicts or an array -> the checked float64 table [B, len(params)].  `checks`:
+    (predicate of a row, what it must be) in the order the library looks at a row, after every parameter being finite."""
+    if len(models) > 0 and isinstance(models[0], dict):
+        tab = np.array([[float(m[k]) for k in params] for m in models], dtype=np.float64)
+    else:
+        tab = np.array(models, dtype=np.float64, order="C")
+    if tab.ndim != 2 or tab.shape[1] != len(params) or tab.shape[0] == 0:
+        raise ValueError(f"models: expected B dicts or an array [B, {len(params)}], got shape {tab.shape}")
+    if B is not None and tab.shape[0] != B:
+        raise ValueError(f"models: {tab.shape[0]} vehicles for a batch of {B} instances")
+    for b, row in enumerate(tab):
+        if not np.all(np.isfinite(row)):
+            raise ValueError(f"models: instance {b}: parameter {params[int(np.flatnonzero(~np.isfinite(row))[0])]} is not finite")
+        for ok, what in checks:
+            if not ok(row):
+                raise ValueError(f"models: instance {b}: {what}")
+    return np.ascontiguousarray(tab)
+
+
+def _positive(params, *names):
+    return [(lambda row, i=params.index(k): row[i] > 0.0, f"{k} must be > 0") for k in names]
+
+
+def _models_arg(table, models, B):
+    """(host table, models_per_instance) of a `models` argument: one dict (or one row) for all, or B of them."""
+    if isinstance(models, dict) or (not isinstance(models, (list, tuple)) and np.ndim(models) == 1):
+        return table([models]), 0
+    return table(models, B), 1
+
+
+_DT_CHECKS = [(lambda row: abs(row[DT_PARAMS.index("Fb_max")]) > 0.0, "|Fb_max| must be > 0")] + \
+    _positive(DT_PARAMS, "Fd_max", "delta_max", "mass", "Pmax", "mu", "Td", "Tb", "Tdelta")   # what the library checks per row
 
 
 def dt_models_table(models, B=None):
@@ -964,23 +997,10 @@ def dt_models_table(models, B=None):
     of B model dicts (the reference's keys) or an array of that shape.  Checks what the library checks, before anything
     reaches it: B (when given), every row finite, and Fd_max, |Fb_max|, delta_max, mass, Pmax, mu, Td, Tb, Tdelta > 0 --
     a ValueError names the first bad instance."""
-    if len(models) > 0 and isinstance(models[0], dict):
-        tab = np.array([[float(m[k]) for k in DT_PARAMS] for m in models], dtype=np.float64)
-    else:
-        tab = np.array(models, dtype=np.float64, order="C")
-    if tab.ndim != 2 or tab.shape[1] != len(DT_PARAMS) or tab.shape[0] == 0:
-        raise ValueError(f"models: expected B dicts or an array [B, {len(DT_PARAMS)}], got shape {tab.shape}")
-    if B is not None and tab.shape[0] != B:
-        raise ValueError(f"models: {tab.shape[0]} vehicles for a batch of {B} instances")
-    for b, row in enumerate(tab):
-        if not np.all(np.isfinite(row)):
-            raise ValueError(f"models: instance {b}: parameter {DT_PARAMS[int(np.flatnonzero(~np.isfinite(row))[0])]} is not finite")
-        if not abs(row[DT_PARAMS.index("Fb_max")]) > 0.0:
-            raise ValueError(f"models: instance {b}: |Fb_max| must be > 0")
-        for k in _DT_POSITIVE:
-            if not row[DT_PARAMS.index(k)] > 0.0:
-                raise ValueError(f"models: instance {b}: {k} must be > 0")
-    return np.ascontiguousarray(tab)
+    return _models_table(models, B, DT_PARAMS, _DT_CHECKS)
+
+
+_dt_models = functools.partial(_models_arg, dt_models_table)
 
 
 def mintime_solve_vehicles(models, s, kappa, left, right, margin, track_length, X0, U0, T0, average_track_width=7.0,
@@ -1003,13 +1023,6 @@ def mintime_solve_vehicles_torch(models, s, kappa, left, right, margin, track_le
     _assert_cuda_f64(s, kappa, left, right, X, U, T)
     return _mintime_solve(_Torch, tab, True, s, kappa, left, right, margin, track_length, X, U, T, average_track_width,
                           speed_cap, max_iter, tol, None)
-
-
-def _dt_models(models, B):
-    """(host table, models_per_instance) of a `models` argument: one dict (or one row [28]) for all, or B of them."""
-    if isinstance(models, dict) or (not isinstance(models, (list, tuple)) and np.ndim(models) == 1):
-        return dt_models_table([models]), 0
-    return dt_models_table(models, B), 1
 
 
 def mintime_track_arrays(B, T, track_of, track_length, average_track_width, speed_cap):
@@ -1153,7 +1166,8 @@ def bicycle_solve_torch(model, P0, yaw, dl, dr, X, U, T, max_iter=200, tol=1e-6)
     return _bicycle_solve(_Torch, model, P0, yaw, dl, dr, X, U, T, max_iter, tol, None)
 
 
-_BK_POSITIVE = ("L", "delta_max", "v_max", "delta_dot_max", "acc_max")   # and a_lon_max > a_lon_min: what the library checks per row
+_BK_CHECKS = _positive(BK_PARAMS, "L", "delta_max", "v_max", "delta_dot_max", "acc_max") + \
+    [(lambda row: row[BK_PARAMS.index("a_lon_max")] > row[BK_PARAMS.index("a_lon_min")], "a_lon_max must be > a_lon_min")]   # as the library
 
 
 def bk_models_table(models, B=None):
@@ -1161,30 +1175,10 @@ def bk_models_table(models, B=None):
     model dicts (the reference test's keys) or an array of that shape.  Checks what the library checks, before anything
     reaches it: B (when given), every row finite, L, delta_max, v_max, delta_dot_max, acc_max > 0 and a_lon_max > a_lon_min
     -- a ValueError names the first bad instance."""
-    if len(models) > 0 and isinstance(models[0], dict):
-        tab = np.array([[float(m[k]) for k in BK_PARAMS] for m in models], dtype=np.float64)
-    else:
-        tab = np.array(models, dtype=np.float64, order="C")
-    if tab.ndim != 2 or tab.shape[1] != len(BK_PARAMS) or tab.shape[0] == 0:
-        raise ValueError(f"models: expected B dicts or an array [B, {len(BK_PARAMS)}], got shape {tab.shape}")
-    if B is not None and tab.shape[0] != B:
-        raise ValueError(f"models: {tab.shape[0]} vehicles for a batch of {B} instances")
-    for b, row in enumerate(tab):
-        if not np.all(np.isfinite(row)):
-            raise ValueError(f"models: instance {b}: parameter {BK_PARAMS[int(np.flatnonzero(~np.isfinite(row))[0])]} is not finite")
-        for k in _BK_POSITIVE:
-            if not row[BK_PARAMS.index(k)] > 0.0:
-                raise ValueError(f"models: instance {b}: {k} must be > 0")
-        if not row[BK_PARAMS.index("a_lon_max")] > row[BK_PARAMS.index("a_lon_min")]:
-            raise ValueError(f"models: instance {b}: a_lon_max must be > a_lon_min")
-    return np.ascontiguousarray(tab)
+    return _models_table(models, B, BK_PARAMS, _BK_CHECKS)
 
 
-def _bk_models(models, B):
-    """(host table, models_per_instance) of a `models` argument: one dict (or one row [8]) for all, or B of them."""
-    if isinstance(models, dict) or (not isinstance(models, (list, tuple)) and np.ndim(models) == 1):
-        return bk_models_table([models]), 0
-    return bk_models_table(models, B), 1
+_bk_models = functools.partial(_models_arg, bk_models_table)
 
 
 def _bk_lines(A, B, N, P0, yaw):

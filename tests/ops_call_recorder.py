@@ -10,7 +10,8 @@ valid shapes; `pkg` is the imported package, so the same file runs against a che
     python tests/ops_call_recorder.py --root CHECKOUT --out tests/golden/ops_calls_torch.json --torch    (needs a GPU)
 
 The goldens of tests/test_ops_calls_*.py were written this way from the commit before the wrappers were folded into one body
-per entry point, and are not regenerated from the code under test.
+per entry point, and are not regenerated from the code under test.  The records of `per_instance_cases` (the tracks and lines
+entries) were added to them from the commit before the two model tables of ops were folded into one helper (e7b9542).
 """
 import contextlib
 import ctypes
@@ -233,6 +234,44 @@ def solve_batch_cases(L):
     ]
 
 
+def per_instance_cases(ops, dev=lambda a: a):
+    """(case, host name, torch name | None, args, kwargs) of the entries with one centre line, one line or one vehicle per
+    instance: one model and B models (dicts and the table), track_of given and None, shared and per-instance lines, and one
+    refusal.  `dev` puts an array where the torch form takes a tensor; models, track_of and the per-track arrays are host
+    arguments in both forms."""
+    dt, bk = _models(ops)
+    bk = dict(bk, a_lon_min=-bk["a_lon_min"])   # the per-instance entries check the rows: a_lon_max > a_lon_min
+    dts = [dict(dt, mass=dt["mass"] + b) for b in range(B)]
+    bks =[dict(bk, L=bk["L"] + b) for b in range(B)]
+    left, right = dev(_arr((B, N), 80)), dev(_arr((B, N), 81))
+    X, U, T = dev(_arr((B, N, 6), 77)), dev(_arr((B, N, 4), 78)), dev(_arr((B, N), 79))
+    s3, k3, s2, k2 = dev(_arr((3, N), 86)), dev(_arr((3, N), 87)), dev(_arr((B, N), 88)), dev(_arr((B, N), 89))
+    L3, L2 = np.array([100.0, 120.0, 140.0]), [100.0, 120.0]
+    mt = ("mintime_solve_tracks", "mintime_solve_tracks_torch")
+    c = [("mintime_solve_tracks/one_model_track_of", *mt, [dt, [2, 0], s3, k3, left, right, 0.5, L3, X, U, T], {}),
+         ("mintime_solve_tracks/models_identity", *mt, [dts, None, s2, k2, left, right, 1, L2, X, U, T],
+          {"average_track_width": [6.0, 6.5], "speed_cap": 25, "max_iter": 7, "tol": 1e-3}),
+         ("mintime_solve_tracks/table_track_of", *mt, [ops.dt_models_table(dts), np.array([1, 1]), s2, k2, left, right, 0.5, L2, X, U, T],
+          {"speed_cap": np.array([25.0, 30.0]), "max_iter": 9}),
+         ("mintime_solve_tracks/one_row_identity", *mt, [ops.dt_models_table([dt])[0], None, s2, k2, left, right, 0.5, L2, X, U, T], {}),
+         ("mintime_solve_tracks/identity_refused", *mt, [dt, None, s3, k3, left, right, 0.5, L3, X, U, T], {})]
+    XB, UB = dev(_arr((B, N, 5), 82)), dev(_arr((B, N, 2), 83))
+    P0, yaw, P0B, yawB = dev(_arr((N, 2), 84)), dev(_arr((N,), 85)), dev(_arr((B, N, 2), 90)), dev(_arr((B, N), 91))
+    dl, dr = dev(_arr((N,), 75)), dev(_arr((N,), 76))
+    bl = ("bicycle_solve_lines", "bicycle_solve_lines_torch")
+    c += [("bicycle_solve_lines/one_model_shared_line", *bl, [bk, P0, yaw, dl, dr, XB, UB, T], {}),
+          ("bicycle_solve_lines/one_model_lines", *bl, [bk, P0B, yawB, left, right, XB, UB, T], {"max_iter": 11, "tol": 1e-4}),
+          ("bicycle_solve_lines/models_shared_line_rows", *bl, [bks, P0, yaw, left, right, XB, UB, T], {}),
+          ("bicycle_solve_lines/table_lines", *bl, [ops.bk_models_table(bks), P0B, yawB, left, right, XB, UB, T], {"max_iter": 5}),
+          ("bicycle_solve_lines/lines_shared_bounds_refused", *bl, [bk, P0B, yawB, dl, dr, XB, UB, T], {})]
+    ev = ("bicycle_eval_nodes_lines", None)   # a host form only
+    c += [("bicycle_eval_nodes_lines/one_model_shared_line", *ev, [bk, P0, yaw, XB, UB, T], {}),
+          ("bicycle_eval_nodes_lines/one_row_lines", *ev, [ops.bk_models_table([bk])[0], P0B, yawB, XB, UB, T], {}),
+          ("bicycle_eval_nodes_lines/models_lines", *ev, [bks, P0B.tolist(), yawB, XB, UB, T], {}),
+          ("bicycle_eval_nodes_lines/table_shared_line", *ev, [ops.bk_models_table(bks), P0, yaw, XB, UB, T], {})]
+    return c
+
+
 def record_host(pkg):
     """{case: record} of every public host entry point of pkg.ops."""
     ops, L = pkg.ops, pkg._lib
@@ -288,6 +327,8 @@ def record_host(pkg):
     case("bicycle_eval_nodes", "bicycle_eval_nodes", bk, P0, yaw, XB, UB, T)
     case("bicycle_solve_batch/shared", "bicycle_solve_batch", bk, P0, yaw, left, right, XB, UB, T)
     case("bicycle_solve_batch/rows", "bicycle_solve_batch", bk, P0, yaw.tolist(), rows_l, rows_r, XB, UB, T, max_iter=11, tol=1e-4)
+    for name, host, _, args, kwargs in per_instance_cases(ops):
+        case(name, host, *args, **kwargs)
     return out
 
 
@@ -358,6 +399,9 @@ def record_torch(pkg):
     XB, UB, P0, yaw = up(_arr((B, N, 5), 82)), up(_arr((B, N, 2), 83)), up(_arr((N, 2), 84)), up(_arr((N,), 85))
     case("bicycle_solve/shared", "bicycle_solve_torch", bk, P0, yaw, left, right, XB, UB, T)
     case("bicycle_solve/rows", "bicycle_solve_torch", bk, P0, yaw, rows_l, rows_r, XB, UB, T, max_iter=11, tol=1e-4)
+    for name, _, fn, args, kwargs in per_instance_cases(ops, up):
+        if fn is not None:
+            case(name, fn, *args, **kwargs)
     return out
 
 

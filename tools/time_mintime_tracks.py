@@ -3,9 +3,10 @@
 README's batch size: MGKT at 1 m (N = 828), B = 1024.  ONE run on one MI355X; host calls timed on the wall clock (copies of the
 guess and of the solution included), one warm-up at the full batch size first, --repeats timed calls per leg, their median /
 min / max.  Every leg records how many instances converged and the mean iteration count.
-  (a) --compare-lib OTHER.so: the shared-model entry and the vehicles entry (B rows of MODEL) on this build and on another
-      build of the library (the parent commit's), in child processes that alternate, --rounds each; "not slower" = this
-      build's median of rounds lies inside the range the other build's rounds show by themselves, which is stated;
+  (a) --compare-lib OTHER.so: the shared-model entry, the vehicles entry (B rows of MODEL) and the tracks entry (B equal
+      tracks, as in (b)) on this build and on another build of the library (the parent commit's), in child processes that
+      alternate, --rounds each; "not slower" = this build's median of rounds lies inside the range the other build's rounds
+      show by themselves, which is stated, as is whether it lies below their largest plus that range;
   (b) B equal tracks and one model through the new entry (T = B, track_of = NULL) against the shared-model entry on the same
       width-perturbed batch: the same bits, the ratio of the medians;
   (c) B uniformly scaled copies of the circuit (0.8 x .. 1.25 x: s, L, the distances and average_track_width times f, kappa /
@@ -63,12 +64,13 @@ def compare(a, _lib, res):
             print(f"round {r} {who}: {rounds[who][-1]}", file=sys.stderr, flush=True)
     order = "other, this, other, this, ..." if a.first == "other" else "this, other, this, other, ..."
     cmp = {"rounds": a.rounds, "order": order, "this": rounds["this"], "other": rounds["other"]}
-    for entry in ("shared", "vehicles"):
+    for entry in ("shared", "vehicles", "tracks"):
         mine = [r[entry]["median_s"] for r in rounds["this"]]; theirs = [r[entry]["median_s"] for r in rounds["other"]]
         cmp[entry] = {"this_median_of_rounds_s": float(np.median(mine)), "other_median_of_rounds_s": float(np.median(theirs)),
                       "other_min_s": float(min(theirs)), "other_max_s": float(max(theirs)),
                       "margin_s": float(max(theirs) - min(theirs)),
-                      "this_within_other_range": bool(np.median(mine) <= max(theirs))}
+                      "this_within_other_range": bool(np.median(mine) <= max(theirs)),
+                      "this_within_other_max_plus_margin": bool(np.median(mine) <= 2 * max(theirs) - min(theirs))}
     res["a_existing_entries_this_build_vs_other" + ("" if a.first == "other" else "_this_first")] = cmp
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
@@ -105,7 +107,9 @@ def main():
     shared_t, shared = timed(lambda: prob.solve_batch(left, right, **kw), a.repeats)
     if a.existing_only:
         veh_t, veh = timed(lambda: prob.solve_batch(left, right, models=[prob.model] * B, **kw), a.repeats)
-        print("EXISTING " + json.dumps({"shared": dict(shared_t, **report(shared[3])), "vehicles": dict(veh_t, **report(veh[3]))}))
+        trk_t, trk = timed(lambda: prob.solve_batch(left, right, tracks=[prob] * B, **kw), a.repeats)   # T = B, track_of = NULL, as in (b)
+        print("EXISTING " + json.dumps({"shared": dict(shared_t, **report(shared[3])), "vehicles": dict(veh_t, **report(veh[3])),
+                                        "tracks": dict(trk_t, **report(trk[3]))}))
         return
     res = {"B": B, "N": int(prob.N), "repeats": a.repeats, "max_iter": MAX_ITER, "tol": TOL, "device": torch.cuda.get_device_name(0),
            "timed": "host calls on the wall clock, host<->device copies of guess and solution included; one warm-up per leg first"}

@@ -90,8 +90,10 @@ RL_DT Dual<ND, T> chain(Dual<ND, T> a, const T& v, const T& dv) { a.v = v; RL_DU
 // them once per direction pair and node (113 times per node and iteration): the library versions (185 / 85
 // instructions for sincos / atan, with a large-argument path that the model's angles never take) were half of those
 // kernels' instructions.  These are the fdlibm kernels (Sun Microsystems' k_sin.c / k_cos.c / s_atan.c coefficients)
-// written branch-free for the wavefront: Cody-Waite reduction with a two-part pi/2 (the model's arguments are angles
-// of a few radians; the absolute error grows like 1e-16 |x|, there is no large-argument path), polynomial on
+// written branch-free for the wavefront: Cody-Waite reduction with a two-part pi/2 (the model's arguments are angles;
+// the tests pin it against a 50-digit reference for |x| <= 4 pi, every quadrant and both signs, and up to |x| = 12.7 through the
+// yaws of the `wraps` family (fixture G16, tests/test_nlp_highprec_gpu.py); the absolute error grows like 1e-16 |x|, there is no
+// large-argument path), polynomial on
 // [-pi/4, pi/4], quadrant by select; atan with its four break points as selects and one division.  Accuracy ~1 ulp
 // (the reference's numpy / CasADi values differ from any libm by as much).
 __device__ __forceinline__ void m_sincos(double x, double& s, double& c) {
